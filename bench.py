@@ -2,7 +2,11 @@
 """Headline benchmark: spin-flip attempts per second of standardMC on GraphRRG(N=4096, K=3, +-J), beta = 1,
 8192 replicas per MI355X (BASELINE.json configs[1]).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline (with `roofline`, read off the timed region's own events);
+--dump-outputs DIR also writes the last step's results as .npy files (dump_outputs).  --full adds everything else, after the timed region:
+the oracle replay of that region (`verified`), the CPU baseline, the synchronous-call rates, the secondary workloads, the copy bandwidth.
 
 One "step" = one sampling call (rrrmc_standard_mc_async) of ITERS iterations for every replica with the
 configuration already resident in HBM; results (energy samples, accepted counts) stay in HBM inside the
@@ -307,6 +311,33 @@ def verify_timed_region(O, X, C_start, C_end, Es_last, acc_last, it0, steps, ite
     return {"replicas": [int(replica0 + r) for r in replicas], "ok": [res.get(r, False) for r in replicas],
             "iterations_replayed_per_replica": int(iters) * int(steps), "seconds": time.perf_counter() - t0,
             "compared": "final configuration, energy samples of the last step, accepted count of the last step (bit-exact)"}
+
+
+DUMP_CHAIN_BYTES = 44 * 10**6    # --dump-outputs: energies + accepted counts (+ replica ids): all 8192 replicas at the default size (34 MB)
+DUMP_SPIN_REPLICAS = 1024       # configurations: 1024 replicas x 4096 spins as float32 (17 MB); with the above, under 64 MB in all
+
+
+def _dump_rows(rng, n, k):
+    """all n replicas when k >= n, else a sorted, seeded sample of k of them (the same rows in every run of the same arguments)"""
+    return np.arange(n) if k >= n else np.sort(rng.choice(n, k, replace=False))
+
+
+def dump_outputs(path, Es, acc, s, replica0):
+    """--dump-outputs: what the last timed step handed its caller, as float .npy files in `path` — energies.npy (replicas x samples; integer
+    energies, exact in float32) and accepted.npy (float64) for the global replica ids in energies_replicas.npy — every replica while they fit
+    DUMP_CHAIN_BYTES —, spins.npy (+-1, float32) for those in spins_replicas.npy, a seeded sample of DUMP_SPIN_REPLICAS.
+    The inputs are seeded, so two builds of the project can be compared file for file."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(SEED)
+    rows = _dump_rows(rng, len(acc), DUMP_CHAIN_BYTES // (4 * Es.shape[1] + 16))
+    np.save(os.path.join(path, "energies.npy"), Es[rows].astype(np.float32))
+    np.save(os.path.join(path, "accepted.npy"), acc[rows].astype(np.float64))
+    np.save(os.path.join(path, "energies_replicas.npy"), (replica0 + rows).astype(np.float64))
+    rows = _dump_rows(rng, len(s), DUMP_SPIN_REPLICAS)
+    x = np.arange(N_SITES)
+    bits = (s[rows][:, x >> 6] >> (x & 63).astype(np.uint64)) & np.uint64(1)       # spin x is bit (x & 63) of word x >> 6 (graphs.Config)
+    np.save(os.path.join(path, "spins.npy"), 2 * bits.astype(np.float32) - 1)
+    np.save(os.path.join(path, "spins_replicas.npy"), (replica0 + rows).astype(np.float64))
 
 
 def device_copy_bandwidth(pkg, device, nbytes=1 << 30, reps=10):
@@ -963,7 +994,10 @@ def run_rank(args):
         dt = float(t.item())
 
     Es, acc = eng.fetch_results()
-    C_end = eng.get_config().s.copy() if verify else None
+    dump = rank == 0 and args.dump_outputs
+    C_end = eng.get_config().s.copy() if verify or dump else None
+    if dump:
+        dump_outputs(args.dump_outputs, Es, acc, C_end, r0)
     C_start = eng.snapshot_get(0).s.copy() if verify else None    # what the timed region started from, read back after it
     acc_rate = float(acc.mean()) / args.iters
     e_mean = float(Es[:, -1].mean()) / N_SITES if Es.shape[1] else float("nan")
@@ -1034,12 +1068,13 @@ def run_rank(args):
             out["roofline"] = roof
             # what the timed region spent outside the dominant kernel, per step: energy(X, C) + planner at the head of every call, launch gaps
             out["host_gap_ms_per_step"] = 1e3 * dt / max(args.steps, 1) - sweep_ms / max(args.steps, 1)
-            try:      # after the timed region: the box's own copy bandwidth, for reference only (peak stays the nominal figure)
-                bw = device_copy_bandwidth(pkg, local_rank)
-                roof["measured_copy_GBps"] = bw
-            except Exception as e:      # never let the side measurement hide the bench line
-                roof["measured_copy_GBps"] = None
-                sys.stderr.write("device copy bandwidth not measured: %r\n" % (e,))
+            if args.full:
+                try:      # after the timed region: the box's own copy bandwidth, for reference only (peak stays the nominal figure)
+                    bw = device_copy_bandwidth(pkg, local_rank)
+                    roof["measured_copy_GBps"] = bw
+                except Exception as e:      # never let the side measurement hide the bench line
+                    roof["measured_copy_GBps"] = None
+                    sys.stderr.write("device copy bandwidth not measured: %r\n" % (e,))
     if rank == 0 and world == 1 and not args.no_secondary:
         # The reference-style SYNCHRONOUS call (src/RRRMC.jl:126 returns Es and C per call): rrrmc_standard_mc + rrrmc_get_spins, i.e. the
         # sweep plus the transposes and the PCIe transfers of the energy samples (R x 1024 Int64) and the configuration.  Never `value`.
@@ -1099,12 +1134,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=ITERS)
     ap.add_argument("--replicas", type=int, default=REPLICAS_PER_GPU)
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the oracle replay of the timed region, the CPU baseline, the synchronous-call rates, the "
+                         "secondary workloads and the device copy bandwidth (each --no-* below drops its part again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's results (rank 0's shard) to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--no-verify", action="store_true", help="skip the oracle replay of the timed region (3 replicas; ~10 s at the default size)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if not args.full:            # a plain run: set up, warm up, time the steps, report
+        args.no_cpu_baseline = args.no_secondary = args.no_verify = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch(args, sys.argv[1:])
     return run_rank(args)

@@ -137,7 +137,8 @@ def test_two_rank_processes_run_the_hip_path_on_their_shards(pkg, oracle, tmp_pa
 
 def test_bench_gpus2_standalone_launcher_on_hardware():
     """`python bench.py --gpus 2` WITHOUT torchrun: spawns two ranks and reports n_gpus = 2 with both shards' replicas.  On a 1-GPU
-    box the two ranks share the device (RRRMC_BENCH_SHARE_GPU=1: gloo rendezvous); without that switch the request is refused."""
+    box the two ranks share the device (RRRMC_BENCH_SHARE_GPU=1: gloo rendezvous); without that switch the request is refused.  With
+    --full rank 0 replays three replicas of its shard's whole timed region through the oracle (exit 3 on a mismatch)."""
     env = dict(os.environ)
     import torch
     two = torch.cuda.device_count() >= 2
@@ -147,9 +148,10 @@ def test_bench_gpus2_standalone_launcher_on_hardware():
         assert r.returncode == 2 and "only 1 GPU" in r.stderr and not r.stdout.strip()
         env["RRRMC_BENCH_SHARE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--iters", str(1 << 18),
-                        "--replicas", "2048", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=900, env=env)
+                        "--replicas", "2048", "--full", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["verified"] is True
     assert line["n_gpus"] == 2 and line["config"]["replicas_total"] == 4096 and len(line["ms_per_step_per_rank"]) == 2
     assert line["value"] > 0 and 0.05 < line["config"]["acceptance"] < 0.15
     assert line["roofline"]["launches"] == 3

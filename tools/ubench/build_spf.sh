@@ -1,6 +1,6 @@
 #!/bin/bash
 # build tools/ubench/spf_team_bench.out and extract one instantiation's ISA: build_spf.sh [extra hipcc flags]
-cd /root/repo/tools/ubench || exit 1
+cd "$(dirname "$0")" || exit 1
 mkdir -p tmp
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off "$@" spf_team_bench.hip -o spf_team_bench.out -save-temps=obj 2>&1 | grep -v "^$" | head -30
 S=spf_team_bench-hip-amdgcn-amd-amdhsa-gfx950.s
