@@ -59,7 +59,19 @@ enum rrrmc_model {
     /* selectors for rrrmc_ctx_create_multi only (the contexts it makes report RRRMC_MODEL_QUANT_RRG): */
     RRRMC_MODEL_QUANT_SK = 8,    /* GraphQuant over binary GraphSK slices (GraphQSKT, src/QAliases.jl:34-43): rrrmc_ctx_create_quant_sk per device */
     RRRMC_MODEL_QUANT_SKN = 9,   /* GraphQuant over GraphSKNormal slices (GraphQSKNormalT, src/QAliases.jl:45-46): rrrmc_ctx_create_quant_skn per device */
-    RRRMC_MODEL_QUANT_F64 = 10   /* GraphQuant over sparse Float64 slices (GraphQEAT, src/QAliases.jl:50-83): rrrmc_ctx_create_quant_f64 per device */
+    RRRMC_MODEL_QUANT_F64 = 10,  /* GraphQuant over sparse Float64 slices (GraphQEAT, src/QAliases.jl:50-83): rrrmc_ctx_create_quant_f64 per device */
+    /* GraphRobustEnsemble (src/graphs/RE.jl:215-315) over GraphEmpty / binary GraphSK / GraphSKNormal slices: the model of a context made by
+       rrrmc_ctx_create_re, and the selectors of rrrmc_ctx_create_multi for it (N = Nk, M; K ignored) */
+    RRRMC_MODEL_RE_EMPTY = 11,   /* Graph0RE (src/REAliases.jl:20-29) */
+    RRRMC_MODEL_RE_SK = 12,      /* GraphSKRE (src/REAliases.jl:33-38) */
+    RRRMC_MODEL_RE_SKN = 13      /* GraphRobustEnsemble(Nk, M, gamma, beta, GraphSKNormal, J) (test/runtests.jl:90-92) */
+};
+
+/* slice families of rrrmc_ctx_create_re */
+enum rrrmc_re_slice {
+    RRRMC_RE_SLICE_EMPTY = 0,    /* GraphEmpty (src/graphs/Empty.jl): zero residual, zero energy */
+    RRRMC_RE_SLICE_SK = 1,       /* binary GraphSK (src/graphs/SK.jl:28-60): couplings with rrrmc_set_couplings_bits */
+    RRRMC_RE_SLICE_SKN = 2       /* GraphSKNormal (src/graphs/SK.jl:181-210): couplings with rrrmc_set_couplings_dense */
 };
 
 /* Library ABI version (major*10000 + minor*100 + patch). */
@@ -101,8 +113,8 @@ RRRMC_API int32_t rrrmc_ctx_create(rrrmc_ctx **out, int32_t model, int64_t N, in
  * arrive gathered; enqueueing calls return when every device has its work queued, rrrmc_sync / fetch / energy calls run one host
  * thread per device.  rrrmc_last_timing / rrrmc_timing_total report the slowest device.
  *   model  any rrrmc_model; RRRMC_MODEL_QUANT_RRG takes (N = Nk, K, M) as rrrmc_ctx_create_quant does, RRRMC_MODEL_QUANT_SK / _SKN take
- *          (N = Nk, M) as rrrmc_ctx_create_quant_sk / _skn do (K ignored), RRRMC_MODEL_QUANT_F64 takes (N = Nk, K, M) as rrrmc_ctx_create_quant_f64;
- *          M is ignored otherwise.
+ *          (N = Nk, M) as rrrmc_ctx_create_quant_sk / _skn do (K ignored), RRRMC_MODEL_QUANT_F64 takes (N = Nk, K, M) as rrrmc_ctx_create_quant_f64,
+ *          RRRMC_MODEL_RE_EMPTY / _SK / _SKN take (N = Nk, M) as rrrmc_ctx_create_re does (K ignored); M is ignored otherwise.
  */
 RRRMC_API int32_t rrrmc_ctx_create_multi(rrrmc_ctx **out, int32_t model, int64_t N, int64_t K, int64_t M, int64_t R,
                                          const int32_t *device_ids, int32_t ndev, uint32_t replica0);
@@ -223,6 +235,31 @@ RRRMC_API int32_t rrrmc_ctx_create_quant_f64(rrrmc_ctx **out, int64_t Nk, int64_
  * to the same site) — delta_energy sums every entry, neighbors() of the continuous-energy caches is the de-duplicated list (EA.jl:158). */
 RRRMC_API int32_t rrrmc_quant_slice_form(rrrmc_ctx *ctx, int32_t ea_form);
 RRRMC_API int32_t rrrmc_quant_set_field(rrrmc_ctx *ctx, double beta, double fourK);
+/* ---- GraphRobustEnsemble (src/graphs/RE.jl; RRRMC_MODEL_RE_*) -----------------------------------------------------
+ * The Robust Ensemble of M replicas of one graph: the inner graph GraphRE{M,gamma,beta} couples the M replicas of every spin i through
+ * mu_i = sum_k sigma_(i,k) (energy sum_i -log(2 cosh(gamma mu_i)) / beta), and replica k is slice k of a DoubleGraph whose residual is the slice
+ * graph's delta_energy (NOT divided by M, RE.jl:303-310).  All M slices share one coupling set (Gconstr(args...) with the same args).
+ *   N = Nk * M spins per replica of the batch, in the reference's site order: site j (0-based) is spin i = j / M of ensemble replica
+ *   k = j % M (RE.jl:76-95) — in every configuration that crosses this ABI (rrrmc_set_spins / rrrmc_get_spins / rrrmc_init_spins_random, whose
+ *   INIT stream is indexed by j) and in rrrmc_rrr_cache (the class of site j; the ArraySets hold site ids in the reference's member order).
+ *   3 <= M <= 32, N <= 65 535.  Energies are Float64 (_f64 entry points).
+ * rrrmc_ctx_create_re: slice_kind rrrmc_re_slice; then the couplings (rrrmc_set_couplings_bits [Nk rows] for _SK, rrrmc_set_couplings_dense
+ * [Nk x Nk] for _SKN, nothing for _EMPTY) and rrrmc_re_set_params.  Samplers: rrrmc_rrr_mc_async (rrrMC(X::DoubleGraph), src/RRRMC.jl:221-290:
+ * the DeltaECache over L = ceil(M/2) levels; fourK is ignored; streams as GraphQuant's) and rrrmc_standard_mc_async /
+ * rrrmc_standard_mc_f64 (standardMC, SITE + ACCEPT_F64 streams); with the resume, debug-check, timing, results and cache entry points of the
+ * other models.  rrrmc_bkl_mc_async, rrrmc_wtm_mc_async and rrrmc_extremal_opt_async return RRRMC_ERR_UNSUPPORTED. */
+RRRMC_API int32_t rrrmc_ctx_create_re(rrrmc_ctx **out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0);
+/* The type parameters gamma and beta of GraphRE{M,gamma,beta} (beta_graph: the beta inside fk and the mu-energies, not the sampler's): builds the level table
+ * and the mu-energy table on the host (rrrmc_re_tables).  Required before the first sampler or energy call; a change ends a resumed run. */
+RRRMC_API int32_t rrrmc_re_set_params(rrrmc_ctx *ctx, double gamma, double beta_graph);
+/* REenergies(X) (RE.jl:285-301): out[R * M], energy(X1[k], C1[k]) of every slice of every replica for the current configuration, in the
+ * reference's summation order (SK.jl:62-96, 212-237).  Reads the configuration only — unlike the reference's, it does not rebuild the slice
+ * caches, so a hook that calls it leaves the run as it was. */
+RRRMC_API int32_t rrrmc_re_energies(rrrmc_ctx *ctx, double *out);
+/* Host-only (no device needed): dElist[M] = DeltaElist(GraphRE{M,gamma,beta}) = fk(mu) for mu = -(M-1), -(M-3), ..., M-1 (RE.jl:18-26, 53-56; the
+ * upper ceil(M/2) entries are allDeltaE), e0[M+1] = log(2 cosh(gamma mu)) / beta for mu = -M, -M+2, ..., M (RE.jl:90-93), evaluated with libm. */
+RRRMC_API int32_t rrrmc_re_tables(int64_t M, double gamma, double beta, double *dElist, double *e0);
+
 /* rrrMC(X::DoubleGraph, beta, iters; step, staged_thr, staged_thr_fact) (src/RRRMC.jl:221-290) for all R replicas.
  *   fourK = round(2/beta * log(coth(beta * Gamma / M)), digits = 8)  (QT.jl:165) is computed by the caller.
  * Enqueues on the ctx's stream; rrrmc_sync + rrrmc_fetch_results_f64 return Es [R x iters/step] and accepted [R];
@@ -262,7 +299,8 @@ RRRMC_API int32_t rrrmc_extremal_opt_results(rrrmc_ctx *ctx, int64_t *Emin_out, 
  * rrrmc_fetch_results_f64, and rrrmc_extremal_opt_results_f64 for (Emin, Cmin, itmin). */
 RRRMC_API int32_t rrrmc_extremal_opt_results_f64(rrrmc_ctx *ctx, double *Emin_out, uint64_t *Cmin_chunks, int64_t *itmin_out);
 /* parity/debug view of the move-selection cache after the last rrrMC call: pos_out[R * N] = class of every spin
- * (DeltaECache.pos, 0-based a + 2*up), sizes_out[R * 4] = |class k| (DeltaE.jl:63-73).  RRRMC_MODEL_SPARSE_PM1 / _LEVELS (rrrMC and
+ * (DeltaECache.pos, 0-based a + 2*up), sizes_out[R * 4] = |class k| (DeltaE.jl:63-73).  RRRMC_MODEL_RE_*: class a + L*up of every site j,
+ * sizes_out[R * 2L] with L = ceil(M/2).  RRRMC_MODEL_SPARSE_PM1 / _LEVELS (rrrMC and
  * bklMC; class a + L*up) and RRRMC_MODEL_SPARSE_DISCRETIZED: sizes_out[R * 16], class k of replica r at 16 r + k. */
 RRRMC_API int32_t rrrmc_rrr_cache(rrrmc_ctx *ctx, int8_t *pos_out, int32_t *sizes_out);
 

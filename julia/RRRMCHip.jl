@@ -54,6 +54,7 @@ version() = Int(ccall((:rrrmc_version, LIB), Int32, ()))
 # model kinds of include/rrrmc_hip.h
 const SPARSE_PM1, SK_NORMAL, QUANT_RRG, SK_BINARY, SPARSE_F64, SPARSE_DISCRETIZED, SPARSE_LEVELS = 1, 2, 3, 4, 5, 6, 7
 const QUANT_SK, QUANT_SKN, QUANT_F64 = 8, 9, 10      # selectors of rrrmc_ctx_create_multi: GraphQuant over GraphSK / GraphSKNormal / sparse Float64 slices
+const RE_EMPTY, RE_SK, RE_SKN = 11, 12, 13            # GraphRobustEnsemble over GraphEmpty / GraphSK / GraphSKNormal (rrrmc_ctx_create_re; multi selectors)
 
 # rrrmc_ctx_create / rrrmc_ctx_create_quant on one device, rrrmc_ctx_create_multi on several (N = Nk for a GraphQuant)
 function create(model::Integer, N::Integer, K::Integer, M::Integer, R::Integer; device = 0, replica0 = 0, devices = nothing)
@@ -196,6 +197,48 @@ function Ctx(X::RRRMC.QT.GraphQuant{fourK,G}, R::Integer, β::Real; device = 0, 
     check(ccall((:rrrmc_quant_set_field, LIB), Int32, (Ptr{Cvoid}, Float64, Float64), ctx.p, β, fourK), ctx.p)
     return ctx
 end
+
+# ---- GraphRobustEnsemble (src/graphs/RE.jl:215-315): M replicas of one slice graph coupled by GraphRE{M,γ,β} --------------------------
+# spins in the reference's order (site (i-1)M + k = spin i of replica k), so C.s.chunks passes as is; the M slices share one coupling set
+function Ctx(X::RRRMC.RE.GraphRobustEnsemble{M,γ,β,G}, R::Integer; device = 0, replica0 = 0, devices = nothing) where {M,γ,β,G}
+    Nk = X.Nk
+    kind = G <: RRRMC.SK.GraphSK ? 1 : G <: RRRMC.SK.GraphSKNormal ? 2 : G <: RRRMC.Empty.GraphEmpty ? 0 :
+           throw(ArgumentError("the engine runs the Robust Ensemble over GraphEmpty, GraphSK and GraphSKNormal slices, given: $G"))
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    if devices === nothing
+        check(ccall((:rrrmc_ctx_create_re, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, Int64, Int32, UInt32), ref, Nk, M, kind, R, device, replica0))
+    else
+        ref[] = create(RE_EMPTY + kind, Nk, 0, M, R; replica0 = replica0, devices = devices)
+    end
+    ctx = Ctx(ref[], R, Nk * M, true)
+    X1 = X.X1[1]
+    if kind == 1
+        Jc = sk_bits(X1.J)
+        GC.@preserve Jc check(ccall((:rrrmc_set_couplings_bits, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt64}), ctx.p, Jc), ctx.p)
+    elseif kind == 2
+        Jm = Matrix{Float64}(undef, Nk, Nk); for i = 1:Nk; Jm[:, i] = X1.J[i]; end
+        GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
+    end
+    check(ccall((:rrrmc_re_set_params, LIB), Int32, (Ptr{Cvoid}, Float64, Float64), ctx.p, γ, β), ctx.p)
+    return ctx
+end
+# REenergies of every replica of the batch, read on the device from the live configuration: column r = replica r (RE.jl:285-301)
+function re_energies(ctx::Ctx, M::Integer)
+    out = Matrix{Float64}(undef, M, ctx.R)
+    check(ccall((:rrrmc_re_energies, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, out), ctx.p)
+    return out
+end
+# the slices' configurations C1[k] of a GraphRobustEnsemble from a configuration of the whole graph (what energy(X, C) does, RE.jl:271-279):
+# before a user's hook runs, so that the reference's own RRRMC.REenergies(X) reads the sample's configuration (one chain)
+function re_slices!(X::RRRMC.RE.GraphRobustEnsemble{M}, C::RRRMC.Config) where {M}
+    for k = 1:M, i = 1:X.Nk
+        X.C1[k].s[i] = C.s[(i - 1) * M + k]
+    end
+    return X
+end
+re_hook(X, hook) = hook
+re_hook(X::RRRMC.RE.GraphRobustEnsemble, hook::Nothing) = hook
+re_hook(X::RRRMC.RE.GraphRobustEnsemble, hook) = (it, X_, C, a, b) -> (re_slices!(X, C); hook(it, X_, C, a, b))
 
 # ---- configurations ------------------------------------------------------------------------------------------------------------------
 seed!(ctx::Ctx, seed) = seed > 0 && check(ccall((:rrrmc_seed, LIB), Int32, (Ptr{Cvoid}, UInt64), ctx.p, seed), ctx.p)   # seed ≤ 0: keep going (RRRMC.jl:89)
@@ -747,7 +790,7 @@ configs_in(G::OnGPU, C0) = C0 ≡ nothing ? nothing : (C0 isa RRRMC.Config ? RRR
 unwrap1(G::OnGPU, Es::AbstractMatrix) = single(G) ? Es[:, 1] : Es
 unwrap1(G::OnGPU, v::AbstractVector) = single(G) ? v[1] : v
 # the hook of ONE chain takes scalars and the Config (src/RRRMC.jl:61-64); the context-first layer hands vectors over the replicas
-hook1(G::OnGPU, hook) = hook ≡ nothing || !single(G) ? hook : (it, X, Cs, a, b) -> hook(it, X, Cs[1], a[1], b[1])
+hook1(G::OnGPU, hook) = hook ≡ nothing || !single(G) ? hook : (it, X, Cs, a, b) -> re_hook(G.X, hook)(it, X, Cs[1], a[1], b[1])
 
 function RRRMC.standardMC(G::OnGPU, β::Real, iters::Integer; seed = DEFAULT_SEED, step::Integer = 1, hook = nothing,
                           C0::Union{RRRMC.Config,Vector{RRRMC.Config},Nothing} = nothing, quiet::Bool = false)

@@ -26,6 +26,7 @@ SYMBOLS = [
     "rrrmc_ctx_create_quant", "rrrmc_ctx_create_quant_sk", "rrrmc_ctx_create_quant_skn", "rrrmc_ctx_create_quant_f64", "rrrmc_quant_set_field", "rrrmc_quant_slice_form", "rrrmc_rrr_mc_async", "rrrmc_rrr_stats", "rrrmc_rrr_cache", "rrrmc_bkl_mc_async",
     "rrrmc_snapshot_reserve", "rrrmc_snapshot_store", "rrrmc_snapshot_get", "rrrmc_overlaps", "rrrmc_quant_observables",
     "rrrmc_set_graph_f64", "rrrmc_gen_couplings_gauss", "rrrmc_set_graph_discretized", "rrrmc_set_level_scale", "rrrmc_discretize", "rrrmc_discretize_scaled", "rrrmc_wtm_mc_async", "rrrmc_wtm_times", "rrrmc_extremal_opt_async", "rrrmc_extremal_opt_results", "rrrmc_extremal_opt_results_f64",
+    "rrrmc_ctx_create_re", "rrrmc_re_set_params", "rrrmc_re_energies", "rrrmc_re_tables",
 ]
 
 
@@ -198,6 +199,14 @@ def lib():
     L.rrrmc_extremal_opt_results.argtypes = [vp, i64p, u64p, i64p]
     L.rrrmc_extremal_opt_results_f64.restype = C.c_int32
     L.rrrmc_extremal_opt_results_f64.argtypes = [vp, f64p, u64p, i64p]
+    L.rrrmc_ctx_create_re.restype = C.c_int32
+    L.rrrmc_ctx_create_re.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_uint32]
+    L.rrrmc_re_set_params.restype = C.c_int32
+    L.rrrmc_re_set_params.argtypes = [vp, C.c_double, C.c_double]
+    L.rrrmc_re_energies.restype = C.c_int32
+    L.rrrmc_re_energies.argtypes = [vp, f64p]
+    L.rrrmc_re_tables.restype = C.c_int32
+    L.rrrmc_re_tables.argtypes = [C.c_int64, C.c_double, C.c_double, f64p, f64p]
     _lib = L
     return L
 

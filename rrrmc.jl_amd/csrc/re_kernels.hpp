@@ -1,0 +1,608 @@
+// gfx950 kernels for the Robust Ensemble (src/graphs/RE.jl): GraphRobustEnsemble{M,γ,β,G} = the inner graph GraphRE{M,γ,β}, which couples
+// the M replicas of every spin through μ_i = Σ_k σ_(i,k), plus M slices of one graph G — GraphEmpty (Graph0RE), binary GraphSK (GraphSKRE),
+// GraphSKNormal (src/REAliases.jl:20-38).  Samplers: rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290) with the DeltaECache{Float64,L} over
+// ArraySets (src/DeltaE.jl:63-295, src/ArraySets.jl), standardMC (src/RRRMC.jl:81-127), and REenergies (RE.jl:285-301).
+//
+// Layout.  Spins cross the ABI in the reference's order j = i M + k (spin i of replica k, RE.jl:76-95); the kernels work on a
+// slice-major copy x = k Nk + i, so that a binary-SK slice is a contiguous bit row and its field one popcount row (slice_delta).  The
+// classes, set members and positions are indexed by the ABI site j: the ArraySets hold the reference's site ids, so rand(aset) picks the
+// same site.  GraphRE's cache (lfields[j] = σ_j fk(μ_i − σ_j), RE.jl:96-104) is a table look-up over the stored μ_i and never stored:
+// update_cache! recomputes the whole group (RE.jl:139-160) and its move_last swap (:125-135) gives the same table values.
+//
+// Classes.  findk compares Float64s exactly (DeltaE.jl:53-60) and fk(−x) = −fk(x) holds exactly in IEEE arithmetic, so the level of a site
+// is the integer |mū| / 2 (mū = μ_i − σ_j has the parity of M − 1); `up` is decided on the Float64 value as DeltaE.jl:83 does.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rrr_kernels.hpp"   // RrrView, sbit / sflip, slice_delta, skn_update, kRrrThreads, TAG_RRR, det_exp
+
+namespace rrrmc {
+
+enum ReSlice { RE_EMPTY = 0, RE_SK = 1, RE_SKN = 2 };        // GraphEmpty (Graph0RE), binary GraphSK (GraphSKRE), GraphSKNormal
+constexpr int kReMmax = 32;                                 // replicas of the ensemble; levels L = ceil(M / 2) <= 16
+
+struct ReParams {
+    // the slice graph, shared by the M slices
+    const uint32_t* Jb; int Wk; double sN;                  // binary GraphSK: rows of J as 32-bit words, sqrt(Nk)
+    const double* Jd;                                       // GraphSKNormal: [Nk][Nk]
+    double* slf;                                            // [R][2][M][Nk]  every slice's lfields / lfields_last (SK.jl:212-276)
+    int32_t* smv;                                           // [R][M]         move_last of every slice (-1 = none)
+    uint8_t* scur;                                          // [R][M]         which of the two arrays is `lfields`
+    // tables: host libm (rrrmc_re_tables) and the sampler's class weights
+    const double* tab;                                      // [M]    ΔElist(GraphRE): fk(mū) for mū = -(M-1), -(M-3), ..., M-1 (RE.jl:53-56)
+    const double* etab;                                     // [M+1]  log(2 cosh(γ μ)) / β for μ = -M, -M+2, ..., M (RE.jl:90-93)
+    const double* ft;                                       // [L]    det_exp(-β allΔE[a]) (DeltaE.jl:91)
+    // state
+    uint32_t* abi;                                          // [R][W] spins in ABI site order (the context's configuration)
+    uint32_t* sp;                                           // [R][W] slice-major working copy
+    int8_t* mu;                                             // [R][Nk]      μ_i
+    uint8_t* cls;                                           // [R][N]       DeltaECache.pos (a + L up), by ABI site
+    uint16_t* sv;                                           // [R][2L][N]   ArraySet.v of every class
+    uint16_t* spos;                                         // [R][N]       position of a site inside its set
+    int32_t* st;                                            // [R][2L]      set sizes
+    double* T;                                              // [R][2L]
+    double* zz; double* E_cur; double* acc_rate;            // [R]
+    int64_t* stats;                                         // [R][2]       accepted, staged iterations (this call)
+    double* Es;                                             // [nsamples][R]
+    double* Eslice;                                         // [R][M]       REenergies
+    int32_t* flag;                                          // [2]          debug checks: failures, a failing replica
+    double beta, staged_thr, lambda;
+    uint64_t g0;
+    int64_t iters, step;
+    long long samp0;                                        // the call's first sample is taken before its iteration samp0
+    uint32_t k0, k1, replica0;
+    int Nk, M, L, N, W, R;
+};
+
+// the slice helpers of rrr_kernels.hpp work on a RrrView of the slice-major copy
+__device__ __forceinline__ RrrView re_view(const ReParams& P, uint32_t* sp, int r)
+{
+    RrrView v{};
+    v.sp = sp; v.N = P.N; v.Nk = P.Nk; v.M = P.M; v.K = 0; v.wide = 0;
+    v.Jb = P.Jb; v.Wk = P.Wk; v.sN = P.sN;
+    v.Jd = P.Jd;
+    v.slf = P.slf ? P.slf + (size_t)r * 2 * P.M * P.Nk : nullptr;
+    v.smv = P.smv ? P.smv + (size_t)r * P.M : nullptr;
+    v.scur = P.scur ? P.scur + (size_t)r * P.M : nullptr;
+    v.nk_magic = (uint32_t)((0x100000000ull + (uint32_t)P.Nk - 1u) / (uint32_t)P.Nk);
+    return v;
+}
+
+// delta_energy_residual (RE.jl:303-310) = delta_energy(X1[k], C1[k], i), NOT divided by M: 0 (GraphEmpty), lfields[i] / sqrt(Nk) (GraphSK,
+// SK.jl:137-140, the integer field by popcounts), lfields[i] (GraphSKNormal, SK.jl:278-284)
+template <int SLICE>
+__device__ __forceinline__ double re_residual(const RrrView& v, int x, int k, int i)
+{
+    if constexpr (SLICE == RE_EMPTY) return 0.0;
+    else if constexpr (SLICE == RE_SK) return (double)slice_delta(v, x) / v.sN;
+    else return v.slf[((size_t)v.scur[k] * v.M + k) * v.Nk + i];
+}
+// the slice graph's update_cache! after the bit flip (spinflip!(X1[k], C1[k], i), RE.jl:246-253); the binary SK field is recomputed
+template <int SLICE>
+__device__ __forceinline__ void re_slice_update(const RrrView& v, int x)
+{
+    if constexpr (SLICE == RE_SKN) skn_update(v, x);
+}
+// class of ABI site j with spin bit s, for the group's μ = mub + σ: a + L up (DeltaE.jl:80-86 with lfields[j] = σ_j fk(mū), RE.jl:101)
+__device__ __forceinline__ int re_class(const double* tab, int M, int L, int mub, int s)
+{
+    const double dE = (double)(2 * s - 1) * tab[(mub + M - 1) >> 1];
+    const int a = (mub < 0 ? -mub : mub) >> 1;
+    const int up = dE > 0 || (dE == 0 && s == 1);
+    return a + L * up;
+}
+__device__ __forceinline__ double re_class_f(const double* ft, int L, int k) { return k >= L ? ft[k - L] : 1.0; }     // get_class_f
+
+// energy(X1[k], C1[k]) of one slice from the slice-major spins: GraphSK n / sqrt(Nk) (SK.jl:62-96), GraphSKNormal recomputed in the
+// reference's order (SK.jl:212-237); 0 for GraphEmpty.  Sequential (REenergies, debug checks).
+template <int SLICE>
+__device__ inline double re_slice_energy(const ReParams& P, const RrrView& v, int k)
+{
+    const int Nk = P.Nk;
+    if constexpr (SLICE == RE_SK) {
+        long long n = 0;
+        for (int i = 0; i < Nk; ++i) n -= slice_delta(v, k * Nk + i) / 2;
+        n /= 2;
+        return (double)n / P.sN;
+    } else if constexpr (SLICE == RE_SKN) {
+        double n = 0.0;
+        for (int i = 0; i < Nk; ++i) {
+            const int si = sbit(v.sp, k * Nk + i);
+            const double* Ji = P.Jd + (size_t)i * Nk;
+            double lf = 0.0;
+            for (int j = 0; j < Nk; ++j) lf += (double)(1 - 2 * (si ^ sbit(v.sp, k * Nk + j))) * Ji[j];
+            n -= lf;
+        }
+        n /= 2;
+        return n;
+    } else {
+        return 0.0;
+    }
+}
+
+// ABI order <-> slice-major copy, one thread per output word
+__global__ __launch_bounds__(256) void re_to_slices_kernel(ReParams P)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (w >= P.W) return;
+    const uint32_t* a = P.abi + (size_t)r * P.W;
+    uint32_t word = 0u;
+    for (int b = 0; b < 32; ++b) {
+        const int x = 32 * w + b;
+        if (x >= P.N) break;
+        const int k = x / P.Nk, i = x - k * P.Nk, j = i * P.M + k;
+        word |= ((a[j >> 5] >> (j & 31)) & 1u) << b;
+    }
+    P.sp[(size_t)r * P.W + w] = word;
+}
+__global__ __launch_bounds__(256) void re_from_slices_kernel(ReParams P)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    if (w >= P.W) return;
+    const uint32_t* s = P.sp + (size_t)r * P.W;
+    uint32_t word = 0u;
+    for (int b = 0; b < 32; ++b) {
+        const int j = 32 * w + b;
+        if (j >= P.N) break;
+        const int i = j / P.M, k = j - i * P.M, x = k * P.Nk + i;
+        word |= ((s[x >> 5] >> (x & 31)) & 1u) << b;
+    }
+    P.abi[(size_t)r * P.W + w] = word;
+}
+
+// energy(X::GraphRobustEnsemble, C) (RE.jl:265-283: energy(X0) summed left to right in i, then the slices in k order) and, with `cache`,
+// the DeltaECache (DeltaE.jl:74-103: sites pushed in ABI order j = 1..N), one workgroup per replica.  The slice caches of GraphSKNormal are
+// rebuilt as SK.jl:212-237 does (lfields = 2 lf, lfields_last = 0, move_last = none).
+constexpr int kReInitThreads = 256;
+template <int SLICE>
+__global__ __launch_bounds__(kReInitThreads) void re_init_kernel(ReParams P, int cache)
+{
+    __shared__ int s_cnt[2 * (kReMmax / 2)][kReInitThreads];
+    __shared__ int s_tot[2 * (kReMmax / 2)];
+    __shared__ long long s_n[kReMmax];
+    __shared__ double s_E[kReMmax];
+    const int r = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int N = P.N, Nk = P.Nk, M = P.M, L = P.L;
+    uint32_t* sp = P.sp + (size_t)r * P.W;
+    int8_t* mu = P.mu + (size_t)r * Nk;
+    const RrrView v = re_view(P, sp, r);
+    for (int k = tid; k < M; k += kReInitThreads) s_n[k] = 0;
+    for (int i = tid; i < Nk; i += kReInitThreads) {
+        int m = 0;
+        for (int k = 0; k < M; ++k) m += 2 * sbit(sp, k * Nk + i) - 1;
+        mu[i] = (int8_t)m;
+    }
+    __syncthreads();
+    if constexpr (SLICE == RE_SK) {
+        for (int x = tid; x < N; x += kReInitThreads)
+            atomicAdd(reinterpret_cast<unsigned long long*>(&s_n[x / Nk]), (unsigned long long)(long long)(-(slice_delta(v, x) / 2)));
+    } else if constexpr (SLICE == RE_SKN) {
+        for (int x = tid; x < N; x += kReInitThreads) {
+            const int k = x / Nk, i = x - k * Nk;
+            const double* Ji = P.Jd + (size_t)i * Nk;
+            const int si = sbit(sp, x);
+            double lf = 0.0;
+            for (int j = 0; j < Nk; ++j) lf += (double)(1 - 2 * (si ^ sbit(sp, k * Nk + j))) * Ji[j];
+            v.slf[((size_t)0 * M + k) * Nk + i] = 2 * lf;
+            v.slf[((size_t)1 * M + k) * Nk + i] = lf;
+        }
+        __syncthreads();
+        for (int k = tid; k < M; k += kReInitThreads) {
+            double n = 0.0;
+            for (int i = 0; i < Nk; ++i) n -= v.slf[((size_t)1 * M + k) * Nk + i];
+            n /= 2;
+            s_E[k] = n;
+            v.smv[k] = -1;
+            v.scur[k] = 0;
+        }
+        __syncthreads();
+        for (int x = tid; x < N; x += kReInitThreads) v.slf[(size_t)M * Nk + x] = 0.0;
+    }
+    __syncthreads();
+    if (cache) {
+        // classes of a contiguous block of ABI sites per thread, an exclusive scan of the per-class counts over the threads: site order
+        // inside every class, as push! in site order leaves it
+        uint8_t* cls = P.cls + (size_t)r * N;
+        uint16_t* spos = P.spos + (size_t)r * N;
+        uint16_t* sv = P.sv + (size_t)r * 2 * L * N;
+        for (int k = 0; k < 2 * L; ++k) s_cnt[k][tid] = 0;
+        const int per = (N + kReInitThreads - 1) / kReInitThreads, j0 = tid * per, j1 = j0 + per < N ? j0 + per : N;
+        for (int j = j0; j < j1; ++j) {
+            const int i = j / M, k = j - i * M, s = sbit(sp, k * Nk + i);
+            const int c = re_class(P.tab, M, L, mu[i] - (2 * s - 1), s);
+            cls[j] = (uint8_t)c;
+            s_cnt[c][tid] += 1;
+        }
+        __syncthreads();
+        if (tid < 2 * L) {
+            int run = 0;
+            for (int t = 0; t < kReInitThreads; ++t) { const int c = s_cnt[tid][t]; s_cnt[tid][t] = run; run += c; }
+            s_tot[tid] = run;
+        }
+        __syncthreads();
+        for (int j = j0; j < j1; ++j) {
+            const int c = cls[j];
+            const int p = s_cnt[c][tid]++;
+            sv[(size_t)c * N + p] = (uint16_t)j;
+            spos[j] = (uint16_t)p;
+        }
+    }
+    if (tid == 0) {
+        double E = 0.0;
+        for (int i = 0; i < Nk; ++i) E -= P.etab[(mu[i] + M) >> 1];
+        for (int k = 0; k < M; ++k) {
+            if constexpr (SLICE == RE_SK) { long long n = s_n[k]; n /= 2; E += (double)n / P.sN; }
+            else if constexpr (SLICE == RE_SKN) E += s_E[k];
+            else E += 0.0;
+        }
+        P.E_cur[r] = E;
+        if (cache) {
+            double z = 0.0;
+            for (int k = 0; k < 2 * L; ++k) {
+                P.st[(size_t)r * 2 * L + k] = s_tot[k];
+                const double x = (double)s_tot[k] * re_class_f(P.ft, L, k);
+                z += x;
+                P.T[(size_t)r * 2 * L + k] = x;
+            }
+            P.zz[r] = z;
+            P.acc_rate[r] = 0.5;
+        }
+        P.stats[(size_t)r * 2] = 0;
+        P.stats[(size_t)r * 2 + 1] = 0;
+    }
+}
+
+// bytes of LDS one replica takes in the LDS build below: spins, positions, classes, μ, set sizes, the RRR draws of 64 iterations
+inline size_t re_rrr_lds_bytes(int64_t N, int64_t W, int64_t Nk)
+{
+    return (size_t)W * 4 + (((size_t)N * 2 + 3) & ~(size_t)3) + (((size_t)N + 3) & ~(size_t)3) + (((size_t)Nk + 3) & ~(size_t)3) +
+           (size_t)kReMmax * 4 + (size_t)kRrrThreads * 8 * 4;
+}
+
+// rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290) on the Robust Ensemble.  LM >= L: the class weights T live in 2 LM registers (indexed only
+// through unrolled selects: no scratch), classes L .. LM - 1 and L + L .. stay empty.
+// LDS = false: one thread per replica, everything in HBM/L2.
+// LDS = true:  one workgroup (one wavefront) per replica with the replica's spins, positions, classes, μ and set sizes staged in LDS; the
+//   two Philox blocks of 64 iterations are computed by the whole wavefront, then lane 0 runs the chain (rrr_quant_kernel<true>'s pattern).
+//   The member arrays (2 L N entries) stay in HBM/L2.  Same arithmetic, same order: the results are the thread build's.
+template <bool LDS, int LM, int SLICE>
+__global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
+{
+    extern __shared__ uint32_t re_lds[];
+    int r;
+    if constexpr (LDS) {
+        r = (int)blockIdx.x;
+    } else {
+        r = blockIdx.x * blockDim.x + threadIdx.x;
+        if (r >= P.R) return;
+    }
+    const int N = P.N, Nk = P.Nk, M = P.M, L = P.L, Mh = P.M >> 1;
+    uint32_t* const g_sp = P.sp + (size_t)r * P.W;
+    int8_t* const g_mu = P.mu + (size_t)r * Nk;
+    uint8_t* const g_cls = P.cls + (size_t)r * N;
+    uint16_t* const g_spos = P.spos + (size_t)r * N;
+    int32_t* const g_t = P.st + (size_t)r * 2 * L;
+    uint16_t* const sv = P.sv + (size_t)r * 2 * L * N;
+    uint32_t* sp = g_sp; int8_t* mu = g_mu; uint8_t* cls = g_cls; uint16_t* spos = g_spos; int32_t* t = g_t;
+    uint32_t* l_rng = nullptr;
+    if constexpr (LDS) {
+        const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+        uint32_t* l_sp = re_lds;                                                   // [W]
+        uint16_t* l_spos = reinterpret_cast<uint16_t*>(l_sp + P.W);                // [N]
+        uint8_t* l_cls = reinterpret_cast<uint8_t*>(l_spos) + ((2 * N + 3) & ~3);  // [N]
+        int8_t* l_mu = reinterpret_cast<int8_t*>(l_cls + ((N + 3) & ~3));          // [Nk]
+        int32_t* l_t = reinterpret_cast<int32_t*>(l_mu + ((Nk + 3) & ~3));         // [kReMmax]
+        l_rng = reinterpret_cast<uint32_t*>(l_t + kReMmax);                        // [64][8]
+        for (int i = tid; i < P.W; i += nt) l_sp[i] = g_sp[i];
+        for (int i = tid; i < N; i += nt) { l_spos[i] = g_spos[i]; l_cls[i] = g_cls[i]; }
+        for (int i = tid; i < Nk; i += nt) l_mu[i] = g_mu[i];
+        if (tid < 2 * L) l_t[tid] = g_t[tid];
+        __syncthreads();
+        sp = l_sp; spos = l_spos; cls = l_cls; mu = l_mu; t = l_t;
+    }
+    const RrrView v = re_view(P, sp, r);
+    const bool worker = !LDS || threadIdx.x == 0;
+    const uint32_t rep = P.replica0 + (uint32_t)r;
+    const double* tab = P.tab;
+    const double* ft = P.ft;
+    double T[2 * LM];
+#pragma unroll
+    for (int q = 0; q < 2 * LM; ++q) T[q] = 0.0;
+    for (int q = 0; q < 2 * L; ++q) {                                  // class q in register q (q < L) or q - L + LM
+        const double x = P.T[(size_t)r * 2 * L + q];
+        const int uq = q < L ? q : q - L + LM;
+#pragma unroll
+        for (int u = 0; u < 2 * LM; ++u) if (u == uq) T[u] = x;
+    }
+    double z = P.zz[r], E = P.E_cur[r], acc_rate = P.acc_rate[r];
+    int64_t accepted = P.stats[(size_t)r * 2], staged_its = P.stats[(size_t)r * 2 + 1];
+    int64_t ns = 0;
+    long long next_sample = P.samp0;
+
+    // ArraySet delete! / push! (ArraySets.jl:56-76)
+    auto set_move = [&](int j, int k0, int k1) {
+        const int p = spos[j];
+        const int last = sv[(size_t)k0 * N + t[k0] - 1];
+        sv[(size_t)k0 * N + p] = (uint16_t)last;
+        spos[last] = (uint16_t)p;
+        t[k0] -= 1;
+        sv[(size_t)k1 * N + t[k1]] = (uint16_t)j;
+        spos[j] = (uint16_t)t[k1];
+        t[k1] += 1;
+        cls[j] = (uint8_t)k1;
+    };
+    auto t_add = [&](double* A, int k, double d) {
+#pragma unroll
+        for (int u = 0; u < 2 * LM; ++u) if (u == k) A[u] += d;
+    };
+    auto t_sub = [&](double* A, int k, double d) {
+#pragma unroll
+        for (int u = 0; u < 2 * LM; ++u) if (u == k) A[u] -= d;
+    };
+    auto accept_c = [&](double c, double x, const uint32_t* q2, uint64_t g) {          // accept(c, x), RRRMC.jl:40-44
+        bool ok = (c >= 1 && x >= 0);
+        if (!ok) {
+            const double a = c * det_exp(x);
+            ok = a >= 1;
+            if (!ok) {
+                Philox4 o2;
+                if constexpr (LDS) { o2.w[0] = q2[0]; o2.w[1] = q2[1]; }
+                else o2 = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), rep, TAG_RRR | (1u << 8), P.k0, P.k1);
+                ok = (double)((((uint64_t)o2.w[0] << 32) | o2.w[1]) >> 11) * 0x1.0p-53 < a;
+            }
+        }
+        return ok;
+    };
+
+    for (int64_t base = 0; base < P.iters; base += (LDS ? kRrrThreads : P.iters)) {
+    if constexpr (LDS) {
+        __syncthreads();
+        const uint64_t gl = P.g0 + (uint64_t)(base + 1 + (int64_t)threadIdx.x);
+        const Philox4 a = philox4x32_10((uint32_t)gl, (uint32_t)(gl >> 32), rep, TAG_RRR, P.k0, P.k1);
+        const Philox4 b = philox4x32_10((uint32_t)gl, (uint32_t)(gl >> 32), rep, TAG_RRR | (1u << 8), P.k0, P.k1);
+        uint32_t* q = l_rng + threadIdx.x * 8;
+        q[0] = a.w[0]; q[1] = a.w[1]; q[2] = a.w[2]; q[3] = a.w[3]; q[4] = b.w[0]; q[5] = b.w[1]; q[6] = b.w[2]; q[7] = b.w[3];
+        __syncthreads();
+    }
+    const int64_t it_end = LDS ? (base + kRrrThreads < P.iters ? base + kRrrThreads : P.iters) : P.iters;
+    if (worker)
+    for (int64_t it = base + 1; it <= it_end; ++it) {
+        if (it == next_sample) { next_sample += P.step; P.Es[ns * P.R + r] = E; ns += 1; }
+        const uint64_t g = P.g0 + (uint64_t)it;
+        const uint32_t* q2 = LDS ? l_rng + (it - base - 1) * 8 + 4 : nullptr;
+        // rand_move (DeltaE.jl:146-167)
+        Philox4 o;
+        if constexpr (LDS) { const uint32_t* q = l_rng + (it - base - 1) * 8; o.w[0] = q[0]; o.w[1] = q[1]; o.w[2] = q[2]; o.w[3] = q[3]; }
+        else o = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), rep, TAG_RRR, P.k0, P.k1);
+        const double rr = (double)((((uint64_t)o.w[0] << 32) | o.w[1]) >> 11) * 0x1.0p-53 * z;
+        // the classes in the reference's order 0 .. 2L-1: register u holds class u for u < L and class u - LM + L for u >= LM
+        int k = -1, klast = 0;
+        double cT = 0.0;
+#pragma unroll
+        for (int u = 0; u < 2 * LM; ++u) {
+            const bool live = u < LM ? u < L : u - LM < L;
+            if (live && k < 0) {
+                cT += T[u];
+                klast = u;
+                if (rr < cT) k = u;
+            }
+        }
+        if (k < 0) {                                                   // r < cT failed: walk back over the empty classes
+            k = klast;
+            bool found = false;
+#pragma unroll
+            for (int u = 2 * LM - 1; u >= 0; --u) {
+                const bool live = u < LM ? u < L : u - LM < L;
+                if (live && !found && u <= klast && T[u] != 0) { k = u; found = true; }
+            }
+        }
+        const int kc = k < LM ? k : k - LM + L;                        // the reference's class index (0-based)
+        const double dE0 = kc < L ? -tab[kc + Mh] : tab[kc - L + Mh];
+        const uint64_t uu = ((uint64_t)o.w[2] << 32) | o.w[3];
+        const int move = sv[(size_t)kc * N + (size_t)mulhi64(uu, (uint64_t)t[kc])];
+        const int i = move / M, km = move - i * M, xm = km * Nk + i, jg = i * M;
+
+        bool acc = false;
+        if (acc_rate < P.staged_thr) {
+            // staged branch: step_rrr (RRRMC.jl:131-138) = compute_staged! + compute_reverse_probabilities!, the list in order (the group
+            // ascending without the move, then the move: CavityRange, RE.jl:175-206; DeltaE.jl:202-230); the second pass applies it
+            staged_its += 1;
+            const int s_old = sbit(sp, xm);
+            const int munew = mu[i] + 2 * (1 - 2 * s_old);
+            double Tp[2 * LM];
+#pragma unroll
+            for (int u = 0; u < 2 * LM; ++u) Tp[u] = T[u];
+            double zp = z;
+            for (int y = jg; y < jg + M; ++y) {
+                if (y == move) continue;
+                const int sy = sbit(sp, (y - jg) * Nk + i);
+                const int k0 = cls[y], k1 = re_class(tab, M, L, munew - (2 * sy - 1), sy);
+                if (k0 == k1) continue;
+                const double f0 = re_class_f(ft, L, k0), f1 = re_class_f(ft, L, k1);
+                t_sub(Tp, k0 < L ? k0 : k0 - L + LM, f0);
+                t_add(Tp, k1 < L ? k1 : k1 - L + LM, f1);
+                zp += f1 - f0;
+            }
+            {
+                const int k0 = cls[move], k1 = k0 >= L ? k0 - L : k0 + L;
+                const double f0 = re_class_f(ft, L, k0), f1 = re_class_f(ft, L, k1);
+                t_sub(Tp, k0 < L ? k0 : k0 - L + LM, f0);
+                t_add(Tp, k1 < L ? k1 : k1 - L + LM, f1);
+                zp += f1 - f0;
+            }
+            const double c = z / zp;
+            const double dE1 = re_residual<SLICE>(v, xm, km, i);          // delta_energy_residual, RE.jl:303-310
+            if (accept_c(c, -P.beta * dE1, q2, g)) {
+                sflip(sp, xm);                                             // spinflip!(X, C, move)
+                mu[i] = (int8_t)munew;
+                re_slice_update<SLICE>(v, xm);
+                for (int y = jg; y < jg + M; ++y) {                        // apply_staged!
+                    if (y == move) continue;
+                    const int sy = sbit(sp, (y - jg) * Nk + i);
+                    const int k0 = cls[y], k1 = re_class(tab, M, L, munew - (2 * sy - 1), sy);
+                    if (k0 != k1) set_move(y, k0, k1);
+                }
+                { const int k0 = cls[move]; set_move(move, k0, k0 >= L ? k0 - L : k0 + L); }
+#pragma unroll
+                for (int u = 0; u < 2 * LM; ++u) T[u] = Tp[u];
+                z = zp;
+                E += dE0 + dE1;
+                accepted += 1;
+                acc = true;
+            }
+        } else {
+            // direct branch: apply_move! (DeltaE.jl:232-295), undone by a second apply_move! on rejection
+            const double dE1 = re_residual<SLICE>(v, xm, km, i);
+            for (int pass = 0; pass < 2; ++pass) {
+                sflip(sp, xm);
+                const int s_new = sbit(sp, xm);
+                const int munew = mu[i] + 2 * (2 * s_new - 1);
+                mu[i] = (int8_t)munew;
+                re_slice_update<SLICE>(v, xm);                             // the undo pass takes the slice's swap path (move_last == move)
+                double zp = z;
+                for (int y = jg; y < jg + M; ++y) {
+                    if (y == move) continue;
+                    const int sy = sbit(sp, (y - jg) * Nk + i);
+                    const int k0 = cls[y], k1 = re_class(tab, M, L, munew - (2 * sy - 1), sy);
+                    if (k0 == k1) continue;
+                    const double f0 = re_class_f(ft, L, k0), f1 = re_class_f(ft, L, k1);
+                    t_sub(T, k0 < L ? k0 : k0 - L + LM, f0);
+                    t_add(T, k1 < L ? k1 : k1 - L + LM, f1);
+                    zp += f1 - f0;
+                    set_move(y, k0, k1);
+                }
+                {
+                    const int k0 = cls[move], k1 = k0 >= L ? k0 - L : k0 + L;
+                    const double f0 = re_class_f(ft, L, k0), f1 = re_class_f(ft, L, k1);
+                    t_sub(T, k0 < L ? k0 : k0 - L + LM, f0);
+                    t_add(T, k1 < L ? k1 : k1 - L + LM, f1);
+                    zp += f1 - f0;
+                    set_move(move, k0, k1);
+                }
+                const double cc = z / zp;
+                z = zp;
+                if (pass == 1) break;                                      // that was the undo
+                if (accept_c(cc, -P.beta * dE1, q2, g)) { E += dE0 + dE1; accepted += 1; acc = true; break; }
+            }
+        }
+        acc_rate = acc_rate * (1 - P.lambda) + (acc ? 1.0 : 0.0) * P.lambda;          // RRRMC.jl:281
+    }
+    }
+    if (worker) {
+        for (int q = 0; q < 2 * L; ++q) {
+            double x = 0.0;
+#pragma unroll
+            for (int u = 0; u < 2 * LM; ++u) if (u == (q < L ? q : q - L + LM)) x = T[u];
+            P.T[(size_t)r * 2 * L + q] = x;
+        }
+        P.zz[r] = z; P.E_cur[r] = E; P.acc_rate[r] = acc_rate;
+        P.stats[(size_t)r * 2] = accepted; P.stats[(size_t)r * 2 + 1] = staged_its;
+    }
+    if constexpr (LDS) {
+        __syncthreads();
+        const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+        for (int i = tid; i < P.W; i += nt) g_sp[i] = sp[i];
+        for (int i = tid; i < N; i += nt) { g_spos[i] = spos[i]; g_cls[i] = cls[i]; }
+        for (int i = tid; i < Nk; i += nt) g_mu[i] = mu[i];
+        if (tid < 2 * L) g_t[tid] = t[tid];
+    }
+}
+
+// standardMC (src/RRRMC.jl:81-127): delta_energy = delta_energy(X0, C, j) + delta_energy_residual (RE.jl:312-315); the common SITE stream
+// names ABI site j, rand() < exp(-β ΔE) on the ACCEPT_F64 stream.  E starts from E_cur (re_init_kernel, or the run a resumed call continues).
+template <int SLICE>
+__global__ __launch_bounds__(kRrrThreads) void re_standard_kernel(ReParams P)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= P.R) return;
+    const int Nk = P.Nk, M = P.M;
+    uint32_t* sp = P.sp + (size_t)r * P.W;
+    int8_t* mu = P.mu + (size_t)r * Nk;
+    const RrrView v = re_view(P, sp, r);
+    const uint32_t rep = P.replica0 + (uint32_t)r;
+    double E = P.E_cur[r];
+    int64_t accepted = 0, ns = 0;
+    long long next_sample = P.samp0;
+    for (int64_t it = 1; it <= P.iters; ++it) {
+        if (it == next_sample) { next_sample += P.step; P.Es[ns * P.R + r] = E; ns += 1; }
+        const uint64_t g = P.g0 + (uint64_t)it;
+        const int j = (int)site_of(P.k0, P.k1, g, (uint32_t)P.N);
+        const int i = j / M, k = j - i * M, x = k * Nk + i;
+        const int s = sbit(sp, x), sg = 2 * s - 1;
+        const double dE = (double)sg * P.tab[(mu[i] - sg + M - 1) >> 1] + re_residual<SLICE>(v, x, k, i);
+        const double xx = -P.beta * dE;
+        const bool acc = (xx >= 0.0) || (rand53(P.k0, P.k1, g, rep) < det_exp(xx));          // RRRMC.jl:39
+        if (acc) {
+            sflip(sp, x);
+            mu[i] = (int8_t)(mu[i] - 2 * sg);
+            re_slice_update<SLICE>(v, x);
+            E += dE;
+            accepted += 1;
+        }
+    }
+    P.E_cur[r] = E;
+    P.stats[(size_t)r * 2] = accepted; P.stats[(size_t)r * 2 + 1] = 0;
+}
+
+// REenergies(X) (RE.jl:285-301): energy(X1[k], C1[k]) of every slice, one thread per (replica, slice).  Unlike the reference's (which calls
+// energy and so resets the slice caches), this reads the configuration only: a hook that calls it does not change the run.
+template <int SLICE>
+__global__ __launch_bounds__(64) void re_energies_kernel(ReParams P)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= P.R * P.M) return;
+    const int r = e / P.M, k = e - r * P.M;
+    const RrrView v = re_view(P, P.sp + (size_t)r * P.W, r);
+    P.Eslice[e] = re_slice_energy<SLICE>(P, v, k);
+}
+
+// debug mode (rrrmc_set_debug_checks): after a sampler call every replica's energy(X, C) is re-evaluated from its configuration and compared
+// with the tracked E (|ΔE| <= 1e-10, the bound of the reference's check, RRRMC.jl:250); μ, and after rrrMC every site's class and the set
+// sizes, must equal what the configuration gives; GraphSKNormal slices: the cached fields within 1e-10 Nk of recomputed ones.
+template <int SLICE>
+__global__ __launch_bounds__(64) void re_check_kernel(ReParams P, int cache)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= P.R) return;
+    const int Nk = P.Nk, M = P.M, L = P.L, N = P.N;
+    const uint32_t* sp = P.sp + (size_t)r * P.W;
+    const int8_t* mu = P.mu + (size_t)r * Nk;
+    const RrrView v = re_view(P, P.sp + (size_t)r * P.W, r);
+    bool bad = false;
+    double E = 0.0;
+    for (int i = 0; i < Nk; ++i) {
+        int m = 0;
+        for (int k = 0; k < M; ++k) m += 2 * sbit(sp, k * Nk + i) - 1;
+        bad = bad || m != mu[i];
+        E -= P.etab[(m + M) >> 1];
+    }
+    for (int k = 0; k < M; ++k) E += re_slice_energy<SLICE>(P, v, k);
+    const double d = E - P.E_cur[r];
+    bad = bad || !(d <= 1e-10 && d >= -1e-10);
+    if constexpr (SLICE == RE_SKN) {
+        for (int k = 0; k < M; ++k)
+            for (int i = 0; i < Nk; ++i) {
+                const int si = sbit(sp, k * Nk + i);
+                const double* Ji = P.Jd + (size_t)i * Nk;
+                double lf = 0.0;
+                for (int j = 0; j < Nk; ++j) lf += (double)(1 - 2 * (si ^ sbit(sp, k * Nk + j))) * Ji[j];
+                const double dd = v.slf[((size_t)v.scur[k] * M + k) * Nk + i] - 2 * lf;
+                bad = bad || !(dd <= 1e-10 * Nk && dd >= -1e-10 * Nk);
+            }
+    }
+    if (cache) {
+        int cnt[2 * (kReMmax / 2)];
+        for (int k = 0; k < 2 * L; ++k) cnt[k] = 0;
+        for (int j = 0; j < N; ++j) {
+            const int i = j / M, k = j - i * M, s = sbit(sp, k * Nk + i);
+            const int c = re_class(P.tab, M, L, mu[i] - (2 * s - 1), s);
+            bad = bad || c != P.cls[(size_t)r * N + j] || P.sv[((size_t)r * 2 * L + c) * N + P.spos[(size_t)r * N + j]] != j;
+            cnt[c] += 1;
+        }
+        for (int k = 0; k < 2 * L; ++k) bad = bad || cnt[k] != P.st[(size_t)r * 2 * L + k];
+    }
+    if (bad) { atomicAdd(&P.flag[0], 1); P.flag[1] = r; }
+}
+
+}  // namespace rrrmc

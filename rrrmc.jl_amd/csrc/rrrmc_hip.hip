@@ -34,6 +34,7 @@
 #include "dbl_kernels.hpp"
 #include "cont_kernels.hpp"
 #include "cont_wave_kernel.hpp"
+#include "re_kernels.hpp"
 
 using namespace rrrmc;
 
@@ -258,6 +259,15 @@ struct rrrmc_ctx {
     size_t pairs_cap = 0;
     int32_t* d_ovl = nullptr;      // [pairs_cap][Rpad]
     int32_t* d_qobs = nullptr;     // GraphQuant: e0[R], Eslice[R][M], ovs_raw[R][M/2]
+    // ---- GraphRobustEnsemble (RRRMC_MODEL_RE_*): spins in q_spins / qW (ABI site order), qNk / qM, slices in q_Jb (binary SK) or sk_J +
+    //      q_slf / q_smv / q_scur (GraphSKNormal), the DeltaECache in q_cls / q_sv / q_spos / q_st / q_T / q_z, E in sk_E, counts in q_stats ----
+    uint32_t* re_sp = nullptr;     // [R][qW] slice-major working copy of the spins
+    int8_t* re_mu = nullptr;       // [R][Nk]
+    double* re_tab = nullptr;      // ΔElist [M], mu-energies [M + 1], class weights ft [L]
+    double* re_Eslice = nullptr;   // [R][M] REenergies
+    std::vector<double> re_htab;   // host copy of the first two tables
+    std::vector<double> re_hft;    // staging of ft
+    bool re_params_set = false;
 
     // ---- fast standardMC on RRRMC_MODEL_SPARSE_F64 (spf_fast_kernels.hpp; allocated on first use) ----
     std::vector<double> h_Jf;           // host copy of the couplings (threshold tables per beta)
@@ -416,7 +426,8 @@ hipError_t raise_lds_attr(const void* fn, size_t bytes)
     return e;
 }
 
-inline bool chunk_layout(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_QUANT_RRG || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_SPARSE_LEVELS; }
+inline bool chunk_layout(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_QUANT_RRG || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_SPARSE_LEVELS ||
+                                                       ctx->model == RRRMC_MODEL_RE_EMPTY || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_RE_SKN; }
 inline bool sparse_int_model(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_SPARSE_PM1 || ctx->model == RRRMC_MODEL_SPARSE_LEVELS; }
 inline double lv_to_f64(const rrrmc_ctx* ctx, long long units) { return (double)(units * ctx->lv_mul) / ctx->lv_div; }
 
@@ -557,6 +568,7 @@ inline void smp_commit(rrrmc_ctx* ctx, int kind, int64_t n) { ctx->smp_kind = ki
 #include "host_lev.hpp"
 #include "host_sweep.hpp"
 #include "host_spf_fast.hpp"
+#include "host_re.hpp"
 int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact);
 
 }  // namespace
@@ -867,6 +879,7 @@ void rrrmc_ctx_destroy(rrrmc_ctx* ctx)
     free_dev(ctx->q_Jb); free_dev(ctx->q_slf); free_dev(ctx->q_smv); free_dev(ctx->q_scur);
     free_dev(ctx->cs_spins); free_dev(ctx->cs_buf); free_dev(ctx->cs_u16);
     free_dev(ctx->snap); free_dev(ctx->d_pairs); free_dev(ctx->d_ovl); free_dev(ctx->d_qobs);
+    free_dev(ctx->re_sp); free_dev(ctx->re_mu); free_dev(ctx->re_tab); free_dev(ctx->re_Eslice);
     for (int i = 0; i < 2; ++i) { free_dev(ctx->d_slots[i]); free_dev(ctx->d_vecs[i]); free_dev(ctx->d_nbrs[i]); free_dev(ctx->d_masks[i]); }
     free_dev(ctx->d_bigimg);
     free_dev(ctx->dbg_flag); free_dev(ctx->dbg_Ei); free_dev(ctx->dbg_lf); free_dev(ctx->dbg_lfl); free_dev(ctx->dbg_E); free_dev(ctx->dbg_ml);
@@ -889,7 +902,7 @@ int32_t rrrmc_set_graph(rrrmc_ctx* ctx, const int32_t* A, const int8_t* J)
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
     if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_QUANT_RRG)
-        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph is for sparse +-J models; use rrrmc_set_couplings_dense");
+        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph is for sparse +-J models; use rrrmc_set_couplings_dense%s", is_re(ctx) ? " / rrrmc_set_couplings_bits (GraphRobustEnsemble)" : "");
     if (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk)
         return fail(ctx, RRRMC_ERR_STATE, "this GraphQuant has binary GraphSK slices: give their couplings with rrrmc_set_couplings_bits");
     if (!A || !J) return fail(ctx, RRRMC_ERR_INVALID_ARG, "A and J must not be NULL");
@@ -1184,6 +1197,7 @@ int32_t rrrmc_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int6
     if (ctx->model == RRRMC_MODEL_SPARSE_F64) return spf_standard_mc_async(ctx, beta, iters, step);
     if (ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED) return dbl_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (ctx->model == RRRMC_MODEL_SPARSE_LEVELS) return lev_standard_mc_async(ctx, beta, iters, step, false);
+    if (is_re(ctx)) return re_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (ctx->model == RRRMC_MODEL_QUANT_RRG) {
         if (!(ctx->last_fourK > 0.0)) return fail(ctx, RRRMC_ERR_STATE, "standardMC on a GraphQuant needs fourK: call rrrmc_quant_set_field first");
         return quant_mc_async(ctx, true, beta, ctx->last_fourK, iters, step, 0.0, 0.0);
@@ -1216,8 +1230,8 @@ int32_t rrrmc_set_debug_checks(rrrmc_ctx* ctx, int32_t on)
 {
     RRRMC_MULTI(ctx, false, rrrmc_set_debug_checks(c, on));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64)
-        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL and RRRMC_MODEL_SPARSE_F64");
+    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx))
+        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64 and the GraphRobustEnsemble");
     ctx->debug_checks = on != 0;
     return RRRMC_OK;
 }
@@ -1547,6 +1561,66 @@ int32_t rrrmc_ctx_create_quant_skn(rrrmc_ctx** out, int64_t Nk, int64_t M, int64
     return quant_ctx_create(out, Nk, 0, M, R, device, replica0, false, true);
 }
 
+// ---- GraphRobustEnsemble: exported entry points (host_re.hpp) ---------------------------------------------------------------------
+int32_t rrrmc_ctx_create_re(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0)
+{
+    return re_ctx_create(out, Nk, M, slice_kind, R, device, replica0);
+}
+
+int32_t rrrmc_re_tables(int64_t M, double gamma, double beta, double* dElist, double* e0)
+{
+    if (!dElist || !e0) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "dElist and e0 must not be NULL");
+    if (M <= 2) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "M must be greater than 2, given: %lld", (long long)M);
+    if (M > kReMmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "M = %lld: the Robust Ensemble covers M <= %d", (long long)M, kReMmax);
+    re_tables(M, gamma, beta, dElist, e0);
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_re_set_params(rrrmc_ctx* ctx, double gamma, double beta_graph)
+{
+    RRRMC_MULTI(ctx, false, rrrmc_re_set_params(c, gamma, beta_graph));
+    smp_drop(ctx);
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!is_re(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_re_set_params is for contexts made by rrrmc_ctx_create_re");
+    if (!std::isfinite(gamma) || !std::isfinite(beta_graph) || beta_graph == 0.0)
+        return fail(ctx, RRRMC_ERR_INVALID_ARG, "gamma and beta must be finite and beta non-zero, given: %g, %g", gamma, beta_graph);
+    const int64_t M = ctx->qM;
+    re_tables(M, gamma, beta_graph, ctx->re_htab.data(), ctx->re_htab.data() + M);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(ctx->re_tab, ctx->re_htab.data(), sizeof(double) * (size_t)(2 * M + 1), hipMemcpyHostToDevice));
+    ctx->std_cache_live = false;
+    ctx->q_cache_valid = false;
+    ctx->re_params_set = true;
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_re_energies(rrrmc_ctx* ctx, double* out)
+{
+    RRRMC_MULTI(ctx, true, rrrmc_re_energies(c, at_row(out, r0 * c->qM)));
+    int32_t rc = ensure_state(ctx, true);
+    if (rc) return rc;
+    if (!is_re(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_re_energies is for contexts made by rrrmc_ctx_create_re");
+    if (!out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "out is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    { const int32_t rcp = post_sync_checks(ctx); if (rcp) return rcp; }
+    // read-only for a live run: the working copy is rewritten with the bits it already holds (every sampler call ends by writing it back)
+    const ReParams P = re_params(ctx, 1.0);
+    rc = re_to_slices(ctx, P);
+    if (rc) return rc;
+    const dim3 grid((unsigned)((ctx->R * ctx->qM + 63) / 64)), blk(64);
+    switch (re_slice_of(ctx)) {
+        case RE_SK: hipLaunchKernelGGL(re_energies_kernel<RE_SK>, grid, blk, 0, ctx->stream, P); break;
+        case RE_SKN: hipLaunchKernelGGL(re_energies_kernel<RE_SKN>, grid, blk, 0, ctx->stream, P); break;
+        default: hipLaunchKernelGGL(re_energies_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P); break;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->re_Eslice, sizeof(double) * (size_t)(ctx->R * ctx->qM), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RRRMC_OK;
+}
+
 // One context over several devices: the reference's user makes ONE call from ONE process (src/RRRMC.jl:81-88).
 // Replicas never interact, so the context is a list of per-device contexts over shards of whole 32-replica groups in global-id
 // order (the random streams are addressed by global replica id: the results do not depend on ndev); every entry point forwards
@@ -1564,8 +1638,10 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
     if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
     const bool quant = model == RRRMC_MODEL_QUANT_RRG || model == RRRMC_MODEL_QUANT_SK || model == RRRMC_MODEL_QUANT_SKN || model == RRRMC_MODEL_QUANT_F64;
+    const bool re = model == RRRMC_MODEL_RE_EMPTY || model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_RE_SKN;
     ctx->model = quant ? RRRMC_MODEL_QUANT_RRG : model; ctx->K = K; ctx->R = R; ctx->replica0 = replica0; ctx->device = device_ids[0];
-    ctx->N = quant ? N * M : N;
+    ctx->N = quant || re ? N * M : N;
+    if (re) { ctx->qNk = N; ctx->qM = M; }
     if (quant) { ctx->qNk = N; ctx->qM = M; ctx->q_sk = model == RRRMC_MODEL_QUANT_SK; ctx->q_skn = model == RRRMC_MODEL_QUANT_SKN; ctx->q_spf = model == RRRMC_MODEL_QUANT_F64; }
     for (int32_t d = 0; d < ndev; ++d) {
         int64_t b0 = 0, b1 = 0;
@@ -1576,6 +1652,9 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : model == RRRMC_MODEL_QUANT_SK  ? rrrmc_ctx_create_quant_sk(&c, N, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_QUANT_SKN ? rrrmc_ctx_create_quant_skn(&c, N, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_QUANT_F64 ? rrrmc_ctx_create_quant_f64(&c, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : re ? rrrmc_ctx_create_re(&c, N, M, model == RRRMC_MODEL_RE_SK ? RRRMC_RE_SLICE_SK : model == RRRMC_MODEL_RE_SKN ? RRRMC_RE_SLICE_SKN
+                                                                                                                        : RRRMC_RE_SLICE_EMPTY,
+                                                      b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                                                             : rrrmc_ctx_create(&c, model, N, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0);
         if (rc) {
             for (rrrmc_ctx* k : ctx->kids) rrrmc_ctx_destroy(k);
@@ -1788,6 +1867,7 @@ int32_t rrrmc_rrr_mc_async(rrrmc_ctx* ctx, double beta, double fourK, int64_t it
     if (sparse_int_model(ctx)) return sparse_rrr_bkl_async(ctx, 0, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED) return dbl_rrr_mc_async(ctx, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model == RRRMC_MODEL_SPARSE_F64) return spf_cont_async(ctx, 0, beta, iters, step, 1.0, staged_thr, staged_thr_fact);
+    if (is_re(ctx)) return re_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model != RRRMC_MODEL_QUANT_RRG) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not available for model kind %d", ctx->model);
     return quant_mc_async(ctx, false, beta, fourK, iters, step, staged_thr, staged_thr_fact);
 }
@@ -1798,6 +1878,7 @@ int32_t rrrmc_bkl_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t s
     if (ctx) ctx->std_cache_live = false;
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
+    if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (!std::isfinite(beta)) return fail(ctx, RRRMC_ERR_INVALID_ARG, "beta must be finite, given: %g", beta);
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
         return spf_cont_async(ctx, 1, beta, iters, step, 1.0, 0.0, 5.0);
@@ -1835,6 +1916,7 @@ int32_t rrrmc_wtm_mc_async(rrrmc_ctx* ctx, double beta, int64_t samples, double 
     if (ctx) ctx->std_cache_live = false;
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
+    if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
         return spf_cont_async(ctx, 2, beta, samples, 1, step, 0.0, 5.0);
     if (ctx->model == RRRMC_MODEL_SK_NORMAL || ctx->model == RRRMC_MODEL_SK_BINARY) return sk_rrr_mc_async(ctx, beta, samples, 1, 0.0, 5.0, 2, step);
@@ -1860,6 +1942,7 @@ int32_t rrrmc_extremal_opt_async(rrrmc_ctx* ctx, const double* ftau, int64_t ite
     if (ctx) ctx->std_cache_live = false;
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
+    if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)        // not DiscrGraphs: EOCacheCont
         return spf_cont_async(ctx, 3, 0.0, iters, step, 1.0, 0.0, 0.0, ftau);
     if (ctx->model == RRRMC_MODEL_SK_NORMAL || ctx->model == RRRMC_MODEL_SK_BINARY)                 // EOCacheCont, every spin a neighbour
@@ -1927,8 +2010,16 @@ int32_t rrrmc_rrr_stats(rrrmc_ctx* ctx, int64_t* staged_iters_out)
 
 int32_t rrrmc_rrr_cache(rrrmc_ctx* ctx, int8_t* pos_out, int32_t* sizes_out)
 {
-    RRRMC_MULTI(ctx, true, rrrmc_rrr_cache(c, at_row(pos_out, r0 * ctx->N), at_row(sizes_out, r0 * (ctx->model == RRRMC_MODEL_QUANT_RRG ? 4 : 16))));
+    RRRMC_MULTI(ctx, true, rrrmc_rrr_cache(c, at_row(pos_out, r0 * ctx->N), at_row(sizes_out, r0 * (ctx->model == RRRMC_MODEL_QUANT_RRG ? 4 : is_re(ctx) ? 2 * re_levels(ctx->qM) : 16))));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (is_re(ctx)) {             // classes of the ABI sites, sizes_out[R * 2L]
+        if (!ctx->results_valid || !ctx->last_call_rrr || !ctx->q_cache_valid) return fail(ctx, RRRMC_ERR_STATE, "no rrrMC call has been made");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (pos_out) HIP_TRY(ctx, hipMemcpy(pos_out, ctx->q_cls, (size_t)ctx->R * ctx->N, hipMemcpyDeviceToHost));
+        if (sizes_out) HIP_TRY(ctx, hipMemcpy(sizes_out, ctx->q_st, sizeof(int32_t) * ctx->R * 2 * re_levels(ctx->qM), hipMemcpyDeviceToHost));
+        return RRRMC_OK;
+    }
     if ((ctx->model != RRRMC_MODEL_QUANT_RRG && ctx->model != RRRMC_MODEL_SPARSE_DISCRETIZED && !sparse_int_model(ctx)) || !ctx->results_valid || !ctx->last_call_rrr)
         return fail(ctx, RRRMC_ERR_STATE, "no rrrMC call has been made");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1970,7 +2061,7 @@ int32_t rrrmc_set_couplings_dense(rrrmc_ctx* ctx, const double* J)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_dense(c, J));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qskn = ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn;      // the slice graph of a GraphQSKNormalT: J is Nk x Nk
+    const bool qskn = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn) || ctx->model == RRRMC_MODEL_RE_SKN;   // slice graphs: J is Nk x Nk
     if (ctx->model != RRRMC_MODEL_SK_NORMAL && !qskn) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_dense is for RRRMC_MODEL_SK_NORMAL (or a GraphQuant over GraphSKNormal slices)");
     if (!J) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J is NULL");
     const int64_t N = qskn ? ctx->qNk : ctx->N;
@@ -2006,6 +2097,10 @@ int32_t rrrmc_energy_f64(rrrmc_ctx* ctx, double* E_out)
     if (ctx->model == RRRMC_MODEL_QUANT_RRG) {
         if (!(ctx->last_fourK > 0.0)) return fail(ctx, RRRMC_ERR_STATE, "energy of a GraphQuant needs fourK: call rrrmc_quant_set_field first");
         rc = quant_run_init(ctx, ctx->last_beta, ctx->last_fourK);
+    } else if (is_re(ctx)) {
+        if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphRobustEnsemble needs (gamma, beta): call rrrmc_re_set_params first");
+        ctx->std_cache_live = false;
+        rc = re_run_init(ctx, 1.0, false);
     } else if (ctx->model == RRRMC_MODEL_SPARSE_F64) {
         rc = spf_run_energy(ctx);
     } else if (ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED) {
@@ -2098,7 +2193,7 @@ int32_t rrrmc_set_couplings_bits(rrrmc_ctx* ctx, const uint64_t* Jc)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_bits(c, Jc));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qsk = ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk;          // the slice graph of a GraphQSKT
+    const bool qsk = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk) || ctx->model == RRRMC_MODEL_RE_SK;     // the slice graph of a GraphQSKT / GraphSKRE
     if (ctx->model != RRRMC_MODEL_SK_BINARY && !qsk)
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_bits is for RRRMC_MODEL_SK_BINARY and for contexts made by rrrmc_ctx_create_quant_sk");
     if (!Jc) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J_chunks is NULL");

@@ -14,6 +14,8 @@ MODEL_SK_BINARY = 4
 MODEL_SPARSE_F64 = 5
 MODEL_SPARSE_DISCRETIZED = 6
 MODEL_SPARSE_LEVELS = 7
+MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN = 11, 12, 13          # GraphRobustEnsemble (rrrmc_ctx_create_re; also the selectors of rrrmc_ctx_create_multi)
+MODEL_RE = (MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN)
 
 
 class Engine:
@@ -32,8 +34,11 @@ class Engine:
             # a GraphQuant over dense slices is made per device by rrrmc_ctx_create_quant_skn / _sk: the selectors 9 / 8 of the header
             kind = (X.model_kind if not quant else MODEL_QUANT_SKN if getattr(X, "skn_slices", False) else MODEL_QUANT_SK if X.sk_slices
                     else MODEL_QUANT_F64 if getattr(X, "f64_slices", False) else X.model_kind)
-            check(lib().rrrmc_ctx_create_multi(C.byref(self._ctx), kind, X.Nk if quant else X.N, X.K, X.M if quant else 0, self.R,
+            re = X.model_kind in MODEL_RE
+            check(lib().rrrmc_ctx_create_multi(C.byref(self._ctx), kind, X.Nk if quant or re else X.N, X.K, X.M if quant or re else 0, self.R,
                                                ids, len(ids), replica0))
+        elif X.model_kind in MODEL_RE:
+            check(lib().rrrmc_ctx_create_re(C.byref(self._ctx), X.Nk, X.M, X.slice_kind, self.R, device, replica0))
         elif X.model_kind == MODEL_QUANT_RRG and getattr(X, "skn_slices", False):
             check(lib().rrrmc_ctx_create_quant_skn(C.byref(self._ctx), X.Nk, X.M, self.R, device, replica0))
         elif X.model_kind == MODEL_QUANT_RRG and X.sk_slices:
@@ -45,7 +50,14 @@ class Engine:
         else:
             check(lib().rrrmc_ctx_create(C.byref(self._ctx), X.model_kind, X.N, X.K, self.R, device, replica0))
         try:
-            if X.model_kind == MODEL_QUANT_RRG:
+            if X.model_kind in MODEL_RE:
+                if X.model_kind == MODEL_RE_SK:
+                    check(lib().rrrmc_set_couplings_bits(self._ctx, X.J.reshape(-1)), self._ctx)
+                elif X.model_kind == MODEL_RE_SKN:
+                    check(lib().rrrmc_set_couplings_dense(self._ctx, X.J.reshape(-1)), self._ctx)
+                check(lib().rrrmc_re_set_params(self._ctx, X.gamma, X.beta), self._ctx)
+                X._engine = self                # REenergies(X) inside a hook reads this engine's live configuration
+            elif X.model_kind == MODEL_QUANT_RRG:
                 if getattr(X, "skn_slices", False):
                     check(lib().rrrmc_set_couplings_dense(self._ctx, X.J.reshape(-1)), self._ctx)
                 elif X.sk_slices:
@@ -80,6 +92,8 @@ class Engine:
         if getattr(self, "_ctx", None) is not None and self._ctx:
             lib().rrrmc_ctx_destroy(self._ctx)
             self._ctx = C.c_void_p()
+        if getattr(getattr(self, "X", None), "_engine", None) is self:
+            self.X._engine = None
 
     def __del__(self):
         try:
@@ -274,9 +288,17 @@ class Engine:
         """(pos[R, N], sizes[R, 4]) of the DeltaECache after the last rrrMC call (GraphQuant); sizes[R, 16] for the DiscrGraphs
         (GraphRRG / GraphEA, rrrMC and bklMC) and the discretised DoubleGraphs, class k of replica r at [r, k]."""
         pos = np.zeros((self.R, self.X.N), np.int8)
-        sizes = np.zeros((self.R, 4 if self.X.model_kind == MODEL_QUANT_RRG else 16), np.int32)
+        ncls = 4 if self.X.model_kind == MODEL_QUANT_RRG else 2 * ((self.X.M + 1) // 2) if self.X.model_kind in MODEL_RE else 16
+        sizes = np.zeros((self.R, ncls), np.int32)
         check(lib().rrrmc_rrr_cache(self._ctx, pos.ctypes.data, sizes.ctypes.data), self._ctx)
         return pos, sizes
+
+    def re_energies(self):
+        """REenergies (RE.jl:285-301) of the live configuration: (M,) for one replica, (R, M) otherwise.  Read-only: a run the engine
+        continues is not disturbed."""
+        out = np.zeros((self.R, self.X.M), np.float64)
+        check(lib().rrrmc_re_energies(self._ctx, out.reshape(-1)), self._ctx)
+        return out[0] if self.R == 1 else out
 
     # -- snapshots and observables (SURVEY.md §8f rank 2) ---------------------------------------------
     def snapshot_reserve(self, nslots):

@@ -488,6 +488,64 @@ def GraphQSKT(Nk, M, Gamma, beta, seed=DEFAULT_SEED):
     return GraphQuant(GraphSK(Nk, seed=seed), M, Gamma, beta)
 
 
+class GraphRobustEnsemble:
+    """``GraphRobustEnsemble(Nk, M, γ, β, slice_graph)`` — the Robust Ensemble (src/graphs/RE.jl:215-263): M replicas of one graph (the
+    slices, which share one coupling set as ``Gconstr(args...)`` with the same ``args`` gives them) coupled by ``GraphRE{M,γ,β}`` through
+    μ_i = Σ_k σ_(i,k), energy Σ_i −log(2 cosh(γ μ_i)) / β.  ``slice_graph`` is ``None`` (GraphEmpty: ``Graph0RE``), a binary ``GraphSK``
+    (``GraphSKRE``) or a ``GraphSKNormal`` with ``N == Nk``.  ``N = Nk * M`` spins in the reference's order: site j is spin j // M of replica
+    j % M (RE.jl:76-95).  β here is the graph's (inside fk), not a sampler's.  ``ET = Float64``.  See ``REenergies``."""
+    energy_dtype = np.float64
+    K = 0
+
+    def __init__(self, Nk, M, gamma, beta, slice_graph=None):
+        if M <= 2:
+            raise ValueError("M must be greater than 2, given: %d" % M)                  # RE.jl:37
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal)):
+            raise TypeError("the slices of a GraphRobustEnsemble are GraphEmpty (None), GraphSK or GraphSKNormal")
+        if slice_graph is not None and slice_graph.N != int(Nk):
+            raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
+        self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
+        self.N = self.Nk * self.M
+        self.X1 = slice_graph
+        self.slice_kind = 0 if slice_graph is None else 1 if isinstance(slice_graph, GraphSK) else 2
+        self.model_kind = 11 + self.slice_kind          # RRRMC_MODEL_RE_EMPTY / _SK / _SKN
+        self.J = None if slice_graph is None else slice_graph.J
+        self._engine = None                             # the Engine running this graph: REenergies reads the live configuration there
+
+    def tables(self):
+        """(ΔElist[M], μ-energies[M + 1]) of GraphRE{M,γ,β} (rrrmc_re_tables: host libm, no device)"""
+        dE = np.zeros(self.M, np.float64)
+        e0 = np.zeros(self.M + 1, np.float64)
+        check(lib().rrrmc_re_tables(self.M, self.gamma, self.beta, dE, e0))
+        return dE, e0
+
+
+def Graph0RE(Nk, M, gamma, beta):
+    """``Graph0RE(Nk, M, γ, β)`` = ``GraphRobustEnsemble(Nk, M, γ, β, GraphEmpty, Nk)`` (src/REAliases.jl:20-29)."""
+    return GraphRobustEnsemble(Nk, M, gamma, beta, None)
+
+
+def GraphSKRE(Nk, M, gamma, beta, seed=DEFAULT_SEED):
+    """``GraphSKRE(Nk, M, γ, β)`` = ``GraphRobustEnsemble(Nk, M, γ, β, GraphSK, SK.gen_J(Nk))`` (src/REAliases.jl:33-38): the couplings are
+    drawn once (``rrrmc_gen_sk_binary``, as ``GraphSK`` does) and shared by the M slices."""
+    return GraphRobustEnsemble(Nk, M, gamma, beta, GraphSK(Nk, seed=seed))
+
+
+def REenergies(X, C=None):
+    """``REenergies(X)`` (RE.jl:285-301): the energy of every replica of the ensemble as its own graph defines it — shape (M,) for one
+    replica of the batch, (R, M) otherwise — computed on the device from the CURRENT configuration of the engine that runs ``X`` (inside a
+    hook: the sample's configuration).  With ``C`` (a ``Config`` of N = Nk M spins) it is evaluated for that configuration instead."""
+    from .engine import Engine
+    if C is not None:
+        with Engine(X, C.R) as eng:
+            eng.set_config(C)
+            return eng.re_energies()
+    eng = getattr(X, "_engine", None)
+    if eng is None or not eng._ctx:
+        raise RuntimeError("REenergies(X): no engine is running this graph; pass a configuration: REenergies(X, C)")
+    return eng.re_energies()
+
+
 def checkerboard_coloring(L, D):
     """Two-colouring (parity of the coordinate sum) of the periodic L^D lattice of ``GraphEA``; L must be even."""
     if L % 2:

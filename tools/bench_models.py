@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Secondary benchmarks (not the headline metric): throughput of the other model kernels on one GPU.
   python tools/bench_models.py sk      GraphSKNormal N=1024, 2048 replicas (BASELINE.json configs[2])
+  python tools/bench_models.py re [R ...]   GraphSKRE(1024, 5), γ = 2, β = 0.4: rrrMC (both builds) and standardMC
 """
 import json
 import os
@@ -178,6 +179,42 @@ def bench_ea_random(L=64, D=3, beta=1.0, sweeps=8, seed=0x5EED):
         eng.close()
 
 
+def bench_re(Nk=1024, M=5, gamma=2.0, beta=0.4, iters=1 << 14, step=1 << 12, seed=0x5EED):
+    """GraphSKRE(1024, 5), γ = 2, β = 0.4 (scripts.jl:866-963 test_REIsing): rrrMC through the thread and the LDS build and standardMC, kernel
+    iterations/s per replica count (python tools/bench_models.py re 128 1024 4096), and the standardMC-per-rrrMC time ratio of the pair."""
+    pkg = entry.load_package()
+    X = pkg.GraphSKRE(Nk, M, gamma, beta, seed=seed)
+    for R in ([int(a) for a in sys.argv[2:]] or [128, 1024, 4096]):
+        it = max(step, iters * 1024 // max(R, 1024))
+        out = {"model": "GraphSKRE", "Nk": Nk, "M": M, "gamma": gamma, "beta": beta, "replicas": R, "iters": it}
+        for name, env in (("rrr_thread", {"RRRMC_RE_NO_LDS": "1"}), ("rrr_lds", {"RRRMC_RE_LDS": "1"}), ("standard", {})):
+            for k in ("RRRMC_RE_NO_LDS", "RRRMC_RE_LDS"):
+                os.environ.pop(k, None)
+            os.environ.update(env)
+            eng = pkg.Engine(X, R)
+            eng.seed(seed)
+            eng.init_spins_random()
+            if name == "standard":
+                eng.standard_mc(beta, it, step)                  # warm-up, then the timed call from the configuration it left
+                Es, acc = eng.standard_mc(beta, it, step)
+                staged = np.zeros(R)
+            else:
+                eng.rrr_mc(beta, it, step)
+                Es, acc, staged = eng.rrr_mc(beta, it, step)
+            _, sweep_ms, _ = eng.last_timing()
+            out[name] = {"kernel_iterations_per_s": float(R) * it / (sweep_ms * 1e-3), "kernel_ms": sweep_ms,
+                         "acceptance": float(acc.mean()) / it, "staged_frac": float(staged.mean()) / it,
+                         "energy_per_spin": float(Es[:, -1].mean()) / X.N}
+            eng.close()
+        for k in ("RRRMC_RE_NO_LDS", "RRRMC_RE_LDS"):
+            os.environ.pop(k, None)
+        best = max(out["rrr_thread"]["kernel_iterations_per_s"], out["rrr_lds"]["kernel_iterations_per_s"])
+        # seconds of standardMC per second of rrrMC at met_factor standardMC iterations per rrrMC iteration (scripts.jl:877: 20.8)
+        out["met_factor_time_ratio"] = 20.8 * best / out["standard"]["kernel_iterations_per_s"]
+        out["iters_ratio_equal_time"] = out["standard"]["kernel_iterations_per_s"] / best
+        print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "sk"
-    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random}[which]()
+    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re}[which]()
