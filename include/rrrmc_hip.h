@@ -64,7 +64,12 @@ enum rrrmc_model {
        rrrmc_ctx_create_re, and the selectors of rrrmc_ctx_create_multi for it (N = Nk, M; K ignored) */
     RRRMC_MODEL_RE_EMPTY = 11,   /* Graph0RE (src/REAliases.jl:20-29) */
     RRRMC_MODEL_RE_SK = 12,      /* GraphSKRE (src/REAliases.jl:33-38) */
-    RRRMC_MODEL_RE_SKN = 13      /* GraphRobustEnsemble(Nk, M, gamma, beta, GraphSKNormal, J) (test/runtests.jl:90-92) */
+    RRRMC_MODEL_RE_SKN = 13,     /* GraphRobustEnsemble(Nk, M, gamma, beta, GraphSKNormal, J) (test/runtests.jl:90-92) */
+    /* GraphLocalEntropy (src/graphs/LE.jl:183-318) over GraphEmpty / binary GraphSK / GraphSKNormal slices: the model of a context made by
+       rrrmc_ctx_create_le, and the selectors of rrrmc_ctx_create_multi for it (N = Nk, M; K ignored) */
+    RRRMC_MODEL_LE_EMPTY = 14,   /* Graph0LE (src/LEAliases.jl:18-27) */
+    RRRMC_MODEL_LE_SK = 15,      /* GraphSKLE (src/LEAliases.jl:31-38) */
+    RRRMC_MODEL_LE_SKN = 16      /* GraphLocalEntropy(Nk, M, gamma, beta, GraphSKNormal, J) (test/runtests.jl:103) */
 };
 
 /* slice families of rrrmc_ctx_create_re */
@@ -114,7 +119,8 @@ RRRMC_API int32_t rrrmc_ctx_create(rrrmc_ctx **out, int32_t model, int64_t N, in
  * thread per device.  rrrmc_last_timing / rrrmc_timing_total report the slowest device.
  *   model  any rrrmc_model; RRRMC_MODEL_QUANT_RRG takes (N = Nk, K, M) as rrrmc_ctx_create_quant does, RRRMC_MODEL_QUANT_SK / _SKN take
  *          (N = Nk, M) as rrrmc_ctx_create_quant_sk / _skn do (K ignored), RRRMC_MODEL_QUANT_F64 takes (N = Nk, K, M) as rrrmc_ctx_create_quant_f64,
- *          RRRMC_MODEL_RE_EMPTY / _SK / _SKN take (N = Nk, M) as rrrmc_ctx_create_re does (K ignored); M is ignored otherwise.
+ *          RRRMC_MODEL_RE_EMPTY / _SK / _SKN take (N = Nk, M) as rrrmc_ctx_create_re does (K ignored), RRRMC_MODEL_LE_EMPTY / _SK / _SKN
+ *          take (N = Nk, M) as rrrmc_ctx_create_le does (K ignored); M is ignored otherwise.
  */
 RRRMC_API int32_t rrrmc_ctx_create_multi(rrrmc_ctx **out, int32_t model, int64_t N, int64_t K, int64_t M, int64_t R,
                                          const int32_t *device_ids, int32_t ndev, uint32_t replica0);
@@ -260,6 +266,36 @@ RRRMC_API int32_t rrrmc_re_energies(rrrmc_ctx *ctx, double *out);
  * upper ceil(M/2) entries are allDeltaE), e0[M+1] = log(2 cosh(gamma mu)) / beta for mu = -M, -M+2, ..., M (RE.jl:90-93), evaluated with libm. */
 RRRMC_API int32_t rrrmc_re_tables(int64_t M, double gamma, double beta, double *dElist, double *e0);
 
+/* ---- GraphLocalEntropy (src/graphs/LE.jl; RRRMC_MODEL_LE_*) -------------------------------------------------------
+ * The Local Entropy ensemble: M replicas of one graph, each coupled to an explicit reference ("centre") configuration by the inner graph
+ * GraphLE{M,gammaT} with gammaT = gamma / beta (LE.jl:221-225): integer fields lfields = sigma_c sigma_(i,k) on a replica site and
+ * sigma_c mu_i (mu_i = sum_k sigma_(i,k)) on the centre, DeltaE0 = 2 gammaT lfields, energy(X0) = -gammaT sum_i sigma_c mu_i.  Replica k is slice k
+ * of a DoubleGraph whose residual is the slice graph's delta_energy (not divided by M); centre moves have residual 0 (LE.jl:276-290).  The
+ * centre graph's own energy is not part of E.  The centre and all M slices share one coupling set.
+ *   N = Nk * (M + 1) spins per replica of the batch, in the reference's site order: site j (0-based) is spin i = j / (M+1) of the centre when
+ *   k = j % (M+1) is 0 and of replica k otherwise (LE.jl:55-84) — in every configuration that crosses this ABI and in rrrmc_rrr_cache.
+ *   3 <= M <= 31, N <= 65 535.  Energies are Float64 (_f64 entry points).
+ * rrrmc_ctx_create_le: slice_kind rrrmc_re_slice; then the couplings (rrrmc_set_couplings_bits [Nk rows] for _SK, rrrmc_set_couplings_dense
+ * [Nk x Nk] for _SKN, nothing for _EMPTY) and rrrmc_le_set_params.  Samplers: rrrmc_rrr_mc_async (rrrMC(X::DoubleGraph): the DeltaECache over
+ * L = M/2 + 2 (M even) or (M+1)/2 (M odd) levels, classes by findk evaluated literally; fourK is ignored; streams as the Robust Ensemble's)
+ * and rrrmc_standard_mc_async / rrrmc_standard_mc_f64, with the resume, debug-check, timing, results and cache entry points of the other
+ * models.  rrrmc_bkl_mc_async, rrrmc_wtm_mc_async and rrrmc_extremal_opt_async return RRRMC_ERR_UNSUPPORTED. */
+RRRMC_API int32_t rrrmc_ctx_create_le(rrrmc_ctx **out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0);
+/* The parameters gamma and beta_graph of GraphLocalEntropy(Nk, M, gamma, beta_graph, ...) (gammaT = gamma / beta_graph, not the sampler's beta).
+ * gammaT must be finite and 2 M gammaT too; gamma = 0 is allowed.  Required before the first sampler or energy call; a change ends a resumed run. */
+RRRMC_API int32_t rrrmc_le_set_params(rrrmc_ctx *ctx, double gamma, double beta_graph);
+/* LEenergies(X) (LE.jl:259-269): out[R * M], energy(X1[k], C1[k]) of every replica slice of every replica of the batch for the current
+ * configuration.  rrrmc_le_cenergy: cenergy(X) (LE.jl:271-274), out[R], energy(Xc, Cc) of the centre configuration under the slice graph
+ * (0 for GraphEmpty).  rrrmc_le_distances: distances(X) (LE.jl:309-318), out[R * M * M], the Hamming distances between the replica
+ * configurations (centre excluded), entry (k1, k2) of replica r at (r * M + k1) * M + k2.  All three read the configuration only — unlike
+ * the reference's LEenergies / cenergy, they do not rebuild the slice caches, so a hook that calls them leaves the run as it was. */
+RRRMC_API int32_t rrrmc_le_energies(rrrmc_ctx *ctx, double *out);
+RRRMC_API int32_t rrrmc_le_cenergy(rrrmc_ctx *ctx, double *out);
+RRRMC_API int32_t rrrmc_le_distances(rrrmc_ctx *ctx, int64_t *out);
+/* Host-only (no device needed): dElist[L] = allDeltaE(GraphLE{M, gamma/beta}) (LE.jl:176-179), L = M/2 + 2 for even M and (M+1)/2 for odd M
+ * (a buffer of M/2 + 2 entries always suffices). */
+RRRMC_API int32_t rrrmc_le_tables(int64_t M, double gamma, double beta, double *dElist);
+
 /* rrrMC(X::DoubleGraph, beta, iters; step, staged_thr, staged_thr_fact) (src/RRRMC.jl:221-290) for all R replicas.
  *   fourK = round(2/beta * log(coth(beta * Gamma / M)), digits = 8)  (QT.jl:165) is computed by the caller.
  * Enqueues on the ctx's stream; rrrmc_sync + rrrmc_fetch_results_f64 return Es [R x iters/step] and accepted [R];
@@ -300,7 +336,7 @@ RRRMC_API int32_t rrrmc_extremal_opt_results(rrrmc_ctx *ctx, int64_t *Emin_out, 
 RRRMC_API int32_t rrrmc_extremal_opt_results_f64(rrrmc_ctx *ctx, double *Emin_out, uint64_t *Cmin_chunks, int64_t *itmin_out);
 /* parity/debug view of the move-selection cache after the last rrrMC call: pos_out[R * N] = class of every spin
  * (DeltaECache.pos, 0-based a + 2*up), sizes_out[R * 4] = |class k| (DeltaE.jl:63-73).  RRRMC_MODEL_RE_*: class a + L*up of every site j,
- * sizes_out[R * 2L] with L = ceil(M/2).  RRRMC_MODEL_SPARSE_PM1 / _LEVELS (rrrMC and
+ * sizes_out[R * 2L] with L = ceil(M/2); RRRMC_MODEL_LE_*: the same with L = M/2 + 2 (M even) or (M+1)/2 (M odd).  RRRMC_MODEL_SPARSE_PM1 / _LEVELS (rrrMC and
  * bklMC; class a + L*up) and RRRMC_MODEL_SPARSE_DISCRETIZED: sizes_out[R * 16], class k of replica r at 16 r + k. */
 RRRMC_API int32_t rrrmc_rrr_cache(rrrmc_ctx *ctx, int8_t *pos_out, int32_t *sizes_out);
 

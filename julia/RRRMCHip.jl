@@ -55,6 +55,7 @@ version() = Int(ccall((:rrrmc_version, LIB), Int32, ()))
 const SPARSE_PM1, SK_NORMAL, QUANT_RRG, SK_BINARY, SPARSE_F64, SPARSE_DISCRETIZED, SPARSE_LEVELS = 1, 2, 3, 4, 5, 6, 7
 const QUANT_SK, QUANT_SKN, QUANT_F64 = 8, 9, 10      # selectors of rrrmc_ctx_create_multi: GraphQuant over GraphSK / GraphSKNormal / sparse Float64 slices
 const RE_EMPTY, RE_SK, RE_SKN = 11, 12, 13            # GraphRobustEnsemble over GraphEmpty / GraphSK / GraphSKNormal (rrrmc_ctx_create_re; multi selectors)
+const LE_EMPTY, LE_SK, LE_SKN = 14, 15, 16            # GraphLocalEntropy over GraphEmpty / GraphSK / GraphSKNormal (rrrmc_ctx_create_le; multi selectors)
 
 # rrrmc_ctx_create / rrrmc_ctx_create_quant on one device, rrrmc_ctx_create_multi on several (N = Nk for a GraphQuant)
 function create(model::Integer, N::Integer, K::Integer, M::Integer, R::Integer; device = 0, replica0 = 0, devices = nothing)
@@ -239,6 +240,70 @@ end
 re_hook(X, hook) = hook
 re_hook(X::RRRMC.RE.GraphRobustEnsemble, hook::Nothing) = hook
 re_hook(X::RRRMC.RE.GraphRobustEnsemble, hook) = (it, X_, C, a, b) -> (re_slices!(X, C); hook(it, X_, C, a, b))
+
+# ---- GraphLocalEntropy (src/graphs/LE.jl:183-318): M replicas of one slice graph, each coupled to the centre by GraphLE{M,γT} ---------------
+# spins in the reference's order (site (i-1)(M+1) + 1 = spin i of the centre, (i-1)(M+1) + 1 + k = spin i of replica k), so C.s.chunks passes
+# as is; the centre and the M slices share one coupling set.  γT is the type parameter: rrrmc_le_set_params takes (γ, β) = (γT, 1), and
+# γT / 1 is γT exactly
+function Ctx(X::RRRMC.LE.GraphLocalEntropy{M,γT,G}, R::Integer; device = 0, replica0 = 0, devices = nothing) where {M,γT,G}
+    Nk = X.Nk
+    kind = G <: RRRMC.SK.GraphSK ? 1 : G <: RRRMC.SK.GraphSKNormal ? 2 : G <: RRRMC.Empty.GraphEmpty ? 0 :
+           throw(ArgumentError("the engine runs the Local Entropy ensemble over GraphEmpty, GraphSK and GraphSKNormal slices, given: $G"))
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    if devices === nothing
+        check(ccall((:rrrmc_ctx_create_le, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, Int64, Int32, UInt32), ref, Nk, M, kind, R, device, replica0))
+    else
+        ref[] = create(LE_EMPTY + kind, Nk, 0, M, R; replica0 = replica0, devices = devices)
+    end
+    ctx = Ctx(ref[], R, Nk * (M + 1), true)
+    X1 = X.X1[1]
+    if kind == 1
+        Jc = sk_bits(X1.J)
+        GC.@preserve Jc check(ccall((:rrrmc_set_couplings_bits, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt64}), ctx.p, Jc), ctx.p)
+    elseif kind == 2
+        Jm = Matrix{Float64}(undef, Nk, Nk); for i = 1:Nk; Jm[:, i] = X1.J[i]; end
+        GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
+    end
+    check(ccall((:rrrmc_le_set_params, LIB), Int32, (Ptr{Cvoid}, Float64, Float64), ctx.p, γT, 1.0), ctx.p)
+    return ctx
+end
+# LEenergies (LE.jl:259-269), cenergy (:271-274) and distances (:309-318) of every replica of the batch, read on the device from the live
+# configuration: column r (or slice [:, :, r]) = replica r.  Read-only, unlike the reference's, which rebuild the slice caches
+function le_energies(ctx::Ctx, M::Integer)
+    out = Matrix{Float64}(undef, M, ctx.R)
+    check(ccall((:rrrmc_le_energies, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, out), ctx.p)
+    return out
+end
+function le_cenergy(ctx::Ctx)
+    out = Vector{Float64}(undef, ctx.R)
+    check(ccall((:rrrmc_le_cenergy, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, out), ctx.p)
+    return out
+end
+function le_distances(ctx::Ctx, M::Integer)
+    out = Array{Int64}(undef, M, M, ctx.R)          # the matrix is symmetric: the row-major layout of the library reads the same
+    check(ccall((:rrrmc_le_distances, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}), ctx.p, out), ctx.p)
+    return out
+end
+# allΔE(GraphLE{M,γT}) on the host (LE.jl:176-179), no device
+function le_tables(M::Integer, γT::Float64)
+    out = Vector{Float64}(undef, iseven(M) ? M ÷ 2 + 2 : (M + 1) ÷ 2)
+    check(ccall((:rrrmc_le_tables, LIB), Int32, (Int64, Float64, Float64, Ptr{Float64}), M, γT, 1.0, out))
+    return out
+end
+# the centre's and the slices' configurations Cc, C1[k] of a GraphLocalEntropy from a configuration of the whole graph (what energy(X, C)
+# does, LE.jl:242-258): before a user's hook runs, so that the reference's own RRRMC.LEenergies(X), cenergy(X) and distances(X) read the
+# sample's configuration (one chain)
+function le_slices!(X::RRRMC.LE.GraphLocalEntropy{M}, C::RRRMC.Config) where {M}
+    for i = 1:X.Nk
+        X.Cc.s[i] = C.s[(i - 1) * (M + 1) + 1]
+        for k = 1:M
+            X.C1[k].s[i] = C.s[(i - 1) * (M + 1) + 1 + k]
+        end
+    end
+    return X
+end
+re_hook(X::RRRMC.LE.GraphLocalEntropy, hook::Nothing) = hook
+re_hook(X::RRRMC.LE.GraphLocalEntropy, hook) = (it, X_, C, a, b) -> (le_slices!(X, C); hook(it, X_, C, a, b))
 
 # ---- configurations ------------------------------------------------------------------------------------------------------------------
 seed!(ctx::Ctx, seed) = seed > 0 && check(ccall((:rrrmc_seed, LIB), Int32, (Ptr{Cvoid}, UInt64), ctx.p, seed), ctx.p)   # seed ≤ 0: keep going (RRRMC.jl:89)

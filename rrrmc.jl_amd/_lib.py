@@ -27,6 +27,7 @@ SYMBOLS = [
     "rrrmc_snapshot_reserve", "rrrmc_snapshot_store", "rrrmc_snapshot_get", "rrrmc_overlaps", "rrrmc_quant_observables",
     "rrrmc_set_graph_f64", "rrrmc_gen_couplings_gauss", "rrrmc_set_graph_discretized", "rrrmc_set_level_scale", "rrrmc_discretize", "rrrmc_discretize_scaled", "rrrmc_wtm_mc_async", "rrrmc_wtm_times", "rrrmc_extremal_opt_async", "rrrmc_extremal_opt_results", "rrrmc_extremal_opt_results_f64",
     "rrrmc_ctx_create_re", "rrrmc_re_set_params", "rrrmc_re_energies", "rrrmc_re_tables",
+    "rrrmc_ctx_create_le", "rrrmc_le_set_params", "rrrmc_le_energies", "rrrmc_le_cenergy", "rrrmc_le_distances", "rrrmc_le_tables",
 ]
 
 
@@ -207,6 +208,18 @@ def lib():
     L.rrrmc_re_energies.argtypes = [vp, f64p]
     L.rrrmc_re_tables.restype = C.c_int32
     L.rrrmc_re_tables.argtypes = [C.c_int64, C.c_double, C.c_double, f64p, f64p]
+    L.rrrmc_ctx_create_le.restype = C.c_int32
+    L.rrrmc_ctx_create_le.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_uint32]
+    L.rrrmc_le_set_params.restype = C.c_int32
+    L.rrrmc_le_set_params.argtypes = [vp, C.c_double, C.c_double]
+    L.rrrmc_le_energies.restype = C.c_int32
+    L.rrrmc_le_energies.argtypes = [vp, f64p]
+    L.rrrmc_le_cenergy.restype = C.c_int32
+    L.rrrmc_le_cenergy.argtypes = [vp, f64p]
+    L.rrrmc_le_distances.restype = C.c_int32
+    L.rrrmc_le_distances.argtypes = [vp, i64p]
+    L.rrrmc_le_tables.restype = C.c_int32
+    L.rrrmc_le_tables.argtypes = [C.c_int64, C.c_double, C.c_double, f64p]
     _lib = L
     return L
 

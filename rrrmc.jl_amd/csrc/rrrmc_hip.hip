@@ -35,6 +35,7 @@
 #include "cont_kernels.hpp"
 #include "cont_wave_kernel.hpp"
 #include "re_kernels.hpp"
+#include "le_kernels.hpp"
 
 using namespace rrrmc;
 
@@ -268,6 +269,11 @@ struct rrrmc_ctx {
     std::vector<double> re_htab;   // host copy of the first two tables
     std::vector<double> re_hft;    // staging of ft
     bool re_params_set = false;
+    // ---- GraphLocalEntropy (RRRMC_MODEL_LE_*): the Robust Ensemble's buffers above with M + 1 rows (row 0 the centre); re_htab = allΔE,
+    //      re_tab = allΔE, ft, the class codes; re_Eslice = [R][M + 1] (row 0: cenergy) ----
+    int64_t* le_dist = nullptr;    // [R][M][M] distances
+    double le_gT = 0.0;            // γT = γ / β (LE.jl:221-225)
+    std::vector<uint8_t> le_hcode; // class codes of lfields = -M .. M (host_le.hpp)
 
     // ---- fast standardMC on RRRMC_MODEL_SPARSE_F64 (spf_fast_kernels.hpp; allocated on first use) ----
     std::vector<double> h_Jf;           // host copy of the couplings (threshold tables per beta)
@@ -427,7 +433,8 @@ hipError_t raise_lds_attr(const void* fn, size_t bytes)
 }
 
 inline bool chunk_layout(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_QUANT_RRG || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_SPARSE_LEVELS ||
-                                                       ctx->model == RRRMC_MODEL_RE_EMPTY || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_RE_SKN; }
+                                                       ctx->model == RRRMC_MODEL_RE_EMPTY || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_RE_SKN ||
+                                                       ctx->model == RRRMC_MODEL_LE_EMPTY || ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_LE_SKN; }
 inline bool sparse_int_model(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_SPARSE_PM1 || ctx->model == RRRMC_MODEL_SPARSE_LEVELS; }
 inline double lv_to_f64(const rrrmc_ctx* ctx, long long units) { return (double)(units * ctx->lv_mul) / ctx->lv_div; }
 
@@ -569,6 +576,7 @@ inline void smp_commit(rrrmc_ctx* ctx, int kind, int64_t n) { ctx->smp_kind = ki
 #include "host_sweep.hpp"
 #include "host_spf_fast.hpp"
 #include "host_re.hpp"
+#include "host_le.hpp"
 int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact);
 
 }  // namespace
@@ -879,7 +887,7 @@ void rrrmc_ctx_destroy(rrrmc_ctx* ctx)
     free_dev(ctx->q_Jb); free_dev(ctx->q_slf); free_dev(ctx->q_smv); free_dev(ctx->q_scur);
     free_dev(ctx->cs_spins); free_dev(ctx->cs_buf); free_dev(ctx->cs_u16);
     free_dev(ctx->snap); free_dev(ctx->d_pairs); free_dev(ctx->d_ovl); free_dev(ctx->d_qobs);
-    free_dev(ctx->re_sp); free_dev(ctx->re_mu); free_dev(ctx->re_tab); free_dev(ctx->re_Eslice);
+    free_dev(ctx->re_sp); free_dev(ctx->re_mu); free_dev(ctx->re_tab); free_dev(ctx->re_Eslice); free_dev(ctx->le_dist);
     for (int i = 0; i < 2; ++i) { free_dev(ctx->d_slots[i]); free_dev(ctx->d_vecs[i]); free_dev(ctx->d_nbrs[i]); free_dev(ctx->d_masks[i]); }
     free_dev(ctx->d_bigimg);
     free_dev(ctx->dbg_flag); free_dev(ctx->dbg_Ei); free_dev(ctx->dbg_lf); free_dev(ctx->dbg_lfl); free_dev(ctx->dbg_E); free_dev(ctx->dbg_ml);
@@ -902,7 +910,7 @@ int32_t rrrmc_set_graph(rrrmc_ctx* ctx, const int32_t* A, const int8_t* J)
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
     if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_QUANT_RRG)
-        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph is for sparse +-J models; use rrrmc_set_couplings_dense%s", is_re(ctx) ? " / rrrmc_set_couplings_bits (GraphRobustEnsemble)" : "");
+        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph is for sparse +-J models; use rrrmc_set_couplings_dense%s", is_re(ctx) || is_le(ctx) ? " / rrrmc_set_couplings_bits (GraphRobustEnsemble, GraphLocalEntropy)" : "");
     if (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk)
         return fail(ctx, RRRMC_ERR_STATE, "this GraphQuant has binary GraphSK slices: give their couplings with rrrmc_set_couplings_bits");
     if (!A || !J) return fail(ctx, RRRMC_ERR_INVALID_ARG, "A and J must not be NULL");
@@ -1198,6 +1206,7 @@ int32_t rrrmc_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int6
     if (ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED) return dbl_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (ctx->model == RRRMC_MODEL_SPARSE_LEVELS) return lev_standard_mc_async(ctx, beta, iters, step, false);
     if (is_re(ctx)) return re_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
+    if (is_le(ctx)) return le_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (ctx->model == RRRMC_MODEL_QUANT_RRG) {
         if (!(ctx->last_fourK > 0.0)) return fail(ctx, RRRMC_ERR_STATE, "standardMC on a GraphQuant needs fourK: call rrrmc_quant_set_field first");
         return quant_mc_async(ctx, true, beta, ctx->last_fourK, iters, step, 0.0, 0.0);
@@ -1230,8 +1239,8 @@ int32_t rrrmc_set_debug_checks(rrrmc_ctx* ctx, int32_t on)
 {
     RRRMC_MULTI(ctx, false, rrrmc_set_debug_checks(c, on));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx))
-        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64 and the GraphRobustEnsemble");
+    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx))
+        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble and the GraphLocalEntropy");
     ctx->debug_checks = on != 0;
     return RRRMC_OK;
 }
@@ -1621,6 +1630,93 @@ int32_t rrrmc_re_energies(rrrmc_ctx* ctx, double* out)
     return RRRMC_OK;
 }
 
+// ---- GraphLocalEntropy: exported entry points (host_le.hpp) ----------------------------------------------------------------------
+int32_t rrrmc_ctx_create_le(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0)
+{
+    return le_ctx_create(out, Nk, M, slice_kind, R, device, replica0);
+}
+
+int32_t rrrmc_le_tables(int64_t M, double gamma, double beta, double* dElist)
+{
+    if (!dElist) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "dElist must not be NULL");
+    if (M <= 2) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "M must be greater than 2, given: %lld", (long long)M);
+    if (M > kLeMmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "M = %lld: the Local Entropy ensemble covers M <= %d", (long long)M, kLeMmax);
+    le_tables(M, gamma / beta, dElist);
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_le_set_params(rrrmc_ctx* ctx, double gamma, double beta_graph)
+{
+    RRRMC_MULTI(ctx, false, rrrmc_le_set_params(c, gamma, beta_graph));
+    smp_drop(ctx);
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!is_le(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_le_set_params is for contexts made by rrrmc_ctx_create_le");
+    const int64_t M = ctx->qM, L = le_levels(M);
+    const double gT = gamma / beta_graph;                       // LE.jl:221-225
+    if (!std::isfinite(gT) || !std::isfinite(2 * (double)M * gT))
+        return fail(ctx, RRRMC_ERR_INVALID_ARG, "gamma / beta must be finite (and 2 M gamma / beta too), given: %g, %g", gamma, beta_graph);
+    le_tables(M, gT, ctx->re_htab.data());
+    for (int64_t a = 0; a < L; ++a)
+        if (!std::isfinite(ctx->re_htab[(size_t)a])) return fail(ctx, RRRMC_ERR_INVALID_ARG, "allΔE is not finite for gamma / beta = %g", gT);
+    if (!le_codes(M, gT, ctx->re_htab.data(), ctx->le_hcode.data()))
+        return fail(ctx, RRRMC_ERR_INVALID_ARG, "findk finds no level for a field of GraphLE{%lld, %g}", (long long)M, gT);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(ctx->re_tab, ctx->re_htab.data(), sizeof(double) * (size_t)L, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->re_tab + 2 * L, ctx->le_hcode.data(), ctx->le_hcode.size(), hipMemcpyHostToDevice));
+    ctx->le_gT = gT;
+    ctx->std_cache_live = false;
+    ctx->q_cache_valid = false;
+    ctx->re_params_set = true;
+    return RRRMC_OK;
+}
+
+// the observables of the current configuration into host memory: what = 0 LEenergies [R][M], 1 cenergy [R], 2 distances [R][M][M]
+static int32_t le_observable_out(rrrmc_ctx* ctx, int what, void* out)
+{
+    int32_t rc = ensure_state(ctx, true);
+    if (rc) return rc;
+    if (!is_le(ctx)) return fail(ctx, RRRMC_ERR_STATE, "the LE observables are for contexts made by rrrmc_ctx_create_le");
+    if (!out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "out is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    { const int32_t rcp = post_sync_checks(ctx); if (rcp) return rcp; }
+    rc = le_observables(ctx);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const int64_t R = ctx->R, M = ctx->qM;
+    if (what == 2) {
+        HIP_TRY(ctx, hipMemcpy(out, ctx->le_dist, sizeof(int64_t) * (size_t)(R * M * M), hipMemcpyDeviceToHost));
+        return RRRMC_OK;
+    }
+    std::vector<double> e((size_t)(R * (M + 1)));
+    HIP_TRY(ctx, hipMemcpy(e.data(), ctx->re_Eslice, sizeof(double) * e.size(), hipMemcpyDeviceToHost));
+    double* o = static_cast<double*>(out);
+    for (int64_t r = 0; r < R; ++r) {
+        if (what == 1) o[r] = e[(size_t)(r * (M + 1))];
+        else for (int64_t k = 0; k < M; ++k) o[r * M + k] = e[(size_t)(r * (M + 1) + 1 + k)];
+    }
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_le_energies(rrrmc_ctx* ctx, double* out)
+{
+    RRRMC_MULTI(ctx, true, rrrmc_le_energies(c, at_row(out, r0 * c->qM)));
+    return le_observable_out(ctx, 0, out);
+}
+
+int32_t rrrmc_le_cenergy(rrrmc_ctx* ctx, double* out)
+{
+    RRRMC_MULTI(ctx, true, rrrmc_le_cenergy(c, at_row(out, r0)));
+    return le_observable_out(ctx, 1, out);
+}
+
+int32_t rrrmc_le_distances(rrrmc_ctx* ctx, int64_t* out)
+{
+    RRRMC_MULTI(ctx, true, rrrmc_le_distances(c, at_row(out, r0 * c->qM * c->qM)));
+    return le_observable_out(ctx, 2, out);
+}
+
 // One context over several devices: the reference's user makes ONE call from ONE process (src/RRRMC.jl:81-88).
 // Replicas never interact, so the context is a list of per-device contexts over shards of whole 32-replica groups in global-id
 // order (the random streams are addressed by global replica id: the results do not depend on ndev); every entry point forwards
@@ -1639,9 +1735,10 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
     const bool quant = model == RRRMC_MODEL_QUANT_RRG || model == RRRMC_MODEL_QUANT_SK || model == RRRMC_MODEL_QUANT_SKN || model == RRRMC_MODEL_QUANT_F64;
     const bool re = model == RRRMC_MODEL_RE_EMPTY || model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_RE_SKN;
+    const bool le = model == RRRMC_MODEL_LE_EMPTY || model == RRRMC_MODEL_LE_SK || model == RRRMC_MODEL_LE_SKN;
     ctx->model = quant ? RRRMC_MODEL_QUANT_RRG : model; ctx->K = K; ctx->R = R; ctx->replica0 = replica0; ctx->device = device_ids[0];
-    ctx->N = quant || re ? N * M : N;
-    if (re) { ctx->qNk = N; ctx->qM = M; }
+    ctx->N = quant || re ? N * M : le ? N * (M + 1) : N;
+    if (re || le) { ctx->qNk = N; ctx->qM = M; }
     if (quant) { ctx->qNk = N; ctx->qM = M; ctx->q_sk = model == RRRMC_MODEL_QUANT_SK; ctx->q_skn = model == RRRMC_MODEL_QUANT_SKN; ctx->q_spf = model == RRRMC_MODEL_QUANT_F64; }
     for (int32_t d = 0; d < ndev; ++d) {
         int64_t b0 = 0, b1 = 0;
@@ -1653,6 +1750,9 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : model == RRRMC_MODEL_QUANT_SKN ? rrrmc_ctx_create_quant_skn(&c, N, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_QUANT_F64 ? rrrmc_ctx_create_quant_f64(&c, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : re ? rrrmc_ctx_create_re(&c, N, M, model == RRRMC_MODEL_RE_SK ? RRRMC_RE_SLICE_SK : model == RRRMC_MODEL_RE_SKN ? RRRMC_RE_SLICE_SKN
+                                                                                                                        : RRRMC_RE_SLICE_EMPTY,
+                                                      b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : le ? rrrmc_ctx_create_le(&c, N, M, model == RRRMC_MODEL_LE_SK ? RRRMC_RE_SLICE_SK : model == RRRMC_MODEL_LE_SKN ? RRRMC_RE_SLICE_SKN
                                                                                                                         : RRRMC_RE_SLICE_EMPTY,
                                                       b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                                                             : rrrmc_ctx_create(&c, model, N, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0);
@@ -1868,6 +1968,7 @@ int32_t rrrmc_rrr_mc_async(rrrmc_ctx* ctx, double beta, double fourK, int64_t it
     if (ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED) return dbl_rrr_mc_async(ctx, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model == RRRMC_MODEL_SPARSE_F64) return spf_cont_async(ctx, 0, beta, iters, step, 1.0, staged_thr, staged_thr_fact);
     if (is_re(ctx)) return re_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
+    if (is_le(ctx)) return le_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model != RRRMC_MODEL_QUANT_RRG) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not available for model kind %d", ctx->model);
     return quant_mc_async(ctx, false, beta, fourK, iters, step, staged_thr, staged_thr_fact);
 }
@@ -1879,6 +1980,7 @@ int32_t rrrmc_bkl_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t s
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
+    if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
     if (!std::isfinite(beta)) return fail(ctx, RRRMC_ERR_INVALID_ARG, "beta must be finite, given: %g", beta);
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
         return spf_cont_async(ctx, 1, beta, iters, step, 1.0, 0.0, 5.0);
@@ -1917,6 +2019,7 @@ int32_t rrrmc_wtm_mc_async(rrrmc_ctx* ctx, double beta, int64_t samples, double 
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
+    if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
         return spf_cont_async(ctx, 2, beta, samples, 1, step, 0.0, 5.0);
     if (ctx->model == RRRMC_MODEL_SK_NORMAL || ctx->model == RRRMC_MODEL_SK_BINARY) return sk_rrr_mc_async(ctx, beta, samples, 1, 0.0, 5.0, 2, step);
@@ -1943,6 +2046,7 @@ int32_t rrrmc_extremal_opt_async(rrrmc_ctx* ctx, const double* ftau, int64_t ite
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
+    if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)        // not DiscrGraphs: EOCacheCont
         return spf_cont_async(ctx, 3, 0.0, iters, step, 1.0, 0.0, 0.0, ftau);
     if (ctx->model == RRRMC_MODEL_SK_NORMAL || ctx->model == RRRMC_MODEL_SK_BINARY)                 // EOCacheCont, every spin a neighbour
@@ -2010,14 +2114,15 @@ int32_t rrrmc_rrr_stats(rrrmc_ctx* ctx, int64_t* staged_iters_out)
 
 int32_t rrrmc_rrr_cache(rrrmc_ctx* ctx, int8_t* pos_out, int32_t* sizes_out)
 {
-    RRRMC_MULTI(ctx, true, rrrmc_rrr_cache(c, at_row(pos_out, r0 * ctx->N), at_row(sizes_out, r0 * (ctx->model == RRRMC_MODEL_QUANT_RRG ? 4 : is_re(ctx) ? 2 * re_levels(ctx->qM) : 16))));
+    RRRMC_MULTI(ctx, true, rrrmc_rrr_cache(c, at_row(pos_out, r0 * ctx->N), at_row(sizes_out, r0 * (ctx->model == RRRMC_MODEL_QUANT_RRG ? 4 : is_re(ctx) ? 2 * re_levels(ctx->qM) : is_le(ctx) ? 2 * le_levels(ctx->qM) : 16))));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (is_re(ctx)) {             // classes of the ABI sites, sizes_out[R * 2L]
+    if (is_re(ctx) || is_le(ctx)) {             // classes of the ABI sites, sizes_out[R * 2L]
         if (!ctx->results_valid || !ctx->last_call_rrr || !ctx->q_cache_valid) return fail(ctx, RRRMC_ERR_STATE, "no rrrMC call has been made");
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const int64_t L = is_le(ctx) ? le_levels(ctx->qM) : re_levels(ctx->qM);
         if (pos_out) HIP_TRY(ctx, hipMemcpy(pos_out, ctx->q_cls, (size_t)ctx->R * ctx->N, hipMemcpyDeviceToHost));
-        if (sizes_out) HIP_TRY(ctx, hipMemcpy(sizes_out, ctx->q_st, sizeof(int32_t) * ctx->R * 2 * re_levels(ctx->qM), hipMemcpyDeviceToHost));
+        if (sizes_out) HIP_TRY(ctx, hipMemcpy(sizes_out, ctx->q_st, sizeof(int32_t) * ctx->R * 2 * L, hipMemcpyDeviceToHost));
         return RRRMC_OK;
     }
     if ((ctx->model != RRRMC_MODEL_QUANT_RRG && ctx->model != RRRMC_MODEL_SPARSE_DISCRETIZED && !sparse_int_model(ctx)) || !ctx->results_valid || !ctx->last_call_rrr)
@@ -2061,7 +2166,7 @@ int32_t rrrmc_set_couplings_dense(rrrmc_ctx* ctx, const double* J)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_dense(c, J));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qskn = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn) || ctx->model == RRRMC_MODEL_RE_SKN;   // slice graphs: J is Nk x Nk
+    const bool qskn = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn) || ctx->model == RRRMC_MODEL_RE_SKN || ctx->model == RRRMC_MODEL_LE_SKN;   // slice graphs: J is Nk x Nk
     if (ctx->model != RRRMC_MODEL_SK_NORMAL && !qskn) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_dense is for RRRMC_MODEL_SK_NORMAL (or a GraphQuant over GraphSKNormal slices)");
     if (!J) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J is NULL");
     const int64_t N = qskn ? ctx->qNk : ctx->N;
@@ -2101,6 +2206,10 @@ int32_t rrrmc_energy_f64(rrrmc_ctx* ctx, double* E_out)
         if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphRobustEnsemble needs (gamma, beta): call rrrmc_re_set_params first");
         ctx->std_cache_live = false;
         rc = re_run_init(ctx, 1.0, false);
+    } else if (is_le(ctx)) {
+        if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphLocalEntropy needs (gamma, beta): call rrrmc_le_set_params first");
+        ctx->std_cache_live = false;
+        rc = le_run_init(ctx, 1.0, false);
     } else if (ctx->model == RRRMC_MODEL_SPARSE_F64) {
         rc = spf_run_energy(ctx);
     } else if (ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED) {
@@ -2193,7 +2302,7 @@ int32_t rrrmc_set_couplings_bits(rrrmc_ctx* ctx, const uint64_t* Jc)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_bits(c, Jc));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qsk = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk) || ctx->model == RRRMC_MODEL_RE_SK;     // the slice graph of a GraphQSKT / GraphSKRE
+    const bool qsk = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk) || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_LE_SK;     // the slice graph of a GraphQSKT / GraphSKRE / GraphSKLE
     if (ctx->model != RRRMC_MODEL_SK_BINARY && !qsk)
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_bits is for RRRMC_MODEL_SK_BINARY and for contexts made by rrrmc_ctx_create_quant_sk");
     if (!Jc) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J_chunks is NULL");

@@ -16,6 +16,8 @@ MODEL_SPARSE_DISCRETIZED = 6
 MODEL_SPARSE_LEVELS = 7
 MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN = 11, 12, 13          # GraphRobustEnsemble (rrrmc_ctx_create_re; also the selectors of rrrmc_ctx_create_multi)
 MODEL_RE = (MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN)
+MODEL_LE_EMPTY, MODEL_LE_SK, MODEL_LE_SKN = 14, 15, 16          # GraphLocalEntropy (rrrmc_ctx_create_le; also the selectors of rrrmc_ctx_create_multi)
+MODEL_LE = (MODEL_LE_EMPTY, MODEL_LE_SK, MODEL_LE_SKN)
 
 
 class Engine:
@@ -34,9 +36,11 @@ class Engine:
             # a GraphQuant over dense slices is made per device by rrrmc_ctx_create_quant_skn / _sk: the selectors 9 / 8 of the header
             kind = (X.model_kind if not quant else MODEL_QUANT_SKN if getattr(X, "skn_slices", False) else MODEL_QUANT_SK if X.sk_slices
                     else MODEL_QUANT_F64 if getattr(X, "f64_slices", False) else X.model_kind)
-            re = X.model_kind in MODEL_RE
+            re = X.model_kind in MODEL_RE or X.model_kind in MODEL_LE
             check(lib().rrrmc_ctx_create_multi(C.byref(self._ctx), kind, X.Nk if quant or re else X.N, X.K, X.M if quant or re else 0, self.R,
                                                ids, len(ids), replica0))
+        elif X.model_kind in MODEL_LE:
+            check(lib().rrrmc_ctx_create_le(C.byref(self._ctx), X.Nk, X.M, X.slice_kind, self.R, device, replica0))
         elif X.model_kind in MODEL_RE:
             check(lib().rrrmc_ctx_create_re(C.byref(self._ctx), X.Nk, X.M, X.slice_kind, self.R, device, replica0))
         elif X.model_kind == MODEL_QUANT_RRG and getattr(X, "skn_slices", False):
@@ -50,7 +54,14 @@ class Engine:
         else:
             check(lib().rrrmc_ctx_create(C.byref(self._ctx), X.model_kind, X.N, X.K, self.R, device, replica0))
         try:
-            if X.model_kind in MODEL_RE:
+            if X.model_kind in MODEL_LE:
+                if X.model_kind == MODEL_LE_SK:
+                    check(lib().rrrmc_set_couplings_bits(self._ctx, X.J.reshape(-1)), self._ctx)
+                elif X.model_kind == MODEL_LE_SKN:
+                    check(lib().rrrmc_set_couplings_dense(self._ctx, X.J.reshape(-1)), self._ctx)
+                check(lib().rrrmc_le_set_params(self._ctx, X.gamma, X.beta), self._ctx)
+                X._engine = self                # LEenergies / cenergy / distances inside a hook read this engine's live configuration
+            elif X.model_kind in MODEL_RE:
                 if X.model_kind == MODEL_RE_SK:
                     check(lib().rrrmc_set_couplings_bits(self._ctx, X.J.reshape(-1)), self._ctx)
                 elif X.model_kind == MODEL_RE_SKN:
@@ -288,7 +299,9 @@ class Engine:
         """(pos[R, N], sizes[R, 4]) of the DeltaECache after the last rrrMC call (GraphQuant); sizes[R, 16] for the DiscrGraphs
         (GraphRRG / GraphEA, rrrMC and bklMC) and the discretised DoubleGraphs, class k of replica r at [r, k]."""
         pos = np.zeros((self.R, self.X.N), np.int8)
-        ncls = 4 if self.X.model_kind == MODEL_QUANT_RRG else 2 * ((self.X.M + 1) // 2) if self.X.model_kind in MODEL_RE else 16
+        M = getattr(self.X, "M", 0)
+        ncls = (4 if self.X.model_kind == MODEL_QUANT_RRG else 2 * ((M + 1) // 2) if self.X.model_kind in MODEL_RE
+                else 2 * (M // 2 + 2 if M % 2 == 0 else (M + 1) // 2) if self.X.model_kind in MODEL_LE else 16)
         sizes = np.zeros((self.R, ncls), np.int32)
         check(lib().rrrmc_rrr_cache(self._ctx, pos.ctypes.data, sizes.ctypes.data), self._ctx)
         return pos, sizes
@@ -298,6 +311,25 @@ class Engine:
         continues is not disturbed."""
         out = np.zeros((self.R, self.X.M), np.float64)
         check(lib().rrrmc_re_energies(self._ctx, out.reshape(-1)), self._ctx)
+        return out[0] if self.R == 1 else out
+
+    def le_energies(self):
+        """LEenergies (LE.jl:259-269) of the live configuration: (M,) for one replica, (R, M) otherwise.  Read-only: a run the engine
+        continues is not disturbed (the reference's rebuilds the slice caches)."""
+        out = np.zeros((self.R, self.X.M), np.float64)
+        check(lib().rrrmc_le_energies(self._ctx, out.reshape(-1)), self._ctx)
+        return out[0] if self.R == 1 else out
+
+    def cenergy(self):
+        """cenergy (LE.jl:271-274) of the live configuration: a float for one replica, (R,) otherwise.  Read-only."""
+        out = np.zeros(self.R, np.float64)
+        check(lib().rrrmc_le_cenergy(self._ctx, out), self._ctx)
+        return float(out[0]) if self.R == 1 else out
+
+    def distances(self):
+        """distances (LE.jl:309-318) of the live configuration: (M, M) int64 for one replica, (R, M, M) otherwise.  Read-only."""
+        out = np.zeros((self.R, self.X.M, self.X.M), np.int64)
+        check(lib().rrrmc_le_distances(self._ctx, out.reshape(-1)), self._ctx)
         return out[0] if self.R == 1 else out
 
     # -- snapshots and observables (SURVEY.md §8f rank 2) ---------------------------------------------

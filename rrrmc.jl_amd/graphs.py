@@ -546,6 +546,84 @@ def REenergies(X, C=None):
     return eng.re_energies()
 
 
+class GraphLocalEntropy:
+    """``GraphLocalEntropy(Nk, M, γ, β, slice_graph)`` — the Local Entropy ensemble (src/graphs/LE.jl:183-318): M replicas of one graph (the
+    slices), each coupled to an explicit reference configuration (the "centre", under a graph of the same kind, all sharing one coupling set)
+    by ``GraphLE{M,γT}`` with γT = γ / β: ΔE0 = 2γT σc σ_(i,k) on a replica site and 2γT σc μ_i (μ_i = Σ_k σ_(i,k)) on the centre.
+    ``slice_graph`` is ``None`` (GraphEmpty: ``Graph0LE``), a binary ``GraphSK`` (``GraphSKLE``) or a ``GraphSKNormal`` with ``N == Nk``.
+    ``N = Nk * (M + 1)`` spins in the reference's order: site j is spin j // (M+1) of the centre when j % (M+1) == 0 and of replica j % (M+1)
+    otherwise (LE.jl:55-84).  β here is the graph's (γT = γ / β), not a sampler's.  ``ET = Float64``.  The centre's own energy is not part
+    of the ensemble's energy.  See ``LEenergies``, ``cenergy`` and ``distances``."""
+    energy_dtype = np.float64
+    K = 0
+
+    def __init__(self, Nk, M, gamma, beta, slice_graph=None):
+        if M <= 2:
+            raise ValueError("M must be greater than 2, given: %d" % M)                  # LE.jl:24
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal)):
+            raise TypeError("the slices of a GraphLocalEntropy are GraphEmpty (None), GraphSK or GraphSKNormal")
+        if slice_graph is not None and slice_graph.N != int(Nk):
+            raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
+        self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
+        self.gammaT = self.gamma / self.beta                                              # LE.jl:221-225
+        self.N = self.Nk * (self.M + 1)
+        self.X1 = slice_graph
+        self.slice_kind = 0 if slice_graph is None else 1 if isinstance(slice_graph, GraphSK) else 2
+        self.model_kind = 14 + self.slice_kind          # RRRMC_MODEL_LE_EMPTY / _SK / _SKN
+        self.J = None if slice_graph is None else slice_graph.J
+        self._engine = None                             # the Engine running this graph: the observables read the live configuration there
+
+    def tables(self):
+        """allΔE of GraphLE{M,γT} (rrrmc_le_tables: host only, no device)"""
+        L = self.M // 2 + 2 if self.M % 2 == 0 else (self.M + 1) // 2
+        dE = np.zeros(L, np.float64)
+        check(lib().rrrmc_le_tables(self.M, self.gamma, self.beta, dE))
+        return dE
+
+
+def Graph0LE(Nk, M, gamma, beta):
+    """``Graph0LE(Nk, M, γ, β)`` = ``GraphLocalEntropy(Nk, M, γ, β, GraphEmpty, Nk)`` (src/LEAliases.jl)."""
+    return GraphLocalEntropy(Nk, M, gamma, beta, None)
+
+
+def GraphSKLE(Nk, M, gamma, beta, seed=DEFAULT_SEED):
+    """``GraphSKLE(Nk, M, γ, β)`` = ``GraphLocalEntropy(Nk, M, γ, β, GraphSK, SK.gen_J(Nk))`` (src/LEAliases.jl): the couplings are drawn once
+    (``rrrmc_gen_sk_binary``, as ``GraphSK`` does) and shared by the centre and the M slices."""
+    return GraphLocalEntropy(Nk, M, gamma, beta, GraphSK(Nk, seed=seed))
+
+
+def _le_observable(X, C, name, fn):
+    from .engine import Engine
+    if C is not None:
+        with Engine(X, C.R) as eng:
+            eng.set_config(C)
+            return getattr(eng, fn)()
+    eng = getattr(X, "_engine", None)
+    if eng is None or not eng._ctx:
+        raise RuntimeError("%s(X): no engine is running this graph; pass a configuration: %s(X, C)" % (name, name))
+    return getattr(eng, fn)()
+
+
+def LEenergies(X, C=None):
+    """``LEenergies(X)`` (LE.jl:259-269): the energy of every replica of the ensemble as its own graph defines it — shape (M,) for one
+    replica of the batch, (R, M) otherwise — computed on the device from the CURRENT configuration of the engine that runs ``X`` (inside a
+    hook: the sample's configuration).  With ``C`` (a ``Config`` of N = Nk (M+1) spins) it is evaluated for that configuration instead.
+    Unlike the reference's, it reads the configuration only (the slice caches are not rebuilt): a hook that calls it does not change the run."""
+    return _le_observable(X, C, "LEenergies", "le_energies")
+
+
+def cenergy(X, C=None):
+    """``cenergy(X)`` (LE.jl:271-274): the energy of the centre configuration under the slice graph (0 for GraphEmpty) — a float for one
+    replica of the batch, shape (R,) otherwise; read as ``LEenergies`` reads (the live engine, or ``C``), without rebuilding any cache."""
+    return _le_observable(X, C, "cenergy", "cenergy")
+
+
+def distances(X, C=None):
+    """``distances(X)`` (LE.jl:309-318): the M x M matrix of Hamming distances between the replica configurations, centre excluded — shape
+    (M, M) for one replica of the batch, (R, M, M) otherwise (int64); read as ``LEenergies`` reads."""
+    return _le_observable(X, C, "distances", "distances")
+
+
 def checkerboard_coloring(L, D):
     """Two-colouring (parity of the coordinate sum) of the periodic L^D lattice of ``GraphEA``; L must be even."""
     if L % 2:

@@ -2,6 +2,7 @@
 """Secondary benchmarks (not the headline metric): throughput of the other model kernels on one GPU.
   python tools/bench_models.py sk      GraphSKNormal N=1024, 2048 replicas (BASELINE.json configs[2])
   python tools/bench_models.py re [R ...]   GraphSKRE(1024, 5), γ = 2, β = 0.4: rrrMC (both builds) and standardMC
+  python tools/bench_models.py le [R ...]   GraphSKLE(1024, 5), γ = 2, β = 0.4: rrrMC (both builds) and standardMC
 """
 import json
 import os
@@ -215,6 +216,41 @@ def bench_re(Nk=1024, M=5, gamma=2.0, beta=0.4, iters=1 << 14, step=1 << 12, see
         print(json.dumps(out), flush=True)
 
 
+def bench_le(Nk=1024, M=5, gamma=2.0, beta=0.4, iters=1 << 14, step=1 << 12, seed=0x5EED):
+    """GraphSKLE(1024, 5), γ = 2, β = 0.4 (bench_re's point, with the explicit centre: N = 1024 * 6): rrrMC through the thread and the LDS build
+    and standardMC, kernel iterations/s per replica count (python tools/bench_models.py le 128 1024 4096)."""
+    pkg = entry.load_package()
+    X = pkg.GraphSKLE(Nk, M, gamma, beta, seed=seed)
+    envs = ("RRRMC_LE_NO_LDS", "RRRMC_LE_LDS")
+    for R in ([int(a) for a in sys.argv[2:]] or [128, 1024, 4096]):
+        it = max(step, iters * 1024 // max(R, 1024))
+        out = {"model": "GraphSKLE", "Nk": Nk, "M": M, "gamma": gamma, "beta": beta, "replicas": R, "iters": it}
+        for name, env in (("rrr_thread", {"RRRMC_LE_NO_LDS": "1"}), ("rrr_lds", {"RRRMC_LE_LDS": "1"}), ("standard", {})):
+            for k in envs:
+                os.environ.pop(k, None)
+            os.environ.update(env)
+            eng = pkg.Engine(X, R)
+            eng.seed(seed)
+            eng.init_spins_random()
+            if name == "standard":
+                eng.standard_mc(beta, it, step)                  # warm-up, then the timed call from the configuration it left
+                Es, acc = eng.standard_mc(beta, it, step)
+                staged = np.zeros(R)
+            else:
+                eng.rrr_mc(beta, it, step)
+                Es, acc, staged = eng.rrr_mc(beta, it, step)
+            _, sweep_ms, _ = eng.last_timing()
+            out[name] = {"kernel_iterations_per_s": float(R) * it / (sweep_ms * 1e-3), "kernel_ms": sweep_ms,
+                         "acceptance": float(acc.mean()) / it, "staged_frac": float(staged.mean()) / it,
+                         "energy_per_spin": float(Es[:, -1].mean()) / X.N}
+            eng.close()
+        for k in envs:
+            os.environ.pop(k, None)
+        best = max(out["rrr_thread"]["kernel_iterations_per_s"], out["rrr_lds"]["kernel_iterations_per_s"])
+        out["iters_ratio_equal_time"] = out["standard"]["kernel_iterations_per_s"] / best
+        print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "sk"
-    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re}[which]()
+    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le}[which]()
