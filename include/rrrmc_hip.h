@@ -69,14 +69,26 @@ enum rrrmc_model {
        rrrmc_ctx_create_le, and the selectors of rrrmc_ctx_create_multi for it (N = Nk, M; K ignored) */
     RRRMC_MODEL_LE_EMPTY = 14,   /* Graph0LE (src/LEAliases.jl:18-27) */
     RRRMC_MODEL_LE_SK = 15,      /* GraphSKLE (src/LEAliases.jl:31-38) */
-    RRRMC_MODEL_LE_SKN = 16      /* GraphLocalEntropy(Nk, M, gamma, beta, GraphSKNormal, J) (test/runtests.jl:103) */
+    RRRMC_MODEL_LE_SKN = 16,     /* GraphLocalEntropy(Nk, M, gamma, beta, GraphSKNormal, J) (test/runtests.jl:103) */
+    /* the binary perceptron trained on P random patterns (src/graphs/PercStep.jl, PercLinear.jl): the model of a context made by
+       rrrmc_ctx_create_perc (N synapses; K and M ignored by rrrmc_ctx_create_multi) */
+    RRRMC_MODEL_PERC_STEP = 17,    /* GraphPercStep(N, P): energy = the number of misclassified patterns (reported as Float64) */
+    RRRMC_MODEL_PERC_LINEAR = 18,  /* GraphPercLinear(N, P) */
+    /* the two ensembles over perceptron slices that share one pattern matrix (src/REAliases.jl, src/LEAliases.jl): made by
+       rrrmc_ctx_create_re / _le with RRRMC_RE_SLICE_PERC_STEP / _PERC_LINEAR; selectors of rrrmc_ctx_create_multi (N = Nk, M; K ignored) */
+    RRRMC_MODEL_RE_PERC_STEP = 19,   /* GraphPercStepRE */
+    RRRMC_MODEL_RE_PERC_LINEAR = 20, /* GraphPercLinearRE */
+    RRRMC_MODEL_LE_PERC_STEP = 21,   /* GraphPercStepLE */
+    RRRMC_MODEL_LE_PERC_LINEAR = 22  /* GraphPercLinearLE */
 };
 
 /* slice families of rrrmc_ctx_create_re */
 enum rrrmc_re_slice {
     RRRMC_RE_SLICE_EMPTY = 0,    /* GraphEmpty (src/graphs/Empty.jl): zero residual, zero energy */
     RRRMC_RE_SLICE_SK = 1,       /* binary GraphSK (src/graphs/SK.jl:28-60): couplings with rrrmc_set_couplings_bits */
-    RRRMC_RE_SLICE_SKN = 2       /* GraphSKNormal (src/graphs/SK.jl:181-210): couplings with rrrmc_set_couplings_dense */
+    RRRMC_RE_SLICE_SKN = 2,      /* GraphSKNormal (src/graphs/SK.jl:181-210): couplings with rrrmc_set_couplings_dense */
+    RRRMC_RE_SLICE_PERC_STEP = 3,   /* GraphPercStep (src/graphs/PercStep.jl): patterns with rrrmc_set_patterns; Nk odd */
+    RRRMC_RE_SLICE_PERC_LINEAR = 4  /* GraphPercLinear (src/graphs/PercLinear.jl): patterns with rrrmc_set_patterns; Nk odd */
 };
 
 /* Library ABI version (major*10000 + minor*100 + patch). */
@@ -120,7 +132,8 @@ RRRMC_API int32_t rrrmc_ctx_create(rrrmc_ctx **out, int32_t model, int64_t N, in
  *   model  any rrrmc_model; RRRMC_MODEL_QUANT_RRG takes (N = Nk, K, M) as rrrmc_ctx_create_quant does, RRRMC_MODEL_QUANT_SK / _SKN take
  *          (N = Nk, M) as rrrmc_ctx_create_quant_sk / _skn do (K ignored), RRRMC_MODEL_QUANT_F64 takes (N = Nk, K, M) as rrrmc_ctx_create_quant_f64,
  *          RRRMC_MODEL_RE_EMPTY / _SK / _SKN take (N = Nk, M) as rrrmc_ctx_create_re does (K ignored), RRRMC_MODEL_LE_EMPTY / _SK / _SKN
- *          take (N = Nk, M) as rrrmc_ctx_create_le does (K ignored); M is ignored otherwise.
+ *          take (N = Nk, M) as rrrmc_ctx_create_le does (K ignored), and so do RRRMC_MODEL_RE_PERC_* / RRRMC_MODEL_LE_PERC_*;
+ *          RRRMC_MODEL_PERC_STEP / _LINEAR take N as rrrmc_ctx_create_perc does; M is ignored otherwise.
  */
 RRRMC_API int32_t rrrmc_ctx_create_multi(rrrmc_ctx **out, int32_t model, int64_t N, int64_t K, int64_t M, int64_t R,
                                          const int32_t *device_ids, int32_t ndev, uint32_t replica0);
@@ -265,6 +278,24 @@ RRRMC_API int32_t rrrmc_re_energies(rrrmc_ctx *ctx, double *out);
 /* Host-only (no device needed): dElist[M] = DeltaElist(GraphRE{M,gamma,beta}) = fk(mu) for mu = -(M-1), -(M-3), ..., M-1 (RE.jl:18-26, 53-56; the
  * upper ceil(M/2) entries are allDeltaE), e0[M+1] = log(2 cosh(gamma mu)) / beta for mu = -M, -M+2, ..., M (RE.jl:90-93), evaluated with libm. */
 RRRMC_API int32_t rrrmc_re_tables(int64_t M, double gamma, double beta, double *dElist, double *e0);
+
+/* ---- The binary perceptron (src/graphs/PercStep.jl, PercLinear.jl; RRRMC_MODEL_PERC_*, RRRMC_RE_SLICE_PERC_*) ------
+ * rrrmc_ctx_create_perc: R chains of GraphPercStep (linear = 0) or GraphPercLinear (linear != 0) with N synapses.  N must be odd
+ * (RRRMC_ERR_INVALID_ARG, as the reference's ArgumentError) and at most 32767 (RRRMC_ERR_UNSUPPORTED: 16-bit stabilities).  Spins: one
+ * bit per synapse in 64-bit chunks, as every chunk-layout model.  Then rrrmc_set_patterns.  Sampler: rrrmc_standard_mc_async
+ * (src/RRRMC.jl:81-127) with rrrmc_fetch_results_f64 (GraphPercStep's integer energies arrive as exact Float64s), rrrmc_set_resume,
+ * rrrmc_set_debug_checks, rrrmc_energy_f64.  rrrMC / bklMC / wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED: on these graphs they go
+ * through DeltaECacheCont with AllButOne neighbourhoods, which is not wired.
+ *
+ * rrrmc_set_patterns: the P patterns xi[P * ceil(N / 64)], row a = pattern a as ceil(N / 64) chunks, bit i of a row = xi[a, i] (the xi_v
+ * layout of gen_xi, PercStep.jl:19-29); bits beyond N must be 0.  1 <= P <= 4096 (RRRMC_ERR_UNSUPPORTED beyond).  For a context made by
+ * rrrmc_ctx_create_perc, or by rrrmc_ctx_create_re / _le with a perceptron slice kind (N = Nk: all slices, and the centre of a
+ * GraphLocalEntropy, share the one matrix).  May be called again: a new matrix (or a new P) ends a resumed run. */
+RRRMC_API int32_t rrrmc_ctx_create_perc(rrrmc_ctx **out, int64_t N, int32_t linear, int64_t R, int32_t device, uint32_t replica0);
+RRRMC_API int32_t rrrmc_set_patterns(rrrmc_ctx *ctx, const uint64_t *xi, int64_t P);
+/* gen_xi (PercStep.jl:19-29; the reference's bitrand is unpinned): xi_out[P * ceil(N / 64)] in the layout of rrrmc_set_patterns, drawn on
+ * the host from the SKBITS stream of `seed` (third counter word 1).  Needs no device. */
+RRRMC_API int32_t rrrmc_gen_patterns(int64_t N, int64_t P, uint64_t seed, uint64_t *xi_out);
 
 /* ---- GraphLocalEntropy (src/graphs/LE.jl; RRRMC_MODEL_LE_*) -------------------------------------------------------
  * The Local Entropy ensemble: M replicas of one graph, each coupled to an explicit reference ("centre") configuration by the inner graph

@@ -56,6 +56,21 @@ const SPARSE_PM1, SK_NORMAL, QUANT_RRG, SK_BINARY, SPARSE_F64, SPARSE_DISCRETIZE
 const QUANT_SK, QUANT_SKN, QUANT_F64 = 8, 9, 10      # selectors of rrrmc_ctx_create_multi: GraphQuant over GraphSK / GraphSKNormal / sparse Float64 slices
 const RE_EMPTY, RE_SK, RE_SKN = 11, 12, 13            # GraphRobustEnsemble over GraphEmpty / GraphSK / GraphSKNormal (rrrmc_ctx_create_re; multi selectors)
 const LE_EMPTY, LE_SK, LE_SKN = 14, 15, 16            # GraphLocalEntropy over GraphEmpty / GraphSK / GraphSKNormal (rrrmc_ctx_create_le; multi selectors)
+const PERC_STEP, PERC_LINEAR = 17, 18                 # GraphPercStep, GraphPercLinear (rrrmc_ctx_create_perc; multi selectors)
+const RE_MODELS = (RE_EMPTY, RE_SK, RE_SKN, 19, 20)   # by slice kind 0..4 (3, 4: GraphPercStep, GraphPercLinear slices)
+const LE_MODELS = (LE_EMPTY, LE_SK, LE_SKN, 21, 22)
+const PercGraph = Union{RRRMC.PercStep.GraphPercStep,RRRMC.PercLinear.GraphPercLinear}
+# slice kind of an ensemble's graph type (rrrmc_re_slice)
+ens_kind(G, what) = G <: RRRMC.SK.GraphSK ? 1 : G <: RRRMC.SK.GraphSKNormal ? 2 : G <: RRRMC.Empty.GraphEmpty ? 0 :
+                    G <: RRRMC.PercStep.GraphPercStep ? 3 : G <: RRRMC.PercLinear.GraphPercLinear ? 4 :
+                    throw(ArgumentError("the engine runs the $what over GraphEmpty, GraphSK, GraphSKNormal, GraphPercStep and GraphPercLinear slices, given: $G"))
+# the patterns of a perceptron as P rows of chunks (ξv, PercStep.jl:19-29): rrrmc_set_patterns
+function set_patterns!(ctx, X1::PercGraph)
+    nch = (X1.N + 63) >> 6
+    xi = Matrix{UInt64}(undef, nch, X1.P); for a = 1:X1.P; xi[:, a] = X1.ξv[a].chunks; end
+    GC.@preserve xi check(ccall((:rrrmc_set_patterns, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt64}, Int64), ctx.p, xi, X1.P), ctx.p)
+    return ctx
+end
 
 # rrrmc_ctx_create / rrrmc_ctx_create_quant on one device, rrrmc_ctx_create_multi on several (N = Nk for a GraphQuant)
 function create(model::Integer, N::Integer, K::Integer, M::Integer, R::Integer; device = 0, replica0 = 0, devices = nothing)
@@ -203,13 +218,12 @@ end
 # spins in the reference's order (site (i-1)M + k = spin i of replica k), so C.s.chunks passes as is; the M slices share one coupling set
 function Ctx(X::RRRMC.RE.GraphRobustEnsemble{M,γ,β,G}, R::Integer; device = 0, replica0 = 0, devices = nothing) where {M,γ,β,G}
     Nk = X.Nk
-    kind = G <: RRRMC.SK.GraphSK ? 1 : G <: RRRMC.SK.GraphSKNormal ? 2 : G <: RRRMC.Empty.GraphEmpty ? 0 :
-           throw(ArgumentError("the engine runs the Robust Ensemble over GraphEmpty, GraphSK and GraphSKNormal slices, given: $G"))
+    kind = ens_kind(G, "Robust Ensemble")
     ref = Ref{Ptr{Cvoid}}(C_NULL)
     if devices === nothing
         check(ccall((:rrrmc_ctx_create_re, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, Int64, Int32, UInt32), ref, Nk, M, kind, R, device, replica0))
     else
-        ref[] = create(RE_EMPTY + kind, Nk, 0, M, R; replica0 = replica0, devices = devices)
+        ref[] = create(RE_MODELS[kind + 1], Nk, 0, M, R; replica0 = replica0, devices = devices)
     end
     ctx = Ctx(ref[], R, Nk * M, true)
     X1 = X.X1[1]
@@ -220,8 +234,22 @@ function Ctx(X::RRRMC.RE.GraphRobustEnsemble{M,γ,β,G}, R::Integer; device = 0,
         Jm = Matrix{Float64}(undef, Nk, Nk); for i = 1:Nk; Jm[:, i] = X1.J[i]; end
         GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
     end
+    kind >= 3 && set_patterns!(ctx, X1)
     check(ccall((:rrrmc_re_set_params, LIB), Int32, (Ptr{Cvoid}, Float64, Float64), ctx.p, γ, β), ctx.p)
     return ctx
+end
+
+# ---- GraphPercStep / GraphPercLinear (src/graphs/PercStep.jl, PercLinear.jl), stand-alone: standardMC only ------------------------------
+# (rrrMC / bklMC / wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED).  GraphPercStep's integer energies arrive as exact Float64s.
+function Ctx(X::PercGraph, R::Integer; device = 0, replica0 = 0, devices = nothing)
+    lin = X isa RRRMC.PercLinear.GraphPercLinear
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    if devices === nothing
+        check(ccall((:rrrmc_ctx_create_perc, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int32, Int64, Int32, UInt32), ref, X.N, lin ? 1 : 0, R, device, replica0))
+    else
+        ref[] = create(lin ? PERC_LINEAR : PERC_STEP, X.N, 0, 0, R; replica0 = replica0, devices = devices)
+    end
+    return set_patterns!(Ctx(ref[], R, X.N, true), X)
 end
 # REenergies of every replica of the batch, read on the device from the live configuration: column r = replica r (RE.jl:285-301)
 function re_energies(ctx::Ctx, M::Integer)
@@ -247,13 +275,12 @@ re_hook(X::RRRMC.RE.GraphRobustEnsemble, hook) = (it, X_, C, a, b) -> (re_slices
 # γT / 1 is γT exactly
 function Ctx(X::RRRMC.LE.GraphLocalEntropy{M,γT,G}, R::Integer; device = 0, replica0 = 0, devices = nothing) where {M,γT,G}
     Nk = X.Nk
-    kind = G <: RRRMC.SK.GraphSK ? 1 : G <: RRRMC.SK.GraphSKNormal ? 2 : G <: RRRMC.Empty.GraphEmpty ? 0 :
-           throw(ArgumentError("the engine runs the Local Entropy ensemble over GraphEmpty, GraphSK and GraphSKNormal slices, given: $G"))
+    kind = ens_kind(G, "Local Entropy ensemble")
     ref = Ref{Ptr{Cvoid}}(C_NULL)
     if devices === nothing
         check(ccall((:rrrmc_ctx_create_le, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, Int64, Int32, UInt32), ref, Nk, M, kind, R, device, replica0))
     else
-        ref[] = create(LE_EMPTY + kind, Nk, 0, M, R; replica0 = replica0, devices = devices)
+        ref[] = create(LE_MODELS[kind + 1], Nk, 0, M, R; replica0 = replica0, devices = devices)
     end
     ctx = Ctx(ref[], R, Nk * (M + 1), true)
     X1 = X.X1[1]
@@ -264,6 +291,7 @@ function Ctx(X::RRRMC.LE.GraphLocalEntropy{M,γT,G}, R::Integer; device = 0, rep
         Jm = Matrix{Float64}(undef, Nk, Nk); for i = 1:Nk; Jm[:, i] = X1.J[i]; end
         GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
     end
+    kind >= 3 && set_patterns!(ctx, X1)
     check(ccall((:rrrmc_le_set_params, LIB), Int32, (Ptr{Cvoid}, Float64, Float64), ctx.p, γT, 1.0), ctx.p)
     return ctx
 end

@@ -28,6 +28,7 @@ SYMBOLS = [
     "rrrmc_set_graph_f64", "rrrmc_gen_couplings_gauss", "rrrmc_set_graph_discretized", "rrrmc_set_level_scale", "rrrmc_discretize", "rrrmc_discretize_scaled", "rrrmc_wtm_mc_async", "rrrmc_wtm_times", "rrrmc_extremal_opt_async", "rrrmc_extremal_opt_results", "rrrmc_extremal_opt_results_f64",
     "rrrmc_ctx_create_re", "rrrmc_re_set_params", "rrrmc_re_energies", "rrrmc_re_tables",
     "rrrmc_ctx_create_le", "rrrmc_le_set_params", "rrrmc_le_energies", "rrrmc_le_cenergy", "rrrmc_le_distances", "rrrmc_le_tables",
+    "rrrmc_ctx_create_perc", "rrrmc_set_patterns", "rrrmc_gen_patterns",
 ]
 
 
@@ -216,6 +217,12 @@ def lib():
     L.rrrmc_le_energies.argtypes = [vp, f64p]
     L.rrrmc_le_cenergy.restype = C.c_int32
     L.rrrmc_le_cenergy.argtypes = [vp, f64p]
+    L.rrrmc_ctx_create_perc.restype = C.c_int32
+    L.rrrmc_ctx_create_perc.argtypes = [C.POINTER(vp), C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_uint32]
+    L.rrrmc_set_patterns.restype = C.c_int32
+    L.rrrmc_set_patterns.argtypes = [vp, u64p, C.c_int64]
+    L.rrrmc_gen_patterns.restype = C.c_int32
+    L.rrrmc_gen_patterns.argtypes = [C.c_int64, C.c_int64, C.c_uint64, u64p]
     L.rrrmc_le_distances.restype = C.c_int32
     L.rrrmc_le_distances.argtypes = [vp, i64p]
     L.rrrmc_le_tables.restype = C.c_int32

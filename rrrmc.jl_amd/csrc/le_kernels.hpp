@@ -101,6 +101,8 @@ __global__ __launch_bounds__(kReInitThreads) void le_init_kernel(LeParams P, int
         for (int k = tid; k < rows; k += kReInitThreads) { v.smv[k] = -1; v.scur[k] = 0; }
         __syncthreads();
         for (int x = Nk + tid; x < N; x += kReInitThreads) v.slf[(size_t)rows * Nk + x] = 0.0;
+    } else if constexpr (kPercSlice<SLICE>) {
+        perc_init_rows<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, Nk, N, s_n);          // (row 0, the centre: built, never used)
     }
     __syncthreads();
     if (cache) {
@@ -136,6 +138,7 @@ __global__ __launch_bounds__(kReInitThreads) void le_init_kernel(LeParams P, int
         for (int k = 1; k < rows; ++k) {
             if constexpr (SLICE == RE_SK) { long long n = s_n[k]; n /= 2; E += (double)n / P.sN; }
             else if constexpr (SLICE == RE_SKN) E += s_E[k];
+            else if constexpr (kPercSlice<SLICE>) E += perc_energy_of<SLICE == RE_PLIN>(s_n[k], P.pc.sN);
             else E += 0.0;
         }
         P.E_cur[r] = E;
@@ -156,7 +159,7 @@ __global__ __launch_bounds__(kReInitThreads) void le_init_kernel(LeParams P, int
 }
 
 // bytes of LDS one replica takes in the LDS build below: spins, positions, classes, μ, set sizes, the RRR draws of 64 iterations
-inline size_t le_rrr_lds_bytes(int64_t N, int64_t W, int64_t Nk)
+__host__ __device__ inline size_t le_rrr_lds_bytes(int64_t N, int64_t W, int64_t Nk)
 {
     return (size_t)W * 4 + (((size_t)N * 2 + 3) & ~(size_t)3) + (((size_t)N + 3) & ~(size_t)3) + (((size_t)Nk + 3) & ~(size_t)3) +
            (size_t)2 * kLeLmax * 4 + (size_t)kRrrThreads * 8 * 4;
@@ -165,10 +168,11 @@ inline size_t le_rrr_lds_bytes(int64_t N, int64_t W, int64_t Nk)
 // rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290) on the Local Entropy ensemble; the builds and the register layout of the class weights are
 // re_rrr_kernel's (LM >= L classes per half in registers, LDS = one wavefront per replica with its hot state in LDS).  Neighbours in the
 // order of apply_move! / compute_staged! (LE.jl:166-174): a centre move's M replicas ascending, a replica move's centre; then the move.
+// Perceptron slices in the LDS build: as in re_rrr_kernel, the Stabilities are staged in LDS and all 64 lanes run the chain.
 template <bool LDS, int LM, int SLICE>
 __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
 {
-    extern __shared__ uint32_t le_lds[];
+    extern __shared__ __attribute__((aligned(16))) uint32_t le_lds[];
     int r;
     if constexpr (LDS) {
         r = (int)blockIdx.x;
@@ -201,7 +205,18 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
         sp = l_sp; spos = l_spos; cls = l_cls; mu = l_mu; t = l_t;
     }
     const RrrView v = re_view(P, sp, r);
-    const bool worker = !LDS || threadIdx.x == 0;
+    const PercView g_pv = perc_view(P.pc, r);
+    PercView pv = g_pv;
+    if constexpr (LDS && kPercSlice<SLICE>) {
+        const int nw = rows * P.pc.PW;                                             // mask words, then 64 stabilities per word
+        pv.pm = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(le_lds) + ((le_rrr_lds_bytes(N, P.W, Nk) + 7) & ~(size_t)7));
+        pv.mm = pv.pm + nw;
+        pv.ds = reinterpret_cast<int16_t*>(pv.mm + nw);
+        for (int i = (int)threadIdx.x; i < nw; i += (int)blockDim.x) { pv.pm[i] = g_pv.pm[i]; pv.mm[i] = g_pv.mm[i]; }
+        for (int i = (int)threadIdx.x; i < 64 * nw; i += (int)blockDim.x) pv.ds[i] = g_pv.ds[i];
+        __syncthreads();
+    }
+    const bool worker = !LDS || threadIdx.x == 0 || kPercSlice<SLICE>;
     const uint32_t rep = P.replica0 + (uint32_t)r;
     const double* tab = P.tab;
     const double* ft = P.ft;
@@ -318,7 +333,7 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
         const int move = sv[(size_t)kc * N + (size_t)mulhi64(uu, (uint64_t)t[kc])];
         const int i = move / rows, km = move - i * rows, xm = km * Nk + i;
         // delta_energy_residual (LE.jl:276-290): 0.0 for the centre, the replica slice's delta_energy (not divided by M)
-        const double dE1 = km == 0 ? 0.0 : re_residual<SLICE>(v, xm, km, i);
+        const double dE1 = km == 0 ? 0.0 : re_residual<SLICE>(v, pv, xm, km, i);
 
         bool acc = false;
         if (acc_rate < P.staged_thr) {
@@ -343,7 +358,7 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
             const double c = z / zp;
             if (accept_c(c, -P.beta * dE1, q2, g)) {
                 sflip(sp, xm);                                             // spinflip!(X, C, move)
-                if (km != 0) { mu[i] = (int8_t)mu_new; re_slice_update<SLICE>(v, xm); }
+                if (km != 0) { mu[i] = (int8_t)mu_new; re_slice_update<SLICE, LDS>(v, pv, xm, km, i); }
                 neighbours(i, km, sc_new, mu_new, [&](int y, int k0, int k1) { set_move(y, k0, k1); });     // apply_staged!
                 { const int k0 = cls[move]; set_move(move, k0, k0 >= L ? k0 - L : k0 + L); }
 #pragma unroll
@@ -359,7 +374,8 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
                 sflip(sp, xm);
                 if (km != 0) {
                     mu[i] = (int8_t)(mu[i] + 2 * (2 * sbit(sp, xm) - 1));
-                    re_slice_update<SLICE>(v, xm);                         // the undo pass takes the slice's swap path (move_last == move)
+                    // the undo pass takes the slice's swap path (move_last == move); perceptron slices: once, below, when accepted
+                    if constexpr (!kPercSlice<SLICE>) re_slice_update<SLICE>(v, xm);
                 }
                 double zp = z;
                 auto apply = [&](int y, int k0, int k1) {
@@ -376,6 +392,7 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
                 if (pass == 1) break;                                      // that was the undo
                 if (accept_c(cc, -P.beta * dE1, q2, g)) { E += dE0 + dE1; accepted += 1; acc = true; break; }
             }
+            if constexpr (kPercSlice<SLICE>) { if (acc && km != 0) re_slice_update<SLICE, LDS>(v, pv, xm, km, i); }
         }
         acc_rate = acc_rate * (1 - P.lambda) + (acc ? 1.0 : 0.0) * P.lambda;          // RRRMC.jl:281
     }
@@ -389,6 +406,12 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
         }
         P.zz[r] = z; P.E_cur[r] = E; P.acc_rate[r] = acc_rate;
         P.stats[(size_t)r * 2] = accepted; P.stats[(size_t)r * 2 + 1] = staged_its;
+    }
+    if constexpr (LDS && kPercSlice<SLICE>) {
+        __syncthreads();
+        const int nw = rows * P.pc.PW;
+        for (int i = (int)threadIdx.x; i < nw; i += (int)blockDim.x) { g_pv.pm[i] = pv.pm[i]; g_pv.mm[i] = pv.mm[i]; }
+        for (int i = (int)threadIdx.x; i < 64 * nw; i += (int)blockDim.x) g_pv.ds[i] = pv.ds[i];
     }
     if constexpr (LDS) {
         __syncthreads();
@@ -411,6 +434,7 @@ __global__ __launch_bounds__(kRrrThreads) void le_standard_kernel(LeParams P)
     uint32_t* sp = P.sp + (size_t)r * P.W;
     int8_t* mu = P.mu + (size_t)r * Nk;
     const RrrView v = re_view(P, sp, r);
+    const PercView pv = perc_view(P.pc, r);
     const uint32_t rep = P.replica0 + (uint32_t)r;
     double E = P.E_cur[r];
     int64_t accepted = 0, ns = 0;
@@ -422,14 +446,14 @@ __global__ __launch_bounds__(kRrrThreads) void le_standard_kernel(LeParams P)
         const int i = j / rows, k = j - i * rows, x = k * Nk + i;
         const int sg = 2 * sbit(sp, x) - 1, sc = 2 * sbit(sp, i) - 1;
         const int lf = k == 0 ? sc * mu[i] : sc * sg;
-        const double dE = P.g2 * (double)lf + (k == 0 ? 0.0 : re_residual<SLICE>(v, x, k, i));
+        const double dE = P.g2 * (double)lf + (k == 0 ? 0.0 : re_residual<SLICE>(v, pv, x, k, i));
         const double xx = -P.beta * dE;
         const bool acc = (xx >= 0.0) || (rand53(P.k0, P.k1, g, rep) < det_exp(xx));          // RRRMC.jl:39
         if (acc) {
             sflip(sp, x);
             if (k != 0) {
                 mu[i] = (int8_t)(mu[i] - 2 * sg);
-                re_slice_update<SLICE>(v, x);
+                re_slice_update<SLICE, false>(v, pv, x, k, i);
             }
             E += dE;
             accepted += 1;
@@ -502,6 +526,7 @@ __global__ __launch_bounds__(64) void le_check_kernel(LeParams P, int cache)
                 bad = bad || !(dd <= 1e-10 * Nk && dd >= -1e-10 * Nk);
             }
     }
+    if constexpr (kPercSlice<SLICE>) bad = bad || perc_state_bad<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, 1, Nk, N);
     if (cache) {
         int cnt[2 * kLeLmax];
         for (int k = 0; k < 2 * L; ++k) cnt[k] = 0;

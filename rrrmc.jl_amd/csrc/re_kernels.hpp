@@ -16,16 +16,20 @@
 #include <stdint.h>
 
 #include "rrr_kernels.hpp"   // RrrView, sbit / sflip, slice_delta, skn_update, kRrrThreads, TAG_RRR, det_exp
+#include "perc_kernels.hpp"  // the binary perceptron slices (PercParams, perc_residual, perc_update, perc_init_rows)
 
 namespace rrrmc {
 
-enum ReSlice { RE_EMPTY = 0, RE_SK = 1, RE_SKN = 2 };        // GraphEmpty (Graph0RE), binary GraphSK (GraphSKRE), GraphSKNormal
+enum ReSlice { RE_EMPTY = 0, RE_SK = 1, RE_SKN = 2,          // GraphEmpty (Graph0RE), binary GraphSK (GraphSKRE), GraphSKNormal
+               RE_PSTEP = 3, RE_PLIN = 4 };                  // GraphPercStep (GraphPercStepRE), GraphPercLinear (GraphPercLinearRE)
+template <int SLICE> constexpr bool kPercSlice = SLICE == RE_PSTEP || SLICE == RE_PLIN;
 constexpr int kReMmax = 32;                                 // replicas of the ensemble; levels L = ceil(M / 2) <= 16
 
 struct ReParams {
     // the slice graph, shared by the M slices
     const uint32_t* Jb; int Wk; double sN;                  // binary GraphSK: rows of J as 32-bit words, sqrt(Nk)
     const double* Jd;                                       // GraphSKNormal: [Nk][Nk]
+    PercParams pc;                                          // perceptron slices: the shared patterns, every slice's Stabilities
     double* slf;                                            // [R][2][M][Nk]  every slice's lfields / lfields_last (SK.jl:212-276)
     int32_t* smv;                                           // [R][M]         move_last of every slice (-1 = none)
     uint8_t* scur;                                          // [R][M]         which of the two arrays is `lfields`
@@ -84,6 +88,19 @@ __device__ __forceinline__ void re_slice_update(const RrrView& v, int x)
 {
     if constexpr (SLICE == RE_SKN) skn_update(v, x);
 }
+// the same two with the perceptron slices (perc_kernels.hpp), whose state is not part of the RrrView; WAVE: the wavefront-wide update
+template <int SLICE>
+__device__ __forceinline__ double re_residual(const RrrView& v, const PercView& pv, int x, int k, int i)
+{
+    if constexpr (kPercSlice<SLICE>) return perc_residual<SLICE == RE_PLIN>(pv, k, i, sbit(v.sp, x));
+    else return re_residual<SLICE>(v, x, k, i);
+}
+template <int SLICE, bool WAVE>
+__device__ __forceinline__ void re_slice_update(const RrrView& v, const PercView& pv, int x, int k, int i)
+{
+    if constexpr (kPercSlice<SLICE>) perc_update<SLICE == RE_PLIN, WAVE>(pv, k, i, sbit(v.sp, x));
+    else re_slice_update<SLICE>(v, x);
+}
 // class of ABI site j with spin bit s, for the group's μ = mub + σ: a + L up (DeltaE.jl:80-86 with lfields[j] = σ_j fk(mū), RE.jl:101)
 __device__ __forceinline__ int re_class(const double* tab, int M, int L, int mub, int s)
 {
@@ -116,6 +133,8 @@ __device__ inline double re_slice_energy(const ReParams& P, const RrrView& v, in
         }
         n /= 2;
         return n;
+    } else if constexpr (kPercSlice<SLICE>) {
+        return perc_row_energy<SLICE == RE_PLIN>(P.pc, v.sp, k * Nk, Nk, P.N);
     } else {
         return 0.0;
     }
@@ -198,6 +217,8 @@ __global__ __launch_bounds__(kReInitThreads) void re_init_kernel(ReParams P, int
         }
         __syncthreads();
         for (int x = tid; x < N; x += kReInitThreads) v.slf[(size_t)M * Nk + x] = 0.0;
+    } else if constexpr (kPercSlice<SLICE>) {
+        perc_init_rows<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, Nk, N, s_n);
     }
     __syncthreads();
     if (cache) {
@@ -234,6 +255,7 @@ __global__ __launch_bounds__(kReInitThreads) void re_init_kernel(ReParams P, int
         for (int k = 0; k < M; ++k) {
             if constexpr (SLICE == RE_SK) { long long n = s_n[k]; n /= 2; E += (double)n / P.sN; }
             else if constexpr (SLICE == RE_SKN) E += s_E[k];
+            else if constexpr (kPercSlice<SLICE>) E += perc_energy_of<SLICE == RE_PLIN>(s_n[k], P.pc.sN);
             else E += 0.0;
         }
         P.E_cur[r] = E;
@@ -254,7 +276,7 @@ __global__ __launch_bounds__(kReInitThreads) void re_init_kernel(ReParams P, int
 }
 
 // bytes of LDS one replica takes in the LDS build below: spins, positions, classes, μ, set sizes, the RRR draws of 64 iterations
-inline size_t re_rrr_lds_bytes(int64_t N, int64_t W, int64_t Nk)
+__host__ __device__ inline size_t re_rrr_lds_bytes(int64_t N, int64_t W, int64_t Nk)
 {
     return (size_t)W * 4 + (((size_t)N * 2 + 3) & ~(size_t)3) + (((size_t)N + 3) & ~(size_t)3) + (((size_t)Nk + 3) & ~(size_t)3) +
            (size_t)kReMmax * 4 + (size_t)kRrrThreads * 8 * 4;
@@ -266,10 +288,12 @@ inline size_t re_rrr_lds_bytes(int64_t N, int64_t W, int64_t Nk)
 // LDS = true:  one workgroup (one wavefront) per replica with the replica's spins, positions, classes, μ and set sizes staged in LDS; the
 //   two Philox blocks of 64 iterations are computed by the whole wavefront, then lane 0 runs the chain (rrr_quant_kernel<true>'s pattern).
 //   The member arrays (2 L N entries) stay in HBM/L2.  Same arithmetic, same order: the results are the thread build's.
+//   Perceptron slices: the Stabilities of the M slices are staged in LDS too, and ALL 64 lanes run the chain with identical values, so
+//   that the O(P) update_cache! of an accepted move is one pattern per lane (perc_update<.., true>); stores name one address wave-wide.
 template <bool LDS, int LM, int SLICE>
 __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
 {
-    extern __shared__ uint32_t re_lds[];
+    extern __shared__ __attribute__((aligned(16))) uint32_t re_lds[];
     int r;
     if constexpr (LDS) {
         r = (int)blockIdx.x;
@@ -302,7 +326,18 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
         sp = l_sp; spos = l_spos; cls = l_cls; mu = l_mu; t = l_t;
     }
     const RrrView v = re_view(P, sp, r);
-    const bool worker = !LDS || threadIdx.x == 0;
+    const PercView g_pv = perc_view(P.pc, r);
+    PercView pv = g_pv;
+    if constexpr (LDS && kPercSlice<SLICE>) {
+        const int nw = M * P.pc.PW;                                                // mask words, then 64 stabilities per word
+        pv.pm = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(re_lds) + ((re_rrr_lds_bytes(N, P.W, Nk) + 7) & ~(size_t)7));
+        pv.mm = pv.pm + nw;
+        pv.ds = reinterpret_cast<int16_t*>(pv.mm + nw);
+        for (int i = (int)threadIdx.x; i < nw; i += (int)blockDim.x) { pv.pm[i] = g_pv.pm[i]; pv.mm[i] = g_pv.mm[i]; }
+        for (int i = (int)threadIdx.x; i < 64 * nw; i += (int)blockDim.x) pv.ds[i] = g_pv.ds[i];
+        __syncthreads();
+    }
+    const bool worker = !LDS || threadIdx.x == 0 || kPercSlice<SLICE>;
     const uint32_t rep = P.replica0 + (uint32_t)r;
     const double* tab = P.tab;
     const double* ft = P.ft;
@@ -432,11 +467,11 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
                 zp += f1 - f0;
             }
             const double c = z / zp;
-            const double dE1 = re_residual<SLICE>(v, xm, km, i);          // delta_energy_residual, RE.jl:303-310
+            const double dE1 = re_residual<SLICE>(v, pv, xm, km, i);      // delta_energy_residual, RE.jl:303-310
             if (accept_c(c, -P.beta * dE1, q2, g)) {
                 sflip(sp, xm);                                             // spinflip!(X, C, move)
                 mu[i] = (int8_t)munew;
-                re_slice_update<SLICE>(v, xm);
+                re_slice_update<SLICE, LDS>(v, pv, xm, km, i);
                 for (int y = jg; y < jg + M; ++y) {                        // apply_staged!
                     if (y == move) continue;
                     const int sy = sbit(sp, (y - jg) * Nk + i);
@@ -453,13 +488,15 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
             }
         } else {
             // direct branch: apply_move! (DeltaE.jl:232-295), undone by a second apply_move! on rejection
-            const double dE1 = re_residual<SLICE>(v, xm, km, i);
+            const double dE1 = re_residual<SLICE>(v, pv, xm, km, i);
             for (int pass = 0; pass < 2; ++pass) {
                 sflip(sp, xm);
                 const int s_new = sbit(sp, xm);
                 const int munew = mu[i] + 2 * (2 * s_new - 1);
                 mu[i] = (int8_t)munew;
-                re_slice_update<SLICE>(v, xm);                             // the undo pass takes the slice's swap path (move_last == move)
+                // the undo pass takes the slice's swap path (move_last == move); a perceptron slice's Stabilities are a function of the
+                // configuration, which a rejected move leaves as it was: they are updated once, below, for an accepted move
+                if constexpr (!kPercSlice<SLICE>) re_slice_update<SLICE>(v, xm);
                 double zp = z;
                 for (int y = jg; y < jg + M; ++y) {
                     if (y == move) continue;
@@ -485,6 +522,7 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
                 if (pass == 1) break;                                      // that was the undo
                 if (accept_c(cc, -P.beta * dE1, q2, g)) { E += dE0 + dE1; accepted += 1; acc = true; break; }
             }
+            if constexpr (kPercSlice<SLICE>) { if (acc) re_slice_update<SLICE, LDS>(v, pv, xm, km, i); }
         }
         acc_rate = acc_rate * (1 - P.lambda) + (acc ? 1.0 : 0.0) * P.lambda;          // RRRMC.jl:281
     }
@@ -498,6 +536,12 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
         }
         P.zz[r] = z; P.E_cur[r] = E; P.acc_rate[r] = acc_rate;
         P.stats[(size_t)r * 2] = accepted; P.stats[(size_t)r * 2 + 1] = staged_its;
+    }
+    if constexpr (LDS && kPercSlice<SLICE>) {
+        __syncthreads();
+        const int nw = M * P.pc.PW;
+        for (int i = (int)threadIdx.x; i < nw; i += (int)blockDim.x) { g_pv.pm[i] = pv.pm[i]; g_pv.mm[i] = pv.mm[i]; }
+        for (int i = (int)threadIdx.x; i < 64 * nw; i += (int)blockDim.x) g_pv.ds[i] = pv.ds[i];
     }
     if constexpr (LDS) {
         __syncthreads();
@@ -520,6 +564,7 @@ __global__ __launch_bounds__(kRrrThreads) void re_standard_kernel(ReParams P)
     uint32_t* sp = P.sp + (size_t)r * P.W;
     int8_t* mu = P.mu + (size_t)r * Nk;
     const RrrView v = re_view(P, sp, r);
+    const PercView pv = perc_view(P.pc, r);
     const uint32_t rep = P.replica0 + (uint32_t)r;
     double E = P.E_cur[r];
     int64_t accepted = 0, ns = 0;
@@ -530,13 +575,13 @@ __global__ __launch_bounds__(kRrrThreads) void re_standard_kernel(ReParams P)
         const int j = (int)site_of(P.k0, P.k1, g, (uint32_t)P.N);
         const int i = j / M, k = j - i * M, x = k * Nk + i;
         const int s = sbit(sp, x), sg = 2 * s - 1;
-        const double dE = (double)sg * P.tab[(mu[i] - sg + M - 1) >> 1] + re_residual<SLICE>(v, x, k, i);
+        const double dE = (double)sg * P.tab[(mu[i] - sg + M - 1) >> 1] + re_residual<SLICE>(v, pv, x, k, i);
         const double xx = -P.beta * dE;
         const bool acc = (xx >= 0.0) || (rand53(P.k0, P.k1, g, rep) < det_exp(xx));          // RRRMC.jl:39
         if (acc) {
             sflip(sp, x);
             mu[i] = (int8_t)(mu[i] - 2 * sg);
-            re_slice_update<SLICE>(v, x);
+            re_slice_update<SLICE, false>(v, pv, x, k, i);
             E += dE;
             accepted += 1;
         }
@@ -591,6 +636,7 @@ __global__ __launch_bounds__(64) void re_check_kernel(ReParams P, int cache)
                 bad = bad || !(dd <= 1e-10 * Nk && dd >= -1e-10 * Nk);
             }
     }
+    if constexpr (kPercSlice<SLICE>) bad = bad || perc_state_bad<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, 0, Nk, N);
     if (cache) {
         int cnt[2 * (kReMmax / 2)];
         for (int k = 0; k < 2 * L; ++k) cnt[k] = 0;

@@ -15,9 +15,11 @@ MODEL_SPARSE_F64 = 5
 MODEL_SPARSE_DISCRETIZED = 6
 MODEL_SPARSE_LEVELS = 7
 MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN = 11, 12, 13          # GraphRobustEnsemble (rrrmc_ctx_create_re; also the selectors of rrrmc_ctx_create_multi)
-MODEL_RE = (MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN)
+MODEL_PERC = (17, 18)                                            # GraphPercStep, GraphPercLinear (rrrmc_ctx_create_perc)
+MODEL_RE_PERC, MODEL_LE_PERC = (19, 20), (21, 22)                # the ensembles over perceptron slices (rrrmc_set_patterns)
+MODEL_RE = (MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN) + MODEL_RE_PERC
 MODEL_LE_EMPTY, MODEL_LE_SK, MODEL_LE_SKN = 14, 15, 16          # GraphLocalEntropy (rrrmc_ctx_create_le; also the selectors of rrrmc_ctx_create_multi)
-MODEL_LE = (MODEL_LE_EMPTY, MODEL_LE_SK, MODEL_LE_SKN)
+MODEL_LE = (MODEL_LE_EMPTY, MODEL_LE_SK, MODEL_LE_SKN) + MODEL_LE_PERC
 
 
 class Engine:
@@ -39,6 +41,8 @@ class Engine:
             re = X.model_kind in MODEL_RE or X.model_kind in MODEL_LE
             check(lib().rrrmc_ctx_create_multi(C.byref(self._ctx), kind, X.Nk if quant or re else X.N, X.K, X.M if quant or re else 0, self.R,
                                                ids, len(ids), replica0))
+        elif X.model_kind in MODEL_PERC:
+            check(lib().rrrmc_ctx_create_perc(C.byref(self._ctx), X.N, int(X.model_kind == 18), self.R, device, replica0))
         elif X.model_kind in MODEL_LE:
             check(lib().rrrmc_ctx_create_le(C.byref(self._ctx), X.Nk, X.M, X.slice_kind, self.R, device, replica0))
         elif X.model_kind in MODEL_RE:
@@ -54,15 +58,21 @@ class Engine:
         else:
             check(lib().rrrmc_ctx_create(C.byref(self._ctx), X.model_kind, X.N, X.K, self.R, device, replica0))
         try:
-            if X.model_kind in MODEL_LE:
-                if X.model_kind == MODEL_LE_SK:
+            if X.model_kind in MODEL_PERC:
+                check(lib().rrrmc_set_patterns(self._ctx, X.xi.reshape(-1), X.P), self._ctx)
+            elif X.model_kind in MODEL_LE:
+                if X.model_kind in MODEL_LE_PERC:
+                    check(lib().rrrmc_set_patterns(self._ctx, X.X1.xi.reshape(-1), X.X1.P), self._ctx)
+                elif X.model_kind == MODEL_LE_SK:
                     check(lib().rrrmc_set_couplings_bits(self._ctx, X.J.reshape(-1)), self._ctx)
                 elif X.model_kind == MODEL_LE_SKN:
                     check(lib().rrrmc_set_couplings_dense(self._ctx, X.J.reshape(-1)), self._ctx)
                 check(lib().rrrmc_le_set_params(self._ctx, X.gamma, X.beta), self._ctx)
                 X._engine = self                # LEenergies / cenergy / distances inside a hook read this engine's live configuration
             elif X.model_kind in MODEL_RE:
-                if X.model_kind == MODEL_RE_SK:
+                if X.model_kind in MODEL_RE_PERC:
+                    check(lib().rrrmc_set_patterns(self._ctx, X.X1.xi.reshape(-1), X.X1.P), self._ctx)
+                elif X.model_kind == MODEL_RE_SK:
                     check(lib().rrrmc_set_couplings_bits(self._ctx, X.J.reshape(-1)), self._ctx)
                 elif X.model_kind == MODEL_RE_SKN:
                     check(lib().rrrmc_set_couplings_dense(self._ctx, X.J.reshape(-1)), self._ctx)

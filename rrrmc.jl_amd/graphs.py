@@ -488,6 +488,113 @@ def GraphQSKT(Nk, M, Gamma, beta, seed=DEFAULT_SEED):
     return GraphQuant(GraphSK(Nk, seed=seed), M, Gamma, beta)
 
 
+class _GraphPerc:
+    """The binary perceptron with ``N`` (odd) binary synapses trained on ``P`` random ±1 patterns (src/graphs/PercStep.jl, PercLinear.jl).
+    ``xi`` holds the patterns as P rows of ceil(N/64) chunks, bit i of row a = ξ[a, i] (the ξv representation of gen_ξ; 1 means +1).  The
+    reference draws them with an unpinned ``bitrand``: here ``seed`` names them (``rrrmc_gen_patterns``, host only), and
+    ``from_patterns(ξ)`` takes an explicit P x N 0/1 matrix, as ``GraphPercStep(ξ, ξv)`` does."""
+    K = 0
+
+    def __init__(self, N, P, seed=DEFAULT_SEED):
+        N, P = int(N), int(P)
+        if N % 2 == 0:
+            raise ValueError("N must be odd, given: %d" % N)                             # PercStep.jl:57
+        if P < 1:
+            raise ValueError("P must be >= 1, given: %d" % P)
+        xi = np.zeros((P, nchunks(N)), np.uint64)
+        check(lib().rrrmc_gen_patterns(N, P, seed, xi.reshape(-1)))
+        self.N, self.P, self.xi = N, P, xi
+
+    @classmethod
+    def from_patterns(cls, xi):
+        """the graph of an explicit pattern matrix: ``xi`` is a P x N array of 0/1 (or booleans)"""
+        xi = np.asarray(xi)
+        if xi.ndim != 2 or xi.shape[0] < 1 or xi.shape[1] < 1:
+            raise ValueError("the patterns must be a P x N matrix, given an array of shape %s" % (xi.shape,))
+        if not np.isin(xi, (0, 1)).all():
+            raise ValueError("the patterns must be 0/1")
+        if xi.shape[1] % 2 == 0:
+            raise ValueError("N must be odd, given: %d" % xi.shape[1])
+        X = cls.__new__(cls)
+        X.N, X.P, X.xi = int(xi.shape[1]), int(xi.shape[0]), pack_patterns(xi)
+        return X
+
+    def patterns(self):
+        """the P x N matrix of 0/1"""
+        return unpack_patterns(self.xi, self.N)
+
+
+def pack_patterns(xi):
+    """P x N 0/1 matrix -> [P, ceil(N/64)] chunks (the layout of ``rrrmc_set_patterns``)"""
+    return Config.from_bits(xi).s
+
+
+def unpack_patterns(chunks, N):
+    """[P, ceil(N/64)] chunks -> P x N matrix of 0/1"""
+    chunks = np.ascontiguousarray(chunks, np.uint64)
+    if chunks.ndim != 2 or chunks.shape[1] != nchunks(N):
+        raise ValueError("expected P rows of %d chunks, given an array of shape %s" % (nchunks(N), chunks.shape))
+    return Config(N, chunks.shape[0], chunks).bits()
+
+
+class GraphPercStep(_GraphPerc):
+    """``GraphPercStep(N, P)`` (src/graphs/PercStep.jl:62-72): the energy is the number of misclassified patterns.  ``ET = Int``."""
+    model_kind = 17         # RRRMC_MODEL_PERC_STEP
+    energy_dtype = np.int64
+    __doc__ += _GraphPerc.__doc__
+
+
+class GraphPercLinear(_GraphPerc):
+    """``GraphPercLinear(N, P)`` (src/graphs/PercLinear.jl:64-75): the energy of a pattern is the least number of synapses to flip to
+    satisfy it, in units of 2 / sqrt(N).  ``ET = Float64``."""
+    model_kind = 18         # RRRMC_MODEL_PERC_LINEAR
+    energy_dtype = np.float64
+    __doc__ += _GraphPerc.__doc__
+
+
+def _ensemble_slice_kind(slice_graph):
+    return (0 if slice_graph is None else 1 if isinstance(slice_graph, GraphSK) else 2 if isinstance(slice_graph, GraphSKNormal)
+            else 3 if isinstance(slice_graph, GraphPercStep) else 4)
+
+
+def _perc_ensemble(ens, G, args, seed):
+    """the reference's two signatures (src/REAliases.jl, src/LEAliases.jl): (N, P, M, γ, β) draws the patterns, (X, M, γ, β) takes X's"""
+    if isinstance(args[0], _GraphPerc):
+        if len(args) != 4:
+            raise TypeError("expected (X, M, γ, β)")
+        X, M, gamma, beta = args
+        if not isinstance(X, G):
+            raise TypeError("expected a %s, given a %s" % (G.__name__, type(X).__name__))
+    else:
+        if len(args) != 5:
+            raise TypeError("expected (N, P, M, γ, β) or (X, M, γ, β)")
+        N, P, M, gamma, beta = args
+        X = G(N, P, seed=seed)
+    return ens(X.N, M, gamma, beta, X)
+
+
+def GraphPercStepRE(*args, seed=DEFAULT_SEED):
+    """``GraphPercStepRE(N, P, M, γ, β)`` / ``GraphPercStepRE(X::GraphPercStep, M, γ, β)`` (src/REAliases.jl): a Robust Ensemble of M
+    perceptrons that share one pattern matrix."""
+    return _perc_ensemble(GraphRobustEnsemble, GraphPercStep, args, seed)
+
+
+def GraphPercLinearRE(*args, seed=DEFAULT_SEED):
+    """``GraphPercLinearRE(N, P, M, γ, β)`` / ``GraphPercLinearRE(X::GraphPercLinear, M, γ, β)`` (src/REAliases.jl)."""
+    return _perc_ensemble(GraphRobustEnsemble, GraphPercLinear, args, seed)
+
+
+def GraphPercStepLE(*args, seed=DEFAULT_SEED):
+    """``GraphPercStepLE(N, P, M, γ, β)`` / ``GraphPercStepLE(X::GraphPercStep, M, γ, β)`` (src/LEAliases.jl): a Local Entropy ensemble of M
+    perceptrons and a centre that share one pattern matrix."""
+    return _perc_ensemble(GraphLocalEntropy, GraphPercStep, args, seed)
+
+
+def GraphPercLinearLE(*args, seed=DEFAULT_SEED):
+    """``GraphPercLinearLE(N, P, M, γ, β)`` / ``GraphPercLinearLE(X::GraphPercLinear, M, γ, β)`` (src/LEAliases.jl)."""
+    return _perc_ensemble(GraphLocalEntropy, GraphPercLinear, args, seed)
+
+
 class GraphRobustEnsemble:
     """``GraphRobustEnsemble(Nk, M, γ, β, slice_graph)`` — the Robust Ensemble (src/graphs/RE.jl:215-263): M replicas of one graph (the
     slices, which share one coupling set as ``Gconstr(args...)`` with the same ``args`` gives them) coupled by ``GraphRE{M,γ,β}`` through
@@ -500,16 +607,16 @@ class GraphRobustEnsemble:
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
             raise ValueError("M must be greater than 2, given: %d" % M)                  # RE.jl:37
-        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal)):
-            raise TypeError("the slices of a GraphRobustEnsemble are GraphEmpty (None), GraphSK or GraphSKNormal")
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc)):
+            raise TypeError("the slices of a GraphRobustEnsemble are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep or GraphPercLinear")
         if slice_graph is not None and slice_graph.N != int(Nk):
             raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
         self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
         self.N = self.Nk * self.M
         self.X1 = slice_graph
-        self.slice_kind = 0 if slice_graph is None else 1 if isinstance(slice_graph, GraphSK) else 2
-        self.model_kind = 11 + self.slice_kind          # RRRMC_MODEL_RE_EMPTY / _SK / _SKN
-        self.J = None if slice_graph is None else slice_graph.J
+        self.slice_kind = _ensemble_slice_kind(slice_graph)
+        self.model_kind = (11, 12, 13, 19, 20)[self.slice_kind]          # RRRMC_MODEL_RE_EMPTY / _SK / _SKN / _PERC_STEP / _PERC_LINEAR
+        self.J = getattr(slice_graph, "J", None)
         self._engine = None                             # the Engine running this graph: REenergies reads the live configuration there
 
     def tables(self):
@@ -560,17 +667,17 @@ class GraphLocalEntropy:
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
             raise ValueError("M must be greater than 2, given: %d" % M)                  # LE.jl:24
-        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal)):
-            raise TypeError("the slices of a GraphLocalEntropy are GraphEmpty (None), GraphSK or GraphSKNormal")
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc)):
+            raise TypeError("the slices of a GraphLocalEntropy are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep or GraphPercLinear")
         if slice_graph is not None and slice_graph.N != int(Nk):
             raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
         self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
         self.gammaT = self.gamma / self.beta                                              # LE.jl:221-225
         self.N = self.Nk * (self.M + 1)
         self.X1 = slice_graph
-        self.slice_kind = 0 if slice_graph is None else 1 if isinstance(slice_graph, GraphSK) else 2
-        self.model_kind = 14 + self.slice_kind          # RRRMC_MODEL_LE_EMPTY / _SK / _SKN
-        self.J = None if slice_graph is None else slice_graph.J
+        self.slice_kind = _ensemble_slice_kind(slice_graph)
+        self.model_kind = (14, 15, 16, 21, 22)[self.slice_kind]          # RRRMC_MODEL_LE_EMPTY / _SK / _SKN / _PERC_STEP / _PERC_LINEAR
+        self.J = getattr(slice_graph, "J", None)
         self._engine = None                             # the Engine running this graph: the observables read the live configuration there
 
     def tables(self):

@@ -3,6 +3,7 @@
   python tools/bench_models.py sk      GraphSKNormal N=1024, 2048 replicas (BASELINE.json configs[2])
   python tools/bench_models.py re [R ...]   GraphSKRE(1024, 5), γ = 2, β = 0.4: rrrMC (both builds) and standardMC
   python tools/bench_models.py le [R ...]   GraphSKLE(1024, 5), γ = 2, β = 0.4: rrrMC (both builds) and standardMC
+  python tools/bench_models.py perc [R ...] GraphPercStepRE / GraphPercStepLE(1001, 400, 5) and GraphPercStep(1001, 400): the same three legs
 """
 import json
 import os
@@ -251,6 +252,46 @@ def bench_le(Nk=1024, M=5, gamma=2.0, beta=0.4, iters=1 << 14, step=1 << 12, see
         print(json.dumps(out), flush=True)
 
 
+def bench_perc(Nk=1001, P=400, M=5, gamma=2.0, beta=0.4, iters=1 << 14, step=1 << 12, seed=0x5EED, reps=3):
+    """GraphPercStepRE(1001, 400, 5), GraphPercStepLE(1001, 400, 5) (γ = 2, β = 0.4: bench_re's point over perceptron slices) and the
+    stand-alone GraphPercStep(1001, 400): rrrMC through the thread and the LDS build and standardMC, kernel iterations/s per replica count
+    (python tools/bench_models.py perc 128 1024 4096).  Every figure: one warm-up call, then `reps` timed calls, each continuing from the
+    configuration the last one left; the median and the (min, max) of the kernel rate."""
+    pkg = entry.load_package()
+    X1 = pkg.GraphPercStep(Nk, P, seed=seed)
+    envs = ("RRRMC_RE_NO_LDS", "RRRMC_RE_LDS", "RRRMC_LE_NO_LDS", "RRRMC_LE_LDS")
+    for R in ([int(a) for a in sys.argv[2:]] or [128, 1024, 4096]):
+        it = max(step, iters * 1024 // max(R, 1024))
+        for model, X, pre in (("GraphPercStepRE", pkg.GraphPercStepRE(X1, M, gamma, beta), "RRRMC_RE"),
+                              ("GraphPercStepLE", pkg.GraphPercStepLE(X1, M, gamma, beta), "RRRMC_LE"), ("GraphPercStep", X1, None)):
+            out = {"model": model, "Nk": Nk, "P": P, "M": M if pre else 1, "gamma": gamma, "beta": beta, "replicas": R, "iters": it}
+            legs = (("rrr_thread", {pre + "_NO_LDS": "1"}), ("rrr_lds", {pre + "_LDS": "1"}), ("standard", {})) if pre else (("standard", {}),)
+            for name, env in legs:
+                for k in envs:
+                    os.environ.pop(k, None)
+                os.environ.update(env)
+                eng = pkg.Engine(X, R)
+                eng.seed(seed)
+                eng.init_spins_random()
+                rates = []
+                for rep in range(reps + 1):                       # the first call is the warm-up
+                    if name == "standard":
+                        Es, acc = eng.standard_mc(beta, it, step)
+                        staged = np.zeros(R)
+                    else:
+                        Es, acc, staged = eng.rrr_mc(beta, it, step)
+                    _, sweep_ms, _ = eng.last_timing()
+                    if rep:
+                        rates.append(float(R) * it / (sweep_ms * 1e-3))
+                out[name] = {"kernel_iterations_per_s": float(np.median(rates)), "min": min(rates), "max": max(rates),
+                             "acceptance": float(acc.mean()) / it, "staged_frac": float(staged.mean()) / it,
+                             "energy_per_spin": float(Es[:, -1].mean()) / X.N}
+                eng.close()
+            for k in envs:
+                os.environ.pop(k, None)
+            print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "sk"
-    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le}[which]()
+    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc}[which]()
