@@ -79,7 +79,17 @@ enum rrrmc_model {
     RRRMC_MODEL_RE_PERC_STEP = 19,   /* GraphPercStepRE */
     RRRMC_MODEL_RE_PERC_LINEAR = 20, /* GraphPercLinearRE */
     RRRMC_MODEL_LE_PERC_STEP = 21,   /* GraphPercStepLE */
-    RRRMC_MODEL_LE_PERC_LINEAR = 22  /* GraphPercLinearLE */
+    RRRMC_MODEL_LE_PERC_LINEAR = 22, /* GraphPercLinearLE */
+    /* the two-layer binary committee machines (src/graphs/CommStep.jl, CommReLU.jl): made by rrrmc_ctx_create_comm; selectors of
+       rrrmc_ctx_create_multi with N = K1*K2 and K = K2 (M ignored) */
+    RRRMC_MODEL_COMM_STEP = 23,    /* GraphCommStep(K1, K2, P): energy = the number of misclassified patterns (reported as Float64) */
+    RRRMC_MODEL_COMM_RELU = 24,    /* GraphCommReLU(K1, K2, P) */
+    /* the two ensembles over committee machine slices that share one pattern matrix: made by rrrmc_ctx_create_re / _le with
+       RRRMC_RE_SLICE_COMM_STEP / _COMM_RELU; selectors of rrrmc_ctx_create_multi (N = Nk, M; K ignored: rrrmc_set_comm_patterns fixes K2) */
+    RRRMC_MODEL_RE_COMM_STEP = 25,   /* GraphCommStepRE */
+    RRRMC_MODEL_RE_COMM_RELU = 26,   /* GraphCommReLURE */
+    RRRMC_MODEL_LE_COMM_STEP = 27,   /* GraphCommStepLE */
+    RRRMC_MODEL_LE_COMM_RELU = 28    /* GraphCommReLULE */
 };
 
 /* slice families of rrrmc_ctx_create_re */
@@ -88,7 +98,9 @@ enum rrrmc_re_slice {
     RRRMC_RE_SLICE_SK = 1,       /* binary GraphSK (src/graphs/SK.jl:28-60): couplings with rrrmc_set_couplings_bits */
     RRRMC_RE_SLICE_SKN = 2,      /* GraphSKNormal (src/graphs/SK.jl:181-210): couplings with rrrmc_set_couplings_dense */
     RRRMC_RE_SLICE_PERC_STEP = 3,   /* GraphPercStep (src/graphs/PercStep.jl): patterns with rrrmc_set_patterns; Nk odd */
-    RRRMC_RE_SLICE_PERC_LINEAR = 4  /* GraphPercLinear (src/graphs/PercLinear.jl): patterns with rrrmc_set_patterns; Nk odd */
+    RRRMC_RE_SLICE_PERC_LINEAR = 4, /* GraphPercLinear (src/graphs/PercLinear.jl): patterns with rrrmc_set_patterns; Nk odd */
+    RRRMC_RE_SLICE_COMM_STEP = 5,   /* GraphCommStep (src/graphs/CommStep.jl): patterns with rrrmc_set_comm_patterns; Nk = K1*K2, K1, K2 odd */
+    RRRMC_RE_SLICE_COMM_RELU = 6    /* GraphCommReLU (src/graphs/CommReLU.jl): patterns and labels with rrrmc_set_comm_patterns; K1, K2 even */
 };
 
 /* Library ABI version (major*10000 + minor*100 + patch). */
@@ -132,7 +144,8 @@ RRRMC_API int32_t rrrmc_ctx_create(rrrmc_ctx **out, int32_t model, int64_t N, in
  *   model  any rrrmc_model; RRRMC_MODEL_QUANT_RRG takes (N = Nk, K, M) as rrrmc_ctx_create_quant does, RRRMC_MODEL_QUANT_SK / _SKN take
  *          (N = Nk, M) as rrrmc_ctx_create_quant_sk / _skn do (K ignored), RRRMC_MODEL_QUANT_F64 takes (N = Nk, K, M) as rrrmc_ctx_create_quant_f64,
  *          RRRMC_MODEL_RE_EMPTY / _SK / _SKN take (N = Nk, M) as rrrmc_ctx_create_re does (K ignored), RRRMC_MODEL_LE_EMPTY / _SK / _SKN
- *          take (N = Nk, M) as rrrmc_ctx_create_le does (K ignored), and so do RRRMC_MODEL_RE_PERC_* / RRRMC_MODEL_LE_PERC_*;
+ *          take (N = Nk, M) as rrrmc_ctx_create_le does (K ignored), and so do RRRMC_MODEL_RE_PERC_* / RRRMC_MODEL_LE_PERC_* and
+ *          RRRMC_MODEL_RE_COMM_* / RRRMC_MODEL_LE_COMM_*; RRRMC_MODEL_COMM_STEP / _RELU take (N = K1*K2, K = K2) as rrrmc_ctx_create_comm does;
  *          RRRMC_MODEL_PERC_STEP / _LINEAR take N as rrrmc_ctx_create_perc does; M is ignored otherwise.
  */
 RRRMC_API int32_t rrrmc_ctx_create_multi(rrrmc_ctx **out, int32_t model, int64_t N, int64_t K, int64_t M, int64_t R,
@@ -296,6 +309,25 @@ RRRMC_API int32_t rrrmc_set_patterns(rrrmc_ctx *ctx, const uint64_t *xi, int64_t
 /* gen_xi (PercStep.jl:19-29; the reference's bitrand is unpinned): xi_out[P * ceil(N / 64)] in the layout of rrrmc_set_patterns, drawn on
  * the host from the SKBITS stream of `seed` (third counter word 1).  Needs no device. */
 RRRMC_API int32_t rrrmc_gen_patterns(int64_t N, int64_t P, uint64_t seed, uint64_t *xi_out);
+
+/* ---- The binary committee machines (src/graphs/CommStep.jl, CommReLU.jl; RRRMC_MODEL_COMM_*, RRRMC_RE_SLICE_COMM_*) ------
+ * rrrmc_ctx_create_comm: R chains of GraphCommStep (relu = 0; K1 and K2 odd) or GraphCommReLU (relu != 0; K1 and K2 even) with K2 hidden
+ * units of K1 synapses each, N = K1*K2 (unit k owns synapses k*K1 .. (k+1)*K1 - 1).  A wrong parity is RRRMC_ERR_INVALID_ARG (the
+ * reference's ArgumentError), N > 32767 RRRMC_ERR_UNSUPPORTED (16-bit stabilities).  Spins: one bit per synapse in 64-bit chunks.  Then
+ * rrrmc_set_comm_patterns.  Sampler: rrrmc_standard_mc_async with rrrmc_fetch_results_f64 (integer energies as exact Float64s),
+ * rrrmc_set_resume, rrrmc_set_debug_checks, rrrmc_energy_f64.  rrrMC / bklMC / wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED.
+ *
+ * rrrmc_set_comm_patterns: the P patterns xi[P * ceil(N / 64)] in rrrmc_set_patterns' layout (bits beyond N must be 0), and for
+ * GraphCommReLU the labels y[ceil(P / 64)] (bit a = y_a; bits beyond P must be 0); y must be NULL for GraphCommStep.  1 <= P <= 4096
+ * (RRRMC_ERR_UNSUPPORTED beyond).  N % K2 != 0, a wrong parity of K1 = N / K2 or K2, a missing or extra y: RRRMC_ERR_INVALID_ARG.  For a
+ * context made by rrrmc_ctx_create_comm (K2 must be the context's), or by rrrmc_ctx_create_re / _le with a committee slice kind (N = Nk:
+ * this call fixes K2; all slices, and the centre of a GraphLocalEntropy, share the one matrix).  May be called again: it ends a resumed run. */
+RRRMC_API int32_t rrrmc_ctx_create_comm(rrrmc_ctx **out, int64_t K1, int64_t K2, int32_t relu, int64_t R, int32_t device, uint32_t replica0);
+RRRMC_API int32_t rrrmc_set_comm_patterns(rrrmc_ctx *ctx, int64_t K2, const uint64_t *xi, const uint64_t *y, int64_t P);
+/* gen_xi (CommStep.jl:16-26, CommReLU.jl:16-27, fc: CommStep.jl:85-93), drawn on the host: xi_out[P * ceil(K1*K2 / 64)] as
+ * rrrmc_gen_patterns(fc ? K1 : K1*K2, P, seed) draws its rows, with fc's K1 columns repeated K2 times; y_out[ceil(P / 64)] (may be NULL)
+ * from the SKBITS stream of `seed` with third counter word 2.  Needs no device. */
+RRRMC_API int32_t rrrmc_gen_comm_patterns(int64_t K1, int64_t K2, int64_t P, int32_t fc, uint64_t seed, uint64_t *xi_out, uint64_t *y_out);
 
 /* ---- GraphLocalEntropy (src/graphs/LE.jl; RRRMC_MODEL_LE_*) -------------------------------------------------------
  * The Local Entropy ensemble: M replicas of one graph, each coupled to an explicit reference ("centre") configuration by the inner graph

@@ -57,18 +57,33 @@ const QUANT_SK, QUANT_SKN, QUANT_F64 = 8, 9, 10      # selectors of rrrmc_ctx_cr
 const RE_EMPTY, RE_SK, RE_SKN = 11, 12, 13            # GraphRobustEnsemble over GraphEmpty / GraphSK / GraphSKNormal (rrrmc_ctx_create_re; multi selectors)
 const LE_EMPTY, LE_SK, LE_SKN = 14, 15, 16            # GraphLocalEntropy over GraphEmpty / GraphSK / GraphSKNormal (rrrmc_ctx_create_le; multi selectors)
 const PERC_STEP, PERC_LINEAR = 17, 18                 # GraphPercStep, GraphPercLinear (rrrmc_ctx_create_perc; multi selectors)
-const RE_MODELS = (RE_EMPTY, RE_SK, RE_SKN, 19, 20)   # by slice kind 0..4 (3, 4: GraphPercStep, GraphPercLinear slices)
-const LE_MODELS = (LE_EMPTY, LE_SK, LE_SKN, 21, 22)
+const COMM_STEP, COMM_RELU = 23, 24                   # GraphCommStep, GraphCommReLU (rrrmc_ctx_create_comm; multi selectors, N = K1 K2, K = K2)
+const RE_MODELS = (RE_EMPTY, RE_SK, RE_SKN, 19, 20, 25, 26)   # by slice kind 0..6 (3, 4: GraphPercStep, GraphPercLinear; 5, 6: GraphCommStep, GraphCommReLU)
+const LE_MODELS = (LE_EMPTY, LE_SK, LE_SKN, 21, 22, 27, 28)
+const CommGraph = Union{RRRMC.CommStep.GraphCommStep,RRRMC.CommReLU.GraphCommReLU}
 const PercGraph = Union{RRRMC.PercStep.GraphPercStep,RRRMC.PercLinear.GraphPercLinear}
 # slice kind of an ensemble's graph type (rrrmc_re_slice)
 ens_kind(G, what) = G <: RRRMC.SK.GraphSK ? 1 : G <: RRRMC.SK.GraphSKNormal ? 2 : G <: RRRMC.Empty.GraphEmpty ? 0 :
                     G <: RRRMC.PercStep.GraphPercStep ? 3 : G <: RRRMC.PercLinear.GraphPercLinear ? 4 :
-                    throw(ArgumentError("the engine runs the $what over GraphEmpty, GraphSK, GraphSKNormal, GraphPercStep and GraphPercLinear slices, given: $G"))
+                    G <: RRRMC.CommStep.GraphCommStep ? 5 : G <: RRRMC.CommReLU.GraphCommReLU ? 6 :
+                    throw(ArgumentError("the engine runs the $what over GraphEmpty, GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, GraphCommStep and GraphCommReLU slices, given: $G"))
 # the patterns of a perceptron as P rows of chunks (ξv, PercStep.jl:19-29): rrrmc_set_patterns
 function set_patterns!(ctx, X1::PercGraph)
     nch = (X1.N + 63) >> 6
     xi = Matrix{UInt64}(undef, nch, X1.P); for a = 1:X1.P; xi[:, a] = X1.ξv[a].chunks; end
     GC.@preserve xi check(ccall((:rrrmc_set_patterns, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt64}, Int64), ctx.p, xi, X1.P), ctx.p)
+    return ctx
+end
+# the patterns of a committee machine as P rows of chunks, and GraphCommReLU's labels as P bits: rrrmc_set_comm_patterns (fixes K2)
+function set_patterns!(ctx, X1::CommGraph)
+    nch = (X1.N + 63) >> 6
+    xi = Matrix{UInt64}(undef, nch, X1.P); for a = 1:X1.P; xi[:, a] = X1.ξv[a].chunks; end
+    if X1 isa RRRMC.CommReLU.GraphCommReLU
+        y = copy(X1.y.chunks)
+        GC.@preserve xi y check(ccall((:rrrmc_set_comm_patterns, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{UInt64}, Ptr{UInt64}, Int64), ctx.p, X1.K2, xi, y, X1.P), ctx.p)
+    else
+        GC.@preserve xi check(ccall((:rrrmc_set_comm_patterns, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{UInt64}, Ptr{UInt64}, Int64), ctx.p, X1.K2, xi, C_NULL, X1.P), ctx.p)
+    end
     return ctx
 end
 
@@ -248,6 +263,19 @@ function Ctx(X::PercGraph, R::Integer; device = 0, replica0 = 0, devices = nothi
         check(ccall((:rrrmc_ctx_create_perc, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int32, Int64, Int32, UInt32), ref, X.N, lin ? 1 : 0, R, device, replica0))
     else
         ref[] = create(lin ? PERC_LINEAR : PERC_STEP, X.N, 0, 0, R; replica0 = replica0, devices = devices)
+    end
+    return set_patterns!(Ctx(ref[], R, X.N, true), X)
+end
+
+# ---- GraphCommStep / GraphCommReLU (src/graphs/CommStep.jl, CommReLU.jl), stand-alone: standardMC only -------------------------------
+# (rrrMC / bklMC / wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED).  The integer energies arrive as exact Float64s.
+function Ctx(X::CommGraph, R::Integer; device = 0, replica0 = 0, devices = nothing)
+    relu = X isa RRRMC.CommReLU.GraphCommReLU
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    if devices === nothing
+        check(ccall((:rrrmc_ctx_create_comm, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, Int64, Int32, UInt32), ref, X.K1, X.K2, relu ? 1 : 0, R, device, replica0))
+    else
+        ref[] = create(relu ? COMM_RELU : COMM_STEP, X.N, X.K2, 0, R; replica0 = replica0, devices = devices)
     end
     return set_patterns!(Ctx(ref[], R, X.N, true), X)
 end

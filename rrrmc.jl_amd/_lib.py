@@ -14,6 +14,14 @@ i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 i8p = np.ctypeslib.ndpointer(np.int8, flags="C_CONTIGUOUS")
 f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 
+
+class _U64OrNull:
+    """a uint64 array argument that may be None (a NULL pointer)"""
+    @classmethod
+    def from_param(cls, obj):
+        return None if obj is None else u64p.from_param(obj)
+
+
 # every symbol include/rrrmc_hip.h declares
 SYMBOLS = [
     "rrrmc_version", "rrrmc_last_error", "rrrmc_device_count", "rrrmc_device_copy_bandwidth", "rrrmc_host_alloc", "rrrmc_host_free", "rrrmc_ctx_create", "rrrmc_ctx_create_multi", "rrrmc_ctx_destroy",
@@ -29,6 +37,7 @@ SYMBOLS = [
     "rrrmc_ctx_create_re", "rrrmc_re_set_params", "rrrmc_re_energies", "rrrmc_re_tables",
     "rrrmc_ctx_create_le", "rrrmc_le_set_params", "rrrmc_le_energies", "rrrmc_le_cenergy", "rrrmc_le_distances", "rrrmc_le_tables",
     "rrrmc_ctx_create_perc", "rrrmc_set_patterns", "rrrmc_gen_patterns",
+    "rrrmc_ctx_create_comm", "rrrmc_set_comm_patterns", "rrrmc_gen_comm_patterns",
 ]
 
 
@@ -223,6 +232,12 @@ def lib():
     L.rrrmc_set_patterns.argtypes = [vp, u64p, C.c_int64]
     L.rrrmc_gen_patterns.restype = C.c_int32
     L.rrrmc_gen_patterns.argtypes = [C.c_int64, C.c_int64, C.c_uint64, u64p]
+    L.rrrmc_ctx_create_comm.restype = C.c_int32
+    L.rrrmc_ctx_create_comm.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_uint32]
+    L.rrrmc_set_comm_patterns.restype = C.c_int32
+    L.rrrmc_set_comm_patterns.argtypes = [vp, C.c_int64, u64p, _U64OrNull, C.c_int64]
+    L.rrrmc_gen_comm_patterns.restype = C.c_int32
+    L.rrrmc_gen_comm_patterns.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, u64p, _U64OrNull]
     L.rrrmc_le_distances.restype = C.c_int32
     L.rrrmc_le_distances.argtypes = [vp, i64p]
     L.rrrmc_le_tables.restype = C.c_int32

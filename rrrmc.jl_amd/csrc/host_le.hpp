@@ -2,9 +2,11 @@
 // Included by rrrmc_hip.hip inside its anonymous namespace, after host_re.hpp; not a stand-alone translation unit.  The context reuses the
 // Robust Ensemble's buffers (re_sp, re_mu, re_tab, re_Eslice and the q_* DeltaECache arrays) with M + 1 rows.
 inline bool is_le(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_LE_EMPTY || ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_LE_SKN ||
-                                                ctx->model == RRRMC_MODEL_LE_PERC_STEP || ctx->model == RRRMC_MODEL_LE_PERC_LINEAR; }
+                                                ctx->model == RRRMC_MODEL_LE_PERC_STEP || ctx->model == RRRMC_MODEL_LE_PERC_LINEAR ||
+                                                ctx->model == RRRMC_MODEL_LE_COMM_STEP || ctx->model == RRRMC_MODEL_LE_COMM_RELU; }
 inline int le_slice_of(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_LE_SK ? RE_SK : ctx->model == RRRMC_MODEL_LE_SKN ? RE_SKN :
-                                                      ctx->model == RRRMC_MODEL_LE_PERC_STEP ? RE_PSTEP : ctx->model == RRRMC_MODEL_LE_PERC_LINEAR ? RE_PLIN : RE_EMPTY; }
+                                                      ctx->model == RRRMC_MODEL_LE_PERC_STEP ? RE_PSTEP : ctx->model == RRRMC_MODEL_LE_PERC_LINEAR ? RE_PLIN :
+                                                      ctx->model == RRRMC_MODEL_LE_COMM_STEP ? RE_CSTEP : ctx->model == RRRMC_MODEL_LE_COMM_RELU ? RE_CRELU : RE_EMPTY; }
 inline int le_levels(int64_t M) { return (int)(M % 2 == 0 ? M / 2 + 2 : (M + 1) / 2); }        // length of allΔE(GraphLE) (LE.jl:176-179)
 
 // allΔE(GraphLE{M,γT}) (LE.jl:176-179): M even (0, 2|γT|, 4|γT|, 8|γT|, ..., 2M|γT|), M odd (2|γT|, 6|γT|, ..., 2M|γT|); Julia's integer
@@ -64,6 +66,7 @@ LeParams le_params(rrrmc_ctx* ctx, double beta)
     if (ctx->model == RRRMC_MODEL_LE_SK) { P.Jb = ctx->q_Jb; P.Wk = (int)ctx->q_Wk; P.sN = std::sqrt((double)ctx->qNk); }
     if (ctx->model == RRRMC_MODEL_LE_SKN) { P.Jd = ctx->sk_J; P.slf = ctx->q_slf; P.smv = ctx->q_smv; P.scur = ctx->q_scur; }
     if (le_slice_of(ctx) == RE_PSTEP || le_slice_of(ctx) == RE_PLIN) P.pc = perc_params(ctx, M + 1);
+    if (le_slice_of(ctx) == RE_CSTEP || le_slice_of(ctx) == RE_CRELU) P.cm = comm_params(ctx, M + 1);
     P.tab = ctx->re_tab; P.etab = nullptr; P.ft = ctx->re_tab + L; P.ctab = reinterpret_cast<const uint8_t*>(ctx->re_tab + 2 * L);
     P.abi = ctx->q_spins; P.sp = ctx->re_sp; P.mu = ctx->re_mu; P.cls = ctx->q_cls; P.sv = ctx->q_sv; P.spos = ctx->q_spos; P.st = ctx->q_st;
     P.T = ctx->q_T; P.zz = ctx->q_z; P.E_cur = ctx->sk_E; P.acc_rate = ctx->q_accrate; P.stats = ctx->q_stats; P.Es = ctx->sk_Es;
@@ -90,6 +93,8 @@ int32_t le_run_init(rrrmc_ctx* ctx, double beta, bool cache)
         case RE_SKN: hipLaunchKernelGGL(le_init_kernel<RE_SKN>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_PSTEP: hipLaunchKernelGGL(le_init_kernel<RE_PSTEP>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_PLIN: hipLaunchKernelGGL(le_init_kernel<RE_PLIN>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
+        case RE_CSTEP: hipLaunchKernelGGL(le_init_kernel<RE_CSTEP>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
+        case RE_CRELU: hipLaunchKernelGGL(le_init_kernel<RE_CRELU>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         default: hipLaunchKernelGGL(le_init_kernel<RE_EMPTY>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -111,6 +116,8 @@ le_kernel_fn le_rrr_fn(int slice, bool lds, int L)
         case RE_SKN: return lds ? le_rrr_for_L<true, RE_SKN>(L) : le_rrr_for_L<false, RE_SKN>(L);
         case RE_PSTEP: return lds ? le_rrr_for_L<true, RE_PSTEP>(L) : le_rrr_for_L<false, RE_PSTEP>(L);
         case RE_PLIN: return lds ? le_rrr_for_L<true, RE_PLIN>(L) : le_rrr_for_L<false, RE_PLIN>(L);
+        case RE_CSTEP: return lds ? le_rrr_for_L<true, RE_CSTEP>(L) : le_rrr_for_L<false, RE_CSTEP>(L);
+        case RE_CRELU: return lds ? le_rrr_for_L<true, RE_CRELU>(L) : le_rrr_for_L<false, RE_CRELU>(L);
         default: return lds ? le_rrr_for_L<true, RE_EMPTY>(L) : le_rrr_for_L<false, RE_EMPTY>(L);
     }
 }
@@ -127,6 +134,8 @@ int32_t le_debug_check(rrrmc_ctx* ctx, const LeParams& P0, bool cache)
         case RE_SKN: hipLaunchKernelGGL(le_check_kernel<RE_SKN>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_PSTEP: hipLaunchKernelGGL(le_check_kernel<RE_PSTEP>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_PLIN: hipLaunchKernelGGL(le_check_kernel<RE_PLIN>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
+        case RE_CSTEP: hipLaunchKernelGGL(le_check_kernel<RE_CSTEP>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
+        case RE_CRELU: hipLaunchKernelGGL(le_check_kernel<RE_CRELU>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         default: hipLaunchKernelGGL(le_check_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -181,17 +190,20 @@ int32_t le_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, i
             case RE_SKN: hipLaunchKernelGGL(le_standard_kernel<RE_SKN>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             case RE_PSTEP: hipLaunchKernelGGL(le_standard_kernel<RE_PSTEP>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             case RE_PLIN: hipLaunchKernelGGL(le_standard_kernel<RE_PLIN>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
+            case RE_CSTEP: hipLaunchKernelGGL(le_standard_kernel<RE_CSTEP>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
+            case RE_CRELU: hipLaunchKernelGGL(le_standard_kernel<RE_CRELU>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             default: hipLaunchKernelGGL(le_standard_kernel<RE_EMPTY>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
         }
     } else {
         // the build choice of re_mc_async (one replica per workgroup in LDS up to 2048 replicas, one thread per replica beyond);
         // RRRMC_LE_NO_LDS=1 forces the thread build, RRRMC_LE_LDS=1 the LDS build (timing experiments, the builds' parity test)
         size_t lds = le_rrr_lds_bytes(ctx->N, ctx->qW, ctx->qNk);
-        if (P.pc.ds) lds = ((lds + 7) & ~(size_t)7) + perc_lds_bytes(P.pc.rows, P.pc.PW);          // the rows' Stabilities
+        if (P.pc.ds) lds = ((lds + 7) & ~(size_t)7) + perc_lds_bytes(P.pc.rows, P.pc.PW);
+        if (P.cm.ds) lds = ((lds + 7) & ~(size_t)7) + comm_lds_bytes(P.cm.rows, P.cm.K2, P.cm.PW);          // the rows' Stabilities
         const char* no_lds = std::getenv("RRRMC_LE_NO_LDS");
         const char* want_lds = std::getenv("RRRMC_LE_LDS");
         // (perceptron slices: the LDS build at every replica count, as in re_mc_async)
-        const bool use_lds = lds <= (size_t)kLdsLimit && !(no_lds && no_lds[0] == '1') && (ctx->R <= 2048 || P.pc.ds || (want_lds && want_lds[0] == '1'));
+        const bool use_lds = lds <= (size_t)kLdsLimit && !(no_lds && no_lds[0] == '1') && (ctx->R <= 2048 || P.pc.ds || P.cm.ds || (want_lds && want_lds[0] == '1'));
         const le_kernel_fn fn = le_rrr_fn(slice, use_lds, P.L);
         if (use_lds) {
             HIP_TRY(ctx, raise_lds_attr(reinterpret_cast<const void*>(fn), lds));
@@ -232,6 +244,8 @@ int32_t le_observables(rrrmc_ctx* ctx)
         case RE_SKN: hipLaunchKernelGGL(le_obs_kernel<RE_SKN>, grid, blk, 0, ctx->stream, P); break;
         case RE_PSTEP: hipLaunchKernelGGL(le_obs_kernel<RE_PSTEP>, grid, blk, 0, ctx->stream, P); break;
         case RE_PLIN: hipLaunchKernelGGL(le_obs_kernel<RE_PLIN>, grid, blk, 0, ctx->stream, P); break;
+        case RE_CSTEP: hipLaunchKernelGGL(le_obs_kernel<RE_CSTEP>, grid, blk, 0, ctx->stream, P); break;
+        case RE_CRELU: hipLaunchKernelGGL(le_obs_kernel<RE_CRELU>, grid, blk, 0, ctx->stream, P); break;
         default: hipLaunchKernelGGL(le_obs_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P); break;
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -243,10 +257,12 @@ int32_t le_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind
     if (!out) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     const bool perc = slice_kind == RRRMC_RE_SLICE_PERC_STEP || slice_kind == RRRMC_RE_SLICE_PERC_LINEAR;
-    if (slice_kind != RRRMC_RE_SLICE_EMPTY && slice_kind != RRRMC_RE_SLICE_SK && slice_kind != RRRMC_RE_SLICE_SKN && !perc)
-        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind must be RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP or _PERC_LINEAR, given: %d", slice_kind);
+    const bool comm = slice_kind == RRRMC_RE_SLICE_COMM_STEP || slice_kind == RRRMC_RE_SLICE_COMM_RELU;
+    if (slice_kind != RRRMC_RE_SLICE_EMPTY && slice_kind != RRRMC_RE_SLICE_SK && slice_kind != RRRMC_RE_SLICE_SKN && !perc && !comm)
+        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind must be RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP, _PERC_LINEAR, _COMM_STEP or _COMM_RELU, given: %d", slice_kind);
     if (Nk < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "Nk and R must be >= 1");
     if (perc) { const int32_t rcn = perc_check_n(Nk); if (rcn) return rcn; }
+    if (comm) { const int32_t rcn = comm_check_nk(Nk, slice_kind == RRRMC_RE_SLICE_COMM_RELU); if (rcn) return rcn; }
     if (M <= 2) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "M must be greater than 2, given: %lld", (long long)M);      // LE.jl:24
     if (M > kLeMmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "M = %lld: the Local Entropy kernels cover M <= %d", (long long)M, kLeMmax);
     if (Nk * (M + 1) > 65535)
@@ -259,7 +275,8 @@ int32_t le_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind
     rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
     if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
     ctx->model = slice_kind == RRRMC_RE_SLICE_SK ? RRRMC_MODEL_LE_SK : slice_kind == RRRMC_RE_SLICE_SKN ? RRRMC_MODEL_LE_SKN :
-                 slice_kind == RRRMC_RE_SLICE_PERC_STEP ? RRRMC_MODEL_LE_PERC_STEP : slice_kind == RRRMC_RE_SLICE_PERC_LINEAR ? RRRMC_MODEL_LE_PERC_LINEAR : RRRMC_MODEL_LE_EMPTY;
+                 slice_kind == RRRMC_RE_SLICE_PERC_STEP ? RRRMC_MODEL_LE_PERC_STEP : slice_kind == RRRMC_RE_SLICE_PERC_LINEAR ? RRRMC_MODEL_LE_PERC_LINEAR :
+                 slice_kind == RRRMC_RE_SLICE_COMM_STEP ? RRRMC_MODEL_LE_COMM_STEP : slice_kind == RRRMC_RE_SLICE_COMM_RELU ? RRRMC_MODEL_LE_COMM_RELU : RRRMC_MODEL_LE_EMPTY;
     const int64_t rows = M + 1, N = Nk * rows, L = le_levels(M);
     ctx->N = N; ctx->K = 0; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = Nk; ctx->qM = M; ctx->qW = 2 * ((N + 63) / 64); ctx->q_Wk = 2 * ((Nk + 63) / 64);

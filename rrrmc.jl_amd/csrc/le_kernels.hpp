@@ -103,6 +103,8 @@ __global__ __launch_bounds__(kReInitThreads) void le_init_kernel(LeParams P, int
         for (int x = Nk + tid; x < N; x += kReInitThreads) v.slf[(size_t)rows * Nk + x] = 0.0;
     } else if constexpr (kPercSlice<SLICE>) {
         perc_init_rows<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, Nk, N, s_n);          // (row 0, the centre: built, never used)
+    } else if constexpr (kCommSlice<SLICE>) {
+        comm_init_rows<SLICE == RE_CRELU>(P.cm, comm_view(P.cm, r), sp, Nk, N, s_n);          // (likewise)
     }
     __syncthreads();
     if (cache) {
@@ -139,6 +141,7 @@ __global__ __launch_bounds__(kReInitThreads) void le_init_kernel(LeParams P, int
             if constexpr (SLICE == RE_SK) { long long n = s_n[k]; n /= 2; E += (double)n / P.sN; }
             else if constexpr (SLICE == RE_SKN) E += s_E[k];
             else if constexpr (kPercSlice<SLICE>) E += perc_energy_of<SLICE == RE_PLIN>(s_n[k], P.pc.sN);
+            else if constexpr (kCommSlice<SLICE>) E += (double)s_n[k];
             else E += 0.0;
         }
         P.E_cur[r] = E;
@@ -168,7 +171,7 @@ __host__ __device__ inline size_t le_rrr_lds_bytes(int64_t N, int64_t W, int64_t
 // rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290) on the Local Entropy ensemble; the builds and the register layout of the class weights are
 // re_rrr_kernel's (LM >= L classes per half in registers, LDS = one wavefront per replica with its hot state in LDS).  Neighbours in the
 // order of apply_move! / compute_staged! (LE.jl:166-174): a centre move's M replicas ascending, a replica move's centre; then the move.
-// Perceptron slices in the LDS build: as in re_rrr_kernel, the Stabilities are staged in LDS and all 64 lanes run the chain.
+// Perceptron and committee machine slices in the LDS build: as in re_rrr_kernel, their state is staged in LDS and all 64 lanes run the chain.
 template <bool LDS, int LM, int SLICE>
 __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
 {
@@ -205,8 +208,8 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
         sp = l_sp; spos = l_spos; cls = l_cls; mu = l_mu; t = l_t;
     }
     const RrrView v = re_view(P, sp, r);
-    const PercView g_pv = perc_view(P.pc, r);
-    PercView pv = g_pv;
+    const auto g_pv = re_slice_view<SLICE>(P, r);                                  // PercView, or CommView for committee slices
+    auto pv = g_pv;
     if constexpr (LDS && kPercSlice<SLICE>) {
         const int nw = rows * P.pc.PW;                                             // mask words, then 64 stabilities per word
         pv.pm = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(le_lds) + ((le_rrr_lds_bytes(N, P.W, Nk) + 7) & ~(size_t)7));
@@ -216,7 +219,15 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
         for (int i = (int)threadIdx.x; i < 64 * nw; i += (int)blockDim.x) pv.ds[i] = g_pv.ds[i];
         __syncthreads();
     }
-    const bool worker = !LDS || threadIdx.x == 0 || kPercSlice<SLICE>;
+    if constexpr (LDS && kCommSlice<SLICE>) {
+        const int nm = rows * (int)comm_mk_row(P.cm.K2, P.cm.PW), nd = rows * (int)comm_ds_row(P.cm.K2, P.cm.PW);  // mask words, stabilities
+        pv.mk = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(le_lds) + ((le_rrr_lds_bytes(N, P.W, Nk) + 7) & ~(size_t)7));
+        pv.ds = reinterpret_cast<int16_t*>(pv.mk + nm);
+        for (int i = (int)threadIdx.x; i < nm; i += (int)blockDim.x) pv.mk[i] = g_pv.mk[i];
+        for (int i = (int)threadIdx.x; i < nd; i += (int)blockDim.x) pv.ds[i] = g_pv.ds[i];
+        __syncthreads();
+    }
+    const bool worker = !LDS || threadIdx.x == 0 || kWaveSlice<SLICE>;
     const uint32_t rep = P.replica0 + (uint32_t)r;
     const double* tab = P.tab;
     const double* ft = P.ft;
@@ -375,7 +386,7 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
                 if (km != 0) {
                     mu[i] = (int8_t)(mu[i] + 2 * (2 * sbit(sp, xm) - 1));
                     // the undo pass takes the slice's swap path (move_last == move); perceptron slices: once, below, when accepted
-                    if constexpr (!kPercSlice<SLICE>) re_slice_update<SLICE>(v, xm);
+                    if constexpr (!kWaveSlice<SLICE>) re_slice_update<SLICE>(v, xm);
                 }
                 double zp = z;
                 auto apply = [&](int y, int k0, int k1) {
@@ -392,7 +403,7 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
                 if (pass == 1) break;                                      // that was the undo
                 if (accept_c(cc, -P.beta * dE1, q2, g)) { E += dE0 + dE1; accepted += 1; acc = true; break; }
             }
-            if constexpr (kPercSlice<SLICE>) { if (acc && km != 0) re_slice_update<SLICE, LDS>(v, pv, xm, km, i); }
+            if constexpr (kWaveSlice<SLICE>) { if (acc && km != 0) re_slice_update<SLICE, LDS>(v, pv, xm, km, i); }
         }
         acc_rate = acc_rate * (1 - P.lambda) + (acc ? 1.0 : 0.0) * P.lambda;          // RRRMC.jl:281
     }
@@ -412,6 +423,12 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
         const int nw = rows * P.pc.PW;
         for (int i = (int)threadIdx.x; i < nw; i += (int)blockDim.x) { g_pv.pm[i] = pv.pm[i]; g_pv.mm[i] = pv.mm[i]; }
         for (int i = (int)threadIdx.x; i < 64 * nw; i += (int)blockDim.x) g_pv.ds[i] = pv.ds[i];
+    }
+    if constexpr (LDS && kCommSlice<SLICE>) {
+        __syncthreads();
+        const int nm = rows * (int)comm_mk_row(P.cm.K2, P.cm.PW), nd = rows * (int)comm_ds_row(P.cm.K2, P.cm.PW);
+        for (int i = (int)threadIdx.x; i < nm; i += (int)blockDim.x) g_pv.mk[i] = pv.mk[i];
+        for (int i = (int)threadIdx.x; i < nd; i += (int)blockDim.x) g_pv.ds[i] = pv.ds[i];
     }
     if constexpr (LDS) {
         __syncthreads();
@@ -434,7 +451,7 @@ __global__ __launch_bounds__(kRrrThreads) void le_standard_kernel(LeParams P)
     uint32_t* sp = P.sp + (size_t)r * P.W;
     int8_t* mu = P.mu + (size_t)r * Nk;
     const RrrView v = re_view(P, sp, r);
-    const PercView pv = perc_view(P.pc, r);
+    const auto pv = re_slice_view<SLICE>(P, r);
     const uint32_t rep = P.replica0 + (uint32_t)r;
     double E = P.E_cur[r];
     int64_t accepted = 0, ns = 0;
@@ -527,6 +544,7 @@ __global__ __launch_bounds__(64) void le_check_kernel(LeParams P, int cache)
             }
     }
     if constexpr (kPercSlice<SLICE>) bad = bad || perc_state_bad<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, 1, Nk, N);
+    if constexpr (kCommSlice<SLICE>) bad = bad || comm_state_bad<SLICE == RE_CRELU>(P.cm, comm_view(P.cm, r), sp, 1, Nk, N);
     if (cache) {
         int cnt[2 * kLeLmax];
         for (int k = 0; k < 2 * L; ++k) cnt[k] = 0;

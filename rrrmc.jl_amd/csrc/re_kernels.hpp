@@ -17,12 +17,17 @@
 
 #include "rrr_kernels.hpp"   // RrrView, sbit / sflip, slice_delta, skn_update, kRrrThreads, TAG_RRR, det_exp
 #include "perc_kernels.hpp"  // the binary perceptron slices (PercParams, perc_residual, perc_update, perc_init_rows)
+#include "comm_kernels.hpp"  // the binary committee machine slices (CommParams, comm_residual, comm_update, comm_init_rows)
 
 namespace rrrmc {
 
 enum ReSlice { RE_EMPTY = 0, RE_SK = 1, RE_SKN = 2,          // GraphEmpty (Graph0RE), binary GraphSK (GraphSKRE), GraphSKNormal
-               RE_PSTEP = 3, RE_PLIN = 4 };                  // GraphPercStep (GraphPercStepRE), GraphPercLinear (GraphPercLinearRE)
+               RE_PSTEP = 3, RE_PLIN = 4,                    // GraphPercStep (GraphPercStepRE), GraphPercLinear (GraphPercLinearRE)
+               RE_CSTEP = 5, RE_CRELU = 6 };                 // GraphCommStep (GraphCommStepRE), GraphCommReLU (GraphCommReLURE)
 template <int SLICE> constexpr bool kPercSlice = SLICE == RE_PSTEP || SLICE == RE_PLIN;
+template <int SLICE> constexpr bool kCommSlice = SLICE == RE_CSTEP || SLICE == RE_CRELU;
+// slices whose state is a pure function of the configuration, updated once per accepted move by the whole wavefront in the LDS builds
+template <int SLICE> constexpr bool kWaveSlice = kPercSlice<SLICE> || kCommSlice<SLICE>;
 constexpr int kReMmax = 32;                                 // replicas of the ensemble; levels L = ceil(M / 2) <= 16
 
 struct ReParams {
@@ -30,6 +35,7 @@ struct ReParams {
     const uint32_t* Jb; int Wk; double sN;                  // binary GraphSK: rows of J as 32-bit words, sqrt(Nk)
     const double* Jd;                                       // GraphSKNormal: [Nk][Nk]
     PercParams pc;                                          // perceptron slices: the shared patterns, every slice's Stabilities
+    CommParams cm;                                          // committee machine slices: the same for GraphCommStep / GraphCommReLU
     double* slf;                                            // [R][2][M][Nk]  every slice's lfields / lfields_last (SK.jl:212-276)
     int32_t* smv;                                           // [R][M]         move_last of every slice (-1 = none)
     uint8_t* scur;                                          // [R][M]         which of the two arrays is `lfields`
@@ -101,6 +107,26 @@ __device__ __forceinline__ void re_slice_update(const RrrView& v, const PercView
     if constexpr (kPercSlice<SLICE>) perc_update<SLICE == RE_PLIN, WAVE>(pv, k, i, sbit(v.sp, x));
     else re_slice_update<SLICE>(v, x);
 }
+// ... and with the committee machine slices (comm_kernels.hpp)
+template <int SLICE>
+__device__ __forceinline__ double re_residual(const RrrView& v, const CommView& cv, int x, int k, int i)
+{
+    static_assert(kCommSlice<SLICE>, "a CommView goes with a committee machine slice");
+    return comm_residual<SLICE == RE_CRELU>(cv, k, i, sbit(v.sp, x));
+}
+template <int SLICE, bool WAVE>
+__device__ __forceinline__ void re_slice_update(const RrrView& v, const CommView& cv, int x, int k, int i)
+{
+    static_assert(kCommSlice<SLICE>, "a CommView goes with a committee machine slice");
+    comm_update<SLICE == RE_CRELU, WAVE>(cv, k, i, sbit(v.sp, x));
+}
+// the view of one chain's slice state that the kernels pass to the two above
+template <int SLICE, class PP>
+__device__ __forceinline__ auto re_slice_view(const PP& P, int r)
+{
+    if constexpr (kCommSlice<SLICE>) return comm_view(P.cm, r);
+    else return perc_view(P.pc, r);
+}
 // class of ABI site j with spin bit s, for the group's μ = mub + σ: a + L up (DeltaE.jl:80-86 with lfields[j] = σ_j fk(mū), RE.jl:101)
 __device__ __forceinline__ int re_class(const double* tab, int M, int L, int mub, int s)
 {
@@ -135,6 +161,8 @@ __device__ inline double re_slice_energy(const ReParams& P, const RrrView& v, in
         return n;
     } else if constexpr (kPercSlice<SLICE>) {
         return perc_row_energy<SLICE == RE_PLIN>(P.pc, v.sp, k * Nk, Nk, P.N);
+    } else if constexpr (kCommSlice<SLICE>) {
+        return comm_row_energy<SLICE == RE_CRELU>(P.cm, v.sp, k * Nk, P.N);
     } else {
         return 0.0;
     }
@@ -219,6 +247,8 @@ __global__ __launch_bounds__(kReInitThreads) void re_init_kernel(ReParams P, int
         for (int x = tid; x < N; x += kReInitThreads) v.slf[(size_t)M * Nk + x] = 0.0;
     } else if constexpr (kPercSlice<SLICE>) {
         perc_init_rows<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, Nk, N, s_n);
+    } else if constexpr (kCommSlice<SLICE>) {
+        comm_init_rows<SLICE == RE_CRELU>(P.cm, comm_view(P.cm, r), sp, Nk, N, s_n);
     }
     __syncthreads();
     if (cache) {
@@ -256,6 +286,7 @@ __global__ __launch_bounds__(kReInitThreads) void re_init_kernel(ReParams P, int
             if constexpr (SLICE == RE_SK) { long long n = s_n[k]; n /= 2; E += (double)n / P.sN; }
             else if constexpr (SLICE == RE_SKN) E += s_E[k];
             else if constexpr (kPercSlice<SLICE>) E += perc_energy_of<SLICE == RE_PLIN>(s_n[k], P.pc.sN);
+            else if constexpr (kCommSlice<SLICE>) E += (double)s_n[k];
             else E += 0.0;
         }
         P.E_cur[r] = E;
@@ -290,6 +321,7 @@ __host__ __device__ inline size_t re_rrr_lds_bytes(int64_t N, int64_t W, int64_t
 //   The member arrays (2 L N entries) stay in HBM/L2.  Same arithmetic, same order: the results are the thread build's.
 //   Perceptron slices: the Stabilities of the M slices are staged in LDS too, and ALL 64 lanes run the chain with identical values, so
 //   that the O(P) update_cache! of an accepted move is one pattern per lane (perc_update<.., true>); stores name one address wave-wide.
+//   Committee machine slices (comm_kernels.hpp) the same way: their Δ1 / Δ2 and masks in LDS, comm_update<.., true>.
 template <bool LDS, int LM, int SLICE>
 __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
 {
@@ -326,8 +358,8 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
         sp = l_sp; spos = l_spos; cls = l_cls; mu = l_mu; t = l_t;
     }
     const RrrView v = re_view(P, sp, r);
-    const PercView g_pv = perc_view(P.pc, r);
-    PercView pv = g_pv;
+    const auto g_pv = re_slice_view<SLICE>(P, r);                                  // PercView, or CommView for committee slices
+    auto pv = g_pv;
     if constexpr (LDS && kPercSlice<SLICE>) {
         const int nw = M * P.pc.PW;                                                // mask words, then 64 stabilities per word
         pv.pm = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(re_lds) + ((re_rrr_lds_bytes(N, P.W, Nk) + 7) & ~(size_t)7));
@@ -337,7 +369,15 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
         for (int i = (int)threadIdx.x; i < 64 * nw; i += (int)blockDim.x) pv.ds[i] = g_pv.ds[i];
         __syncthreads();
     }
-    const bool worker = !LDS || threadIdx.x == 0 || kPercSlice<SLICE>;
+    if constexpr (LDS && kCommSlice<SLICE>) {
+        const int nm = M * (int)comm_mk_row(P.cm.K2, P.cm.PW), nd = M * (int)comm_ds_row(P.cm.K2, P.cm.PW);     // mask words, stabilities
+        pv.mk = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(re_lds) + ((re_rrr_lds_bytes(N, P.W, Nk) + 7) & ~(size_t)7));
+        pv.ds = reinterpret_cast<int16_t*>(pv.mk + nm);
+        for (int i = (int)threadIdx.x; i < nm; i += (int)blockDim.x) pv.mk[i] = g_pv.mk[i];
+        for (int i = (int)threadIdx.x; i < nd; i += (int)blockDim.x) pv.ds[i] = g_pv.ds[i];
+        __syncthreads();
+    }
+    const bool worker = !LDS || threadIdx.x == 0 || kWaveSlice<SLICE>;
     const uint32_t rep = P.replica0 + (uint32_t)r;
     const double* tab = P.tab;
     const double* ft = P.ft;
@@ -496,7 +536,7 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
                 mu[i] = (int8_t)munew;
                 // the undo pass takes the slice's swap path (move_last == move); a perceptron slice's Stabilities are a function of the
                 // configuration, which a rejected move leaves as it was: they are updated once, below, for an accepted move
-                if constexpr (!kPercSlice<SLICE>) re_slice_update<SLICE>(v, xm);
+                if constexpr (!kWaveSlice<SLICE>) re_slice_update<SLICE>(v, xm);
                 double zp = z;
                 for (int y = jg; y < jg + M; ++y) {
                     if (y == move) continue;
@@ -522,7 +562,7 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
                 if (pass == 1) break;                                      // that was the undo
                 if (accept_c(cc, -P.beta * dE1, q2, g)) { E += dE0 + dE1; accepted += 1; acc = true; break; }
             }
-            if constexpr (kPercSlice<SLICE>) { if (acc) re_slice_update<SLICE, LDS>(v, pv, xm, km, i); }
+            if constexpr (kWaveSlice<SLICE>) { if (acc) re_slice_update<SLICE, LDS>(v, pv, xm, km, i); }
         }
         acc_rate = acc_rate * (1 - P.lambda) + (acc ? 1.0 : 0.0) * P.lambda;          // RRRMC.jl:281
     }
@@ -542,6 +582,12 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
         const int nw = M * P.pc.PW;
         for (int i = (int)threadIdx.x; i < nw; i += (int)blockDim.x) { g_pv.pm[i] = pv.pm[i]; g_pv.mm[i] = pv.mm[i]; }
         for (int i = (int)threadIdx.x; i < 64 * nw; i += (int)blockDim.x) g_pv.ds[i] = pv.ds[i];
+    }
+    if constexpr (LDS && kCommSlice<SLICE>) {
+        __syncthreads();
+        const int nm = M * (int)comm_mk_row(P.cm.K2, P.cm.PW), nd = M * (int)comm_ds_row(P.cm.K2, P.cm.PW);
+        for (int i = (int)threadIdx.x; i < nm; i += (int)blockDim.x) g_pv.mk[i] = pv.mk[i];
+        for (int i = (int)threadIdx.x; i < nd; i += (int)blockDim.x) g_pv.ds[i] = pv.ds[i];
     }
     if constexpr (LDS) {
         __syncthreads();
@@ -564,7 +610,7 @@ __global__ __launch_bounds__(kRrrThreads) void re_standard_kernel(ReParams P)
     uint32_t* sp = P.sp + (size_t)r * P.W;
     int8_t* mu = P.mu + (size_t)r * Nk;
     const RrrView v = re_view(P, sp, r);
-    const PercView pv = perc_view(P.pc, r);
+    const auto pv = re_slice_view<SLICE>(P, r);
     const uint32_t rep = P.replica0 + (uint32_t)r;
     double E = P.E_cur[r];
     int64_t accepted = 0, ns = 0;
@@ -637,6 +683,7 @@ __global__ __launch_bounds__(64) void re_check_kernel(ReParams P, int cache)
             }
     }
     if constexpr (kPercSlice<SLICE>) bad = bad || perc_state_bad<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, 0, Nk, N);
+    if constexpr (kCommSlice<SLICE>) bad = bad || comm_state_bad<SLICE == RE_CRELU>(P.cm, comm_view(P.cm, r), sp, 0, Nk, N);
     if (cache) {
         int cnt[2 * (kReMmax / 2)];
         for (int k = 0; k < 2 * L; ++k) cnt[k] = 0;

@@ -35,6 +35,7 @@
 #include "cont_kernels.hpp"
 #include "cont_wave_kernel.hpp"
 #include "perc_kernels.hpp"
+#include "comm_kernels.hpp"
 #include "re_kernels.hpp"
 #include "le_kernels.hpp"
 
@@ -283,6 +284,14 @@ struct rrrmc_ctx {
     uint64_t* pc_pm = nullptr;     // [R][rows][PW] the set p
     uint64_t* pc_mm = nullptr;     // [R][rows][PW] the set m
     int64_t pc_P = 0;
+    // ---- the binary committee machines (RRRMC_MODEL_COMM_*, and the slices of RRRMC_MODEL_RE_COMM_* / _LE_COMM_*; host_comm.hpp): spins
+    //      in q_spins, E in sk_E, counts in q_stats ----
+    uint64_t* cm_col = nullptr;    // [Nk][PW] patterns, one column per synapse
+    uint32_t* cm_row = nullptr;    // [P][2 ceil(Nk/64)] patterns, one row per pattern (the ABI's chunks)
+    uint64_t* cm_lab = nullptr;    // [2][PW] the labels y and ~y (GraphCommReLU)
+    int16_t* cm_ds = nullptr;      // [R][rows][K2 + 1][64 PW] Δ1 of every unit, Δ2
+    uint64_t* cm_mk = nullptr;     // [R][rows][2 K2 + 2][PW] the sets p1, m1 of every unit, p2, m2
+    int64_t cm_P = 0, cm_K2 = 0;
 
     // ---- fast standardMC on RRRMC_MODEL_SPARSE_F64 (spf_fast_kernels.hpp; allocated on first use) ----
     std::vector<double> h_Jf;           // host copy of the couplings (threshold tables per beta)
@@ -444,7 +453,7 @@ hipError_t raise_lds_attr(const void* fn, size_t bytes)
 inline bool chunk_layout(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_QUANT_RRG || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_SPARSE_LEVELS ||
                                                        ctx->model == RRRMC_MODEL_RE_EMPTY || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_RE_SKN ||
                                                        ctx->model == RRRMC_MODEL_LE_EMPTY || ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_LE_SKN ||
-                                                       (ctx->model >= RRRMC_MODEL_PERC_STEP && ctx->model <= RRRMC_MODEL_LE_PERC_LINEAR); }
+                                                       (ctx->model >= RRRMC_MODEL_PERC_STEP && ctx->model <= RRRMC_MODEL_LE_COMM_RELU); }
 inline bool sparse_int_model(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_SPARSE_PM1 || ctx->model == RRRMC_MODEL_SPARSE_LEVELS; }
 inline double lv_to_f64(const rrrmc_ctx* ctx, long long units) { return (double)(units * ctx->lv_mul) / ctx->lv_div; }
 
@@ -586,6 +595,7 @@ inline void smp_commit(rrrmc_ctx* ctx, int kind, int64_t n) { ctx->smp_kind = ki
 #include "host_sweep.hpp"
 #include "host_spf_fast.hpp"
 #include "host_perc.hpp"
+#include "host_comm.hpp"
 #include "host_re.hpp"
 #include "host_le.hpp"
 int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact);
@@ -900,6 +910,7 @@ void rrrmc_ctx_destroy(rrrmc_ctx* ctx)
     free_dev(ctx->snap); free_dev(ctx->d_pairs); free_dev(ctx->d_ovl); free_dev(ctx->d_qobs);
     free_dev(ctx->re_sp); free_dev(ctx->re_mu); free_dev(ctx->re_tab); free_dev(ctx->re_Eslice); free_dev(ctx->le_dist);
     free_dev(ctx->pc_col); free_dev(ctx->pc_row); free_dev(ctx->pc_ds); free_dev(ctx->pc_pm); free_dev(ctx->pc_mm);
+    free_dev(ctx->cm_col); free_dev(ctx->cm_row); free_dev(ctx->cm_lab); free_dev(ctx->cm_ds); free_dev(ctx->cm_mk);
     for (int i = 0; i < 2; ++i) { free_dev(ctx->d_slots[i]); free_dev(ctx->d_vecs[i]); free_dev(ctx->d_nbrs[i]); free_dev(ctx->d_masks[i]); }
     free_dev(ctx->d_bigimg);
     free_dev(ctx->dbg_flag); free_dev(ctx->dbg_Ei); free_dev(ctx->dbg_lf); free_dev(ctx->dbg_lfl); free_dev(ctx->dbg_E); free_dev(ctx->dbg_ml);
@@ -1218,6 +1229,7 @@ int32_t rrrmc_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int6
     if (ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED) return dbl_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (ctx->model == RRRMC_MODEL_SPARSE_LEVELS) return lev_standard_mc_async(ctx, beta, iters, step, false);
     if (is_perc(ctx)) return perc_mc_async(ctx, beta, iters, step);
+    if (is_comm(ctx)) return comm_mc_async(ctx, beta, iters, step);
     if (is_re(ctx)) return re_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (is_le(ctx)) return le_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (ctx->model == RRRMC_MODEL_QUANT_RRG) {
@@ -1252,8 +1264,8 @@ int32_t rrrmc_set_debug_checks(rrrmc_ctx* ctx, int32_t on)
 {
     RRRMC_MULTI(ctx, false, rrrmc_set_debug_checks(c, on));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_perc(ctx))
-        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy and the perceptron graphs");
+    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_perc(ctx) && !is_comm(ctx))
+        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy, the perceptron and the committee machine graphs");
     ctx->debug_checks = on != 0;
     return RRRMC_OK;
 }
@@ -1637,6 +1649,8 @@ int32_t rrrmc_re_energies(rrrmc_ctx* ctx, double* out)
         case RE_SKN: hipLaunchKernelGGL(re_energies_kernel<RE_SKN>, grid, blk, 0, ctx->stream, P); break;
         case RE_PSTEP: hipLaunchKernelGGL(re_energies_kernel<RE_PSTEP>, grid, blk, 0, ctx->stream, P); break;
         case RE_PLIN: hipLaunchKernelGGL(re_energies_kernel<RE_PLIN>, grid, blk, 0, ctx->stream, P); break;
+        case RE_CSTEP: hipLaunchKernelGGL(re_energies_kernel<RE_CSTEP>, grid, blk, 0, ctx->stream, P); break;
+        case RE_CRELU: hipLaunchKernelGGL(re_energies_kernel<RE_CRELU>, grid, blk, 0, ctx->stream, P); break;
         default: hipLaunchKernelGGL(re_energies_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P); break;
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -1659,6 +1673,22 @@ int32_t rrrmc_set_patterns(rrrmc_ctx* ctx, const uint64_t* xi, int64_t P)
     if (!is_perc(ctx) && !perc_slices(ctx))
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_patterns is for contexts made by rrrmc_ctx_create_perc, or by rrrmc_ctx_create_re / _le with a perceptron slice kind");
     return perc_set_patterns(ctx, xi, P, is_perc(ctx) ? 1 : is_le(ctx) ? ctx->qM + 1 : ctx->qM);
+}
+
+// ---- the binary committee machines: exported entry points (host_comm.hpp) ----
+int32_t rrrmc_ctx_create_comm(rrrmc_ctx** out, int64_t K1, int64_t K2, int32_t relu, int64_t R, int32_t device, uint32_t replica0)
+{
+    return comm_ctx_create(out, K1, K2, relu, R, device, replica0);
+}
+
+int32_t rrrmc_set_comm_patterns(rrrmc_ctx* ctx, int64_t K2, const uint64_t* xi, const uint64_t* y, int64_t P)
+{
+    RRRMC_MULTI(ctx, false, rrrmc_set_comm_patterns(c, K2, xi, y, P));
+    smp_drop(ctx);
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!is_comm(ctx) && !comm_slices(ctx))
+        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_comm_patterns is for contexts made by rrrmc_ctx_create_comm, or by rrrmc_ctx_create_re / _le with a committee machine slice kind");
+    return comm_set_patterns(ctx, K2, xi, y, P, is_comm(ctx) ? 1 : is_le(ctx) ? ctx->qM + 1 : ctx->qM);
 }
 
 // ---- GraphLocalEntropy: exported entry points (host_le.hpp) ----------------------------------------------------------------------
@@ -1765,18 +1795,28 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
     if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
     const bool quant = model == RRRMC_MODEL_QUANT_RRG || model == RRRMC_MODEL_QUANT_SK || model == RRRMC_MODEL_QUANT_SKN || model == RRRMC_MODEL_QUANT_F64;
-    const bool re = model == RRRMC_MODEL_RE_EMPTY || model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_RE_SKN || model == RRRMC_MODEL_RE_PERC_STEP || model == RRRMC_MODEL_RE_PERC_LINEAR;
-    const bool le = model == RRRMC_MODEL_LE_EMPTY || model == RRRMC_MODEL_LE_SK || model == RRRMC_MODEL_LE_SKN || model == RRRMC_MODEL_LE_PERC_STEP || model == RRRMC_MODEL_LE_PERC_LINEAR;
+    const bool re = model == RRRMC_MODEL_RE_EMPTY || model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_RE_SKN || model == RRRMC_MODEL_RE_PERC_STEP || model == RRRMC_MODEL_RE_PERC_LINEAR ||
+                    model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_RE_COMM_RELU;
+    const bool le = model == RRRMC_MODEL_LE_EMPTY || model == RRRMC_MODEL_LE_SK || model == RRRMC_MODEL_LE_SKN || model == RRRMC_MODEL_LE_PERC_STEP || model == RRRMC_MODEL_LE_PERC_LINEAR ||
+                    model == RRRMC_MODEL_LE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_RELU;
     const bool pc = model == RRRMC_MODEL_PERC_STEP || model == RRRMC_MODEL_PERC_LINEAR;
+    const bool cm = model == RRRMC_MODEL_COMM_STEP || model == RRRMC_MODEL_COMM_RELU;
+    if (cm && (K < 1 || N % K != 0)) {
+        delete ctx;
+        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "a committee machine takes N = K1*K2 and K = K2 with N %% K2 == 0, given N = %lld, K = %lld", (long long)N, (long long)K);
+    }
     const int32_t ens_slice = model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_LE_SK ? RRRMC_RE_SLICE_SK
                               : model == RRRMC_MODEL_RE_SKN || model == RRRMC_MODEL_LE_SKN ? RRRMC_RE_SLICE_SKN
                               : model == RRRMC_MODEL_RE_PERC_STEP || model == RRRMC_MODEL_LE_PERC_STEP ? RRRMC_RE_SLICE_PERC_STEP
                               : model == RRRMC_MODEL_RE_PERC_LINEAR || model == RRRMC_MODEL_LE_PERC_LINEAR ? RRRMC_RE_SLICE_PERC_LINEAR
+                              : model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_STEP ? RRRMC_RE_SLICE_COMM_STEP
+                              : model == RRRMC_MODEL_RE_COMM_RELU || model == RRRMC_MODEL_LE_COMM_RELU ? RRRMC_RE_SLICE_COMM_RELU
                                                                                                        : RRRMC_RE_SLICE_EMPTY;
     ctx->model = quant ? RRRMC_MODEL_QUANT_RRG : model; ctx->K = K; ctx->R = R; ctx->replica0 = replica0; ctx->device = device_ids[0];
     ctx->N = quant || re ? N * M : le ? N * (M + 1) : N;
     if (re || le) { ctx->qNk = N; ctx->qM = M; }
     if (pc) { ctx->qNk = N; ctx->qM = 1; }
+    if (cm) { ctx->qNk = N; ctx->qM = 1; ctx->cm_K2 = K; ctx->K = 0; }
     if (quant) { ctx->qNk = N; ctx->qM = M; ctx->q_sk = model == RRRMC_MODEL_QUANT_SK; ctx->q_skn = model == RRRMC_MODEL_QUANT_SKN; ctx->q_spf = model == RRRMC_MODEL_QUANT_F64; }
     for (int32_t d = 0; d < ndev; ++d) {
         int64_t b0 = 0, b1 = 0;
@@ -1790,6 +1830,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : re ? rrrmc_ctx_create_re(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : le ? rrrmc_ctx_create_le(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : pc ? rrrmc_ctx_create_perc(&c, N, model == RRRMC_MODEL_PERC_LINEAR, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : cm ? rrrmc_ctx_create_comm(&c, N / K, K, model == RRRMC_MODEL_COMM_RELU, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                                                             : rrrmc_ctx_create(&c, model, N, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0);
         if (rc) {
             for (rrrmc_ctx* k : ctx->kids) rrrmc_ctx_destroy(k);
@@ -2003,6 +2044,7 @@ int32_t rrrmc_rrr_mc_async(rrrmc_ctx* ctx, double beta, double fourK, int64_t it
     if (ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED) return dbl_rrr_mc_async(ctx, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model == RRRMC_MODEL_SPARSE_F64) return spf_cont_async(ctx, 0, beta, iters, step, 1.0, staged_thr, staged_thr_fact);
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone perceptron graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
+    if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone committee machine graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
     if (is_re(ctx)) return re_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (is_le(ctx)) return le_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model != RRRMC_MODEL_QUANT_RRG) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not available for model kind %d", ctx->model);
@@ -2016,6 +2058,7 @@ int32_t rrrmc_bkl_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t s
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone perceptron graphs (standardMC is)");
+    if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
     if (!std::isfinite(beta)) return fail(ctx, RRRMC_ERR_INVALID_ARG, "beta must be finite, given: %g", beta);
@@ -2056,6 +2099,7 @@ int32_t rrrmc_wtm_mc_async(rrrmc_ctx* ctx, double beta, int64_t samples, double 
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone perceptron graphs (standardMC is)");
+    if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
@@ -2084,6 +2128,7 @@ int32_t rrrmc_extremal_opt_async(rrrmc_ctx* ctx, const double* ftau, int64_t ite
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone perceptron graphs (standardMC is)");
+    if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)        // not DiscrGraphs: EOCacheCont
@@ -2244,6 +2289,9 @@ int32_t rrrmc_energy_f64(rrrmc_ctx* ctx, double* E_out)
     } else if (is_perc(ctx)) {
         ctx->std_cache_live = false;
         rc = perc_run_init(ctx);
+    } else if (is_comm(ctx)) {
+        ctx->std_cache_live = false;
+        rc = comm_run_init(ctx);
     } else if (is_re(ctx)) {
         if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphRobustEnsemble needs (gamma, beta): call rrrmc_re_set_params first");
         ctx->std_cache_live = false;
@@ -2781,6 +2829,34 @@ int32_t rrrmc_gen_sk_binary(int64_t N, uint64_t seed, uint64_t* Jc)
         for (int64_t j = i + 1; j < N; ++j) {
             const uint64_t b = (Jc[i * nch + (j >> 6)] >> (j & 63)) & 1ull;
             Jc[j * nch + (i >> 6)] = (Jc[j * nch + (i >> 6)] & ~(1ull << (i & 63))) | (b << (i & 63));
+        }
+    }
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_gen_comm_patterns(int64_t K1, int64_t K2, int64_t P, int32_t fc, uint64_t seed, uint64_t* xi, uint64_t* y)
+{
+    // gen_ξ (CommStep.jl:16-26, CommReLU.jl:16-27) and the fc repetition (CommStep.jl:85-93): P rows of Kin = K1 K2 (tree) or K1 (fc) bits,
+    // drawn as rrrmc_gen_patterns(Kin, P, seed) draws them (SKBITS, third counter word 1), the fc columns repeated K2 times; y = bitrand(P):
+    // bit a = bit (a & 31) of word ((a >> 5) & 3) of ctr (a >> 7, 0, 2, TAG_SKBITS).  y may be NULL (GraphCommStep has no labels).
+    if (!xi) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "xi_out is NULL");
+    if (K1 < 1 || K2 < 1 || P < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "K1, K2 and P must be >= 1");
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const int64_t N = K1 * K2, Kin = fc ? K1 : N, nch = (N + 63) / 64;
+    std::memset(xi, 0, sizeof(uint64_t) * P * nch);
+    for (int64_t a = 0; a < P; ++a)
+        for (int64_t ib = 0; ib < Kin; ib += 128) {
+            const Philox4 o = philox4x32_10((uint32_t)(ib >> 7), (uint32_t)a, 1u, TAG_SKBITS, k0, k1);
+            for (int64_t i = ib; i < Kin && i < ib + 128; ++i)
+                if ((o.w[(i >> 5) & 3] >> (i & 31)) & 1u)
+                    for (int64_t x = i; x < N; x += Kin) xi[a * nch + (x >> 6)] |= 1ull << (x & 63);
+        }
+    if (y) {
+        std::memset(y, 0, sizeof(uint64_t) * ((P + 63) / 64));
+        for (int64_t ab = 0; ab < P; ab += 128) {
+            const Philox4 o = philox4x32_10((uint32_t)(ab >> 7), 0u, 2u, TAG_SKBITS, k0, k1);
+            for (int64_t a = ab; a < P && a < ab + 128; ++a)
+                if ((o.w[(a >> 5) & 3] >> (a & 31)) & 1u) y[a >> 6] |= 1ull << (a & 63);
         }
     }
     return RRRMC_OK;

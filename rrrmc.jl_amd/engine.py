@@ -17,9 +17,16 @@ MODEL_SPARSE_LEVELS = 7
 MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN = 11, 12, 13          # GraphRobustEnsemble (rrrmc_ctx_create_re; also the selectors of rrrmc_ctx_create_multi)
 MODEL_PERC = (17, 18)                                            # GraphPercStep, GraphPercLinear (rrrmc_ctx_create_perc)
 MODEL_RE_PERC, MODEL_LE_PERC = (19, 20), (21, 22)                # the ensembles over perceptron slices (rrrmc_set_patterns)
-MODEL_RE = (MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN) + MODEL_RE_PERC
+MODEL_COMM = (23, 24)                                            # GraphCommStep, GraphCommReLU (rrrmc_ctx_create_comm)
+MODEL_RE_COMM, MODEL_LE_COMM = (25, 26), (27, 28)                # the ensembles over committee machine slices (rrrmc_set_comm_patterns)
+MODEL_RE = (MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN) + MODEL_RE_PERC + MODEL_RE_COMM
 MODEL_LE_EMPTY, MODEL_LE_SK, MODEL_LE_SKN = 14, 15, 16          # GraphLocalEntropy (rrrmc_ctx_create_le; also the selectors of rrrmc_ctx_create_multi)
-MODEL_LE = (MODEL_LE_EMPTY, MODEL_LE_SK, MODEL_LE_SKN) + MODEL_LE_PERC
+MODEL_LE = (MODEL_LE_EMPTY, MODEL_LE_SK, MODEL_LE_SKN) + MODEL_LE_PERC + MODEL_LE_COMM
+
+
+def _set_comm_patterns(ctx, X1):
+    """rrrmc_set_comm_patterns with a committee machine's K2, patterns and (GraphCommReLU) labels"""
+    check(lib().rrrmc_set_comm_patterns(ctx, X1.K2, X1.xi.reshape(-1), X1.y, X1.P), ctx)
 
 
 class Engine:
@@ -43,6 +50,8 @@ class Engine:
                                                ids, len(ids), replica0))
         elif X.model_kind in MODEL_PERC:
             check(lib().rrrmc_ctx_create_perc(C.byref(self._ctx), X.N, int(X.model_kind == 18), self.R, device, replica0))
+        elif X.model_kind in MODEL_COMM:
+            check(lib().rrrmc_ctx_create_comm(C.byref(self._ctx), X.K1, X.K2, int(X.model_kind == 24), self.R, device, replica0))
         elif X.model_kind in MODEL_LE:
             check(lib().rrrmc_ctx_create_le(C.byref(self._ctx), X.Nk, X.M, X.slice_kind, self.R, device, replica0))
         elif X.model_kind in MODEL_RE:
@@ -60,8 +69,12 @@ class Engine:
         try:
             if X.model_kind in MODEL_PERC:
                 check(lib().rrrmc_set_patterns(self._ctx, X.xi.reshape(-1), X.P), self._ctx)
+            elif X.model_kind in MODEL_COMM:
+                _set_comm_patterns(self._ctx, X)
             elif X.model_kind in MODEL_LE:
-                if X.model_kind in MODEL_LE_PERC:
+                if X.model_kind in MODEL_LE_COMM:
+                    _set_comm_patterns(self._ctx, X.X1)
+                elif X.model_kind in MODEL_LE_PERC:
                     check(lib().rrrmc_set_patterns(self._ctx, X.X1.xi.reshape(-1), X.X1.P), self._ctx)
                 elif X.model_kind == MODEL_LE_SK:
                     check(lib().rrrmc_set_couplings_bits(self._ctx, X.J.reshape(-1)), self._ctx)
@@ -70,7 +83,9 @@ class Engine:
                 check(lib().rrrmc_le_set_params(self._ctx, X.gamma, X.beta), self._ctx)
                 X._engine = self                # LEenergies / cenergy / distances inside a hook read this engine's live configuration
             elif X.model_kind in MODEL_RE:
-                if X.model_kind in MODEL_RE_PERC:
+                if X.model_kind in MODEL_RE_COMM:
+                    _set_comm_patterns(self._ctx, X.X1)
+                elif X.model_kind in MODEL_RE_PERC:
                     check(lib().rrrmc_set_patterns(self._ctx, X.X1.xi.reshape(-1), X.X1.P), self._ctx)
                 elif X.model_kind == MODEL_RE_SK:
                     check(lib().rrrmc_set_couplings_bits(self._ctx, X.J.reshape(-1)), self._ctx)

@@ -552,9 +552,96 @@ class GraphPercLinear(_GraphPerc):
     __doc__ += _GraphPerc.__doc__
 
 
+class _GraphComm:
+    """A two-layer binary committee machine: ``K2`` hidden units of ``K1`` binary synapses each, N = K1 K2 (unit k owns synapses
+    k K1 .. (k + 1) K1 - 1), trained on ``P`` random ±1 patterns.  ``xi`` holds the patterns as P rows of ceil(N/64) chunks (the layout of
+    ``GraphPercStep``), ``y`` (GraphCommReLU only) the P labels as ceil(P/64) words.  ``fc=True`` draws each pattern over K1 inputs and
+    repeats its columns K2 times (CommStep.jl:85-93).  ``seed`` names the draw (``rrrmc_gen_comm_patterns``, host only);
+    ``from_patterns(K2, ξ[, y])`` takes an explicit P x N 0/1 matrix (and P labels), as ``GraphCommStep(K2, ξ, ξv)`` does."""
+    relu = False
+
+    def __init__(self, K1, K2, P, fc=False, seed=DEFAULT_SEED):
+        K1, K2, P = int(K1), int(K2), int(P)
+        self._check_k(K1, K2)
+        if P < 1:
+            raise ValueError("P must be >= 1, given: %d" % P)
+        xi = np.zeros((P, nchunks(K1 * K2)), np.uint64)
+        y = np.zeros(nchunks(P), np.uint64) if self.relu else None
+        check(lib().rrrmc_gen_comm_patterns(K1, K2, P, int(bool(fc)), seed, xi.reshape(-1), y))
+        self._set(K1, K2, P, xi, y)
+
+    @classmethod
+    def _check_k(cls, K1, K2):
+        par = "even" if cls.relu else "odd"
+        if K1 < 1 or K1 % 2 != (0 if cls.relu else 1):
+            raise ValueError("K1 must be %s, given: %d" % (par, K1))            # CommStep.jl:65-66, CommReLU.jl:68-69
+        if K2 < 1 or K2 % 2 != (0 if cls.relu else 1):
+            raise ValueError("K2 must be %s, given: %d" % (par, K2))
+
+    def _set(self, K1, K2, P, xi, y):
+        self.K1, self.K2, self.N, self.P, self.xi, self.y = K1, K2, K1 * K2, P, xi, y
+        self.K = K2                             # the K of rrrmc_ctx_create_multi
+
+    @classmethod
+    def from_patterns(cls, K2, xi, y=None):
+        """the graph of an explicit pattern matrix: ``xi`` is a P x N array of 0/1 (or booleans), N a multiple of K2; ``y`` the P labels
+        (0/1) of a GraphCommReLU, and nothing for a GraphCommStep"""
+        K2 = int(K2)
+        xi = np.asarray(xi)
+        if xi.ndim != 2 or xi.shape[0] < 1 or xi.shape[1] < 1:
+            raise ValueError("the patterns must be a P x N matrix, given an array of shape %s" % (xi.shape,))
+        if not np.isin(xi, (0, 1)).all():
+            raise ValueError("the patterns must be 0/1")
+        P, N = xi.shape
+        if K2 < 1 or N % K2 != 0:
+            raise ValueError("N = %d is not a multiple of K2 = %d" % (N, K2))              # CommStep.jl:61
+        cls._check_k(N // K2, K2)
+        if cls.relu:
+            if y is None:
+                raise ValueError("a GraphCommReLU needs the labels y")
+            y = np.asarray(y)
+            if y.shape != (P,):
+                raise ValueError("y must hold P = %d labels, given an array of shape %s" % (P, y.shape))      # CommReLU.jl:67
+            if not np.isin(y, (0, 1)).all():
+                raise ValueError("the labels must be 0/1")
+            y = pack_patterns(y.reshape(1, P)).reshape(-1)
+        elif y is not None:
+            raise ValueError("a GraphCommStep has no labels")
+        X = cls.__new__(cls)
+        X._set(N // K2, K2, P, pack_patterns(xi), y)
+        return X
+
+    def patterns(self):
+        """the P x N matrix of 0/1"""
+        return unpack_patterns(self.xi, self.N)
+
+    def labels(self):
+        """the P labels of 0/1 (GraphCommReLU); None for GraphCommStep"""
+        return None if self.y is None else unpack_patterns(self.y.reshape(1, -1), self.P)[0]
+
+
+class GraphCommStep(_GraphComm):
+    """``GraphCommStep(K1, K2, P; fc)`` (src/graphs/CommStep.jl:73-93): hidden units with sign outputs, K1 and K2 odd; the energy is the
+    number of misclassified patterns.  ``ET = Int``."""
+    model_kind = 23         # RRRMC_MODEL_COMM_STEP
+    energy_dtype = np.int64
+    relu = False
+    __doc__ += _GraphComm.__doc__
+
+
+class GraphCommReLU(_GraphComm):
+    """``GraphCommReLU(K1, K2, P; fc)`` (src/graphs/CommReLU.jl:76-97): hidden units with ReLU outputs, the first K2/2 with weight +1 and
+    the rest −1, K1 and K2 even, and a random label per pattern; the energy is the number of misclassified patterns.  ``ET = Int``."""
+    model_kind = 24         # RRRMC_MODEL_COMM_RELU
+    energy_dtype = np.int64
+    relu = True
+    __doc__ += _GraphComm.__doc__
+
+
 def _ensemble_slice_kind(slice_graph):
     return (0 if slice_graph is None else 1 if isinstance(slice_graph, GraphSK) else 2 if isinstance(slice_graph, GraphSKNormal)
-            else 3 if isinstance(slice_graph, GraphPercStep) else 4)
+            else 3 if isinstance(slice_graph, GraphPercStep) else 4 if isinstance(slice_graph, GraphPercLinear)
+            else 5 if isinstance(slice_graph, GraphCommStep) else 6)
 
 
 def _perc_ensemble(ens, G, args, seed):
@@ -571,6 +658,45 @@ def _perc_ensemble(ens, G, args, seed):
         N, P, M, gamma, beta = args
         X = G(N, P, seed=seed)
     return ens(X.N, M, gamma, beta, X)
+
+
+def _comm_ensemble(ens, G, args, fc, seed):
+    """the reference's two signatures (src/REAliases.jl:126-166, src/LEAliases.jl:126-189): (K1, K2, P, M, γ, β; fc) draws the patterns,
+    (X, M, γ, β) takes X's"""
+    if isinstance(args[0], _GraphComm):
+        if len(args) != 4:
+            raise TypeError("expected (X, M, γ, β)")
+        X, M, gamma, beta = args
+        if not isinstance(X, G):
+            raise TypeError("expected a %s, given a %s" % (G.__name__, type(X).__name__))
+    else:
+        if len(args) != 6:
+            raise TypeError("expected (K1, K2, P, M, γ, β) or (X, M, γ, β)")
+        K1, K2, P, M, gamma, beta = args
+        X = G(K1, K2, P, fc=fc, seed=seed)
+    return ens(X.N, M, gamma, beta, X)
+
+
+def GraphCommStepRE(*args, fc=False, seed=DEFAULT_SEED):
+    """``GraphCommStepRE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommStepRE(X::GraphCommStep, M, γ, β)`` (src/REAliases.jl:126-145): a Robust
+    Ensemble of M committee machines that share one pattern matrix."""
+    return _comm_ensemble(GraphRobustEnsemble, GraphCommStep, args, fc, seed)
+
+
+def GraphCommReLURE(*args, fc=False, seed=DEFAULT_SEED):
+    """``GraphCommReLURE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommReLURE(X::GraphCommReLU, M, γ, β)`` (src/REAliases.jl:147-166)."""
+    return _comm_ensemble(GraphRobustEnsemble, GraphCommReLU, args, fc, seed)
+
+
+def GraphCommStepLE(*args, fc=False, seed=DEFAULT_SEED):
+    """``GraphCommStepLE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommStepLE(X::GraphCommStep, M, γ, β)`` (src/LEAliases.jl): a Local Entropy
+    ensemble of M committee machines and a centre that share one pattern matrix."""
+    return _comm_ensemble(GraphLocalEntropy, GraphCommStep, args, fc, seed)
+
+
+def GraphCommReLULE(*args, fc=False, seed=DEFAULT_SEED):
+    """``GraphCommReLULE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommReLULE(X::GraphCommReLU, M, γ, β)`` (src/LEAliases.jl)."""
+    return _comm_ensemble(GraphLocalEntropy, GraphCommReLU, args, fc, seed)
 
 
 def GraphPercStepRE(*args, seed=DEFAULT_SEED):
@@ -607,15 +733,16 @@ class GraphRobustEnsemble:
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
             raise ValueError("M must be greater than 2, given: %d" % M)                  # RE.jl:37
-        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc)):
-            raise TypeError("the slices of a GraphRobustEnsemble are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep or GraphPercLinear")
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm)):
+            raise TypeError("the slices of a GraphRobustEnsemble are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, "
+                            "GraphCommStep or GraphCommReLU")
         if slice_graph is not None and slice_graph.N != int(Nk):
             raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
         self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
         self.N = self.Nk * self.M
         self.X1 = slice_graph
         self.slice_kind = _ensemble_slice_kind(slice_graph)
-        self.model_kind = (11, 12, 13, 19, 20)[self.slice_kind]          # RRRMC_MODEL_RE_EMPTY / _SK / _SKN / _PERC_STEP / _PERC_LINEAR
+        self.model_kind = (11, 12, 13, 19, 20, 25, 26)[self.slice_kind]  # RRRMC_MODEL_RE_EMPTY / _SK / _SKN / _PERC_* / _COMM_*
         self.J = getattr(slice_graph, "J", None)
         self._engine = None                             # the Engine running this graph: REenergies reads the live configuration there
 
@@ -667,8 +794,9 @@ class GraphLocalEntropy:
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
             raise ValueError("M must be greater than 2, given: %d" % M)                  # LE.jl:24
-        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc)):
-            raise TypeError("the slices of a GraphLocalEntropy are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep or GraphPercLinear")
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm)):
+            raise TypeError("the slices of a GraphLocalEntropy are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, "
+                            "GraphCommStep or GraphCommReLU")
         if slice_graph is not None and slice_graph.N != int(Nk):
             raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
         self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
@@ -676,7 +804,7 @@ class GraphLocalEntropy:
         self.N = self.Nk * (self.M + 1)
         self.X1 = slice_graph
         self.slice_kind = _ensemble_slice_kind(slice_graph)
-        self.model_kind = (14, 15, 16, 21, 22)[self.slice_kind]          # RRRMC_MODEL_LE_EMPTY / _SK / _SKN / _PERC_STEP / _PERC_LINEAR
+        self.model_kind = (14, 15, 16, 21, 22, 27, 28)[self.slice_kind]  # RRRMC_MODEL_LE_EMPTY / _SK / _SKN / _PERC_* / _COMM_*
         self.J = getattr(slice_graph, "J", None)
         self._engine = None                             # the Engine running this graph: the observables read the live configuration there
 

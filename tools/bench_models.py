@@ -4,6 +4,8 @@
   python tools/bench_models.py re [R ...]   GraphSKRE(1024, 5), γ = 2, β = 0.4: rrrMC (both builds) and standardMC
   python tools/bench_models.py le [R ...]   GraphSKLE(1024, 5), γ = 2, β = 0.4: rrrMC (both builds) and standardMC
   python tools/bench_models.py perc [R ...] GraphPercStepRE / GraphPercStepLE(1001, 400, 5) and GraphPercStep(1001, 400): the same three legs
+  python tools/bench_models.py comm [R ...] GraphCommStepRE / LE(201, 5, 400, 5), GraphCommReLURE / LE(168, 6, 400, 5) and the two
+                                            stand-alone graphs: the same legs
 """
 import json
 import os
@@ -292,6 +294,51 @@ def bench_perc(Nk=1001, P=400, M=5, gamma=2.0, beta=0.4, iters=1 << 14, step=1 <
             print(json.dumps(out), flush=True)
 
 
+def bench_comm(P=400, M=5, gamma=2.0, beta=0.4, iters=1 << 14, step=1 << 12, seed=0x5EED, reps=3):
+    """GraphCommStepRE / GraphCommStepLE(201, 5, 400, 5), GraphCommReLURE / GraphCommReLULE(168, 6, 400, 5) (γ = 2, β = 0.4: bench_perc's
+    point over committee machine slices) and the stand-alone GraphCommStep(201, 5, 400), GraphCommReLU(168, 6, 400): rrrMC through the
+    thread and the LDS build and standardMC, kernel iterations/s per replica count (python tools/bench_models.py comm 128 1024 4096), measured
+    as bench_perc measures."""
+    pkg = entry.load_package()
+    envs = ("RRRMC_RE_NO_LDS", "RRRMC_RE_LDS", "RRRMC_LE_NO_LDS", "RRRMC_LE_LDS")
+    step_g, relu_g = pkg.GraphCommStep(201, 5, P, seed=seed), pkg.GraphCommReLU(168, 6, P, seed=seed)
+    for R in ([int(a) for a in sys.argv[2:]] or [128, 1024, 4096]):
+        it = max(step, iters * 1024 // max(R, 1024))
+        for model, X, X1, pre in (("GraphCommStepRE", pkg.GraphCommStepRE(step_g, M, gamma, beta), step_g, "RRRMC_RE"),
+                                  ("GraphCommStepLE", pkg.GraphCommStepLE(step_g, M, gamma, beta), step_g, "RRRMC_LE"),
+                                  ("GraphCommStep", step_g, step_g, None),
+                                  ("GraphCommReLURE", pkg.GraphCommReLURE(relu_g, M, gamma, beta), relu_g, "RRRMC_RE"),
+                                  ("GraphCommReLULE", pkg.GraphCommReLULE(relu_g, M, gamma, beta), relu_g, "RRRMC_LE"),
+                                  ("GraphCommReLU", relu_g, relu_g, None)):
+            out = {"model": model, "K1": X1.K1, "K2": X1.K2, "P": P, "M": M if pre else 1, "gamma": gamma, "beta": beta, "replicas": R,
+                   "iters": it}
+            legs = (("rrr_thread", {pre + "_NO_LDS": "1"}), ("rrr_lds", {pre + "_LDS": "1"}), ("standard", {})) if pre else (("standard", {}),)
+            for name, env in legs:
+                for k in envs:
+                    os.environ.pop(k, None)
+                os.environ.update(env)
+                eng = pkg.Engine(X, R)
+                eng.seed(seed)
+                eng.init_spins_random()
+                rates = []
+                for rep in range(reps + 1):                       # the first call is the warm-up
+                    if name == "standard":
+                        Es, acc = eng.standard_mc(beta, it, step)
+                        staged = np.zeros(R)
+                    else:
+                        Es, acc, staged = eng.rrr_mc(beta, it, step)
+                    _, sweep_ms, _ = eng.last_timing()
+                    if rep:
+                        rates.append(float(R) * it / (sweep_ms * 1e-3))
+                out[name] = {"kernel_iterations_per_s": float(np.median(rates)), "min": min(rates), "max": max(rates),
+                             "acceptance": float(acc.mean()) / it, "staged_frac": float(staged.mean()) / it,
+                             "energy_per_spin": float(Es[:, -1].mean()) / X.N}
+                eng.close()
+            for k in envs:
+                os.environ.pop(k, None)
+            print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "sk"
-    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc}[which]()
+    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm}[which]()
