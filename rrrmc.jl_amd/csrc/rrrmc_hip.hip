@@ -1294,6 +1294,9 @@ int32_t rrrmc_tracked_energy(rrrmc_ctx* ctx, int64_t* E_out)
     if (!sparse_int_model(ctx)) return fail(ctx, RRRMC_ERR_STATE, "this model's energies are Float64: use rrrmc_tracked_energy_f64");
     if (!ctx->results_valid || !ctx->d_E) return fail(ctx, RRRMC_ERR_STATE, "no sampler call has left a tracked energy");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the colour sweeps track no energy: d_E holds their last SAMPLE, taken before a sweep.  Evaluate the configuration they left instead
+    // (nothing resumes from d_E after such a call)
+    if (ctx->colored_call) { const int32_t rce = run_energy_bs(ctx, nullptr); if (rce) return rce; }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     { const int32_t rcp = post_sync_checks(ctx); if (rcp) return rcp; }
     std::vector<int32_t> E((size_t)ctx->Rpad);

@@ -1,5 +1,7 @@
 """GPU parity for the colour-parallel (checkerboard) sweeps on sparse +-J models: bit-exact against the oracle's
-sequential restatement, plus size-independent properties at BASELINE.json config 4's full lattice (L = 64, D = 3)."""
+sequential restatement, plus size-independent properties at BASELINE.json config 4's full lattice (L = 64, D = 3).  The restatement
+is this sampler's own definition: what backs it is tests/test_gpu_boltzmann.py, which holds the sweeps (checkerboard and greedy
+colouring) to the exact Boltzmann law."""
 import numpy as np
 import pytest
 

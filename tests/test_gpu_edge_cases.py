@@ -219,8 +219,10 @@ def test_full_width_config2_subset_against_oracle(pkg, oracle):
 
 def test_gpu_replicas_follow_the_boltzmann_law(pkg, oracle):
     """The reference's stationarity check (exact `truep`, RRRMC.jl:528-543, on a tiny system): after many sweeps the 8192 GPU
-    replicas of a 6-spin GraphRRG are distributed like exp(-beta E) / Z.  (All replicas attempt the same sites, so they are not
-    independent samples: the chi-square bound is generous.)"""
+    replicas of a 6-spin GraphRRG are distributed like exp(-beta E) / Z.  All replicas attempt the same sites, but given that sequence the
+    chains are independent (own start, own accept stream) and every step preserves the law: the chi-square limit is the derived upper 1e-6
+    quantile of tests/boltzmann_law.py, and the same counts must fail the law at 1.1 beta."""
+    import boltzmann_law as BL
     seed, N, beta, R = 11, 6, 0.6, 8192
     X = pkg.GraphRRG(N, 3, seed=seed)
     with pkg.Engine(X, R) as eng:
@@ -234,7 +236,14 @@ def test_gpu_replicas_follow_the_boltzmann_law(pkg, oracle):
     p = np.exp(-beta * Es)
     p /= p.sum()
     chi2 = float((((counts - R * p) ** 2) / (R * p)).sum())
-    assert chi2 < 4 * 2 ** N, chi2                                 # 63 degrees of freedom
+    assert chi2 < 4 * 2 ** N, chi2                                 # 63 degrees of freedom: the old, generous bound
+    law, wrong = BL.score(counts, p), BL.score(counts, BL.boltzmann(Es, 1.1 * beta))
+    print("chi2 %.1f (limit %.1f, %d dof, pooled mass %.4f); at 1.1 beta %.1f (limit %.1f)"
+          % (law.chi2, law.limit, law.dof, law.pooled_mass, wrong.chi2, wrong.limit))
+    BL.check_pooling(law)
+    BL.check_pooling(wrong)
+    assert law.chi2 < law.limit, (law.chi2, law.limit)
+    assert wrong.chi2 > wrong.limit, (wrong.chi2, wrong.limit)   # a 10 % error in beta does not pass
     assert abs((counts / R) @ Es - p @ Es) < 0.15                 # mean energy
 
 

@@ -1,7 +1,8 @@
 """GPU parity of the opt-in FAST standardMC on GraphRRGNormal / GraphEANormal (bit-sliced replicas, per-site threshold tables,
 spf_fast_kernels.hpp) against the oracle's restatement of that mode (orc_standard_mc_spf_fast): configurations and accepted counts
 identical, energies (re-evaluated from the spins at every sample on the device, tracked per move by the oracle) within 1e-9 relative
-— the north star asks 1e-6 for Float64 models."""
+— the north star asks 1e-6 for Float64 models.  That restatement shares the design it checks: what backs it is
+tests/test_gpu_boltzmann.py, which holds the fast chain to the exact Boltzmann law (K = 3, K = 4 and a negative β)."""
 import numpy as np
 import pytest
 
