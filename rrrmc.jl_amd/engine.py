@@ -1,32 +1,11 @@
 """Sampler front-end: ``Engine`` owns a device context; ``standardMC`` mirrors src/RRRMC.jl:81-127."""
+import contextlib
 import ctypes as C
 
 import numpy as np
 
 from ._lib import RRRMCError, check, lib
-from .graphs import DEFAULT_SEED, Config, GraphEA, nchunks
-
-MODEL_SPARSE_PM1 = 1
-MODEL_SK_NORMAL = 2
-MODEL_QUANT_RRG = 3
-MODEL_QUANT_SK, MODEL_QUANT_SKN, MODEL_QUANT_F64 = 8, 9, 10          # selectors of rrrmc_ctx_create_multi (GraphQuant over other slice families)
-MODEL_SK_BINARY = 4
-MODEL_SPARSE_F64 = 5
-MODEL_SPARSE_DISCRETIZED = 6
-MODEL_SPARSE_LEVELS = 7
-MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN = 11, 12, 13          # GraphRobustEnsemble (rrrmc_ctx_create_re; also the selectors of rrrmc_ctx_create_multi)
-MODEL_PERC = (17, 18)                                            # GraphPercStep, GraphPercLinear (rrrmc_ctx_create_perc)
-MODEL_RE_PERC, MODEL_LE_PERC = (19, 20), (21, 22)                # the ensembles over perceptron slices (rrrmc_set_patterns)
-MODEL_COMM = (23, 24)                                            # GraphCommStep, GraphCommReLU (rrrmc_ctx_create_comm)
-MODEL_RE_COMM, MODEL_LE_COMM = (25, 26), (27, 28)                # the ensembles over committee machine slices (rrrmc_set_comm_patterns)
-MODEL_RE = (MODEL_RE_EMPTY, MODEL_RE_SK, MODEL_RE_SKN) + MODEL_RE_PERC + MODEL_RE_COMM
-MODEL_LE_EMPTY, MODEL_LE_SK, MODEL_LE_SKN = 14, 15, 16          # GraphLocalEntropy (rrrmc_ctx_create_le; also the selectors of rrrmc_ctx_create_multi)
-MODEL_LE = (MODEL_LE_EMPTY, MODEL_LE_SK, MODEL_LE_SKN) + MODEL_LE_PERC + MODEL_LE_COMM
-
-
-def _set_comm_patterns(ctx, X1):
-    """rrrmc_set_comm_patterns with a committee machine's K2, patterns and (GraphCommReLU) labels"""
-    check(lib().rrrmc_set_comm_patterns(ctx, X1.K2, X1.xi.reshape(-1), X1.y, X1.P), ctx)
+from .graphs import DEFAULT_SEED, Config
 
 
 class Engine:
@@ -37,88 +16,18 @@ class Engine:
     def __init__(self, X, R=1, device=0, replica0=0, devices=None):
         self.X, self.R = X, int(R)
         self._ctx = C.c_void_p()
-        self._f64 = X.model_kind not in (MODEL_SPARSE_PM1, MODEL_SPARSE_LEVELS)
-        self._units = X.model_kind == MODEL_SPARSE_LEVELS        # device energies are int64 level units: X.energy_value converts
+        self._f64 = X._f64              # the device's energy word: Float64, else Int64
+        self._units = X._units          # device energies are int64 level units: X.energy_value converts
         if devices is not None:
             ids = np.asarray(list(devices), np.int32)
-            quant = X.model_kind == MODEL_QUANT_RRG
-            # a GraphQuant over dense slices is made per device by rrrmc_ctx_create_quant_skn / _sk: the selectors 9 / 8 of the header
-            kind = (X.model_kind if not quant else MODEL_QUANT_SKN if getattr(X, "skn_slices", False) else MODEL_QUANT_SK if X.sk_slices
-                    else MODEL_QUANT_F64 if getattr(X, "f64_slices", False) else X.model_kind)
-            re = X.model_kind in MODEL_RE or X.model_kind in MODEL_LE
-            check(lib().rrrmc_ctx_create_multi(C.byref(self._ctx), kind, X.Nk if quant or re else X.N, X.K, X.M if quant or re else 0, self.R,
-                                               ids, len(ids), replica0))
-        elif X.model_kind in MODEL_PERC:
-            check(lib().rrrmc_ctx_create_perc(C.byref(self._ctx), X.N, int(X.model_kind == 18), self.R, device, replica0))
-        elif X.model_kind in MODEL_COMM:
-            check(lib().rrrmc_ctx_create_comm(C.byref(self._ctx), X.K1, X.K2, int(X.model_kind == 24), self.R, device, replica0))
-        elif X.model_kind in MODEL_LE:
-            check(lib().rrrmc_ctx_create_le(C.byref(self._ctx), X.Nk, X.M, X.slice_kind, self.R, device, replica0))
-        elif X.model_kind in MODEL_RE:
-            check(lib().rrrmc_ctx_create_re(C.byref(self._ctx), X.Nk, X.M, X.slice_kind, self.R, device, replica0))
-        elif X.model_kind == MODEL_QUANT_RRG and getattr(X, "skn_slices", False):
-            check(lib().rrrmc_ctx_create_quant_skn(C.byref(self._ctx), X.Nk, X.M, self.R, device, replica0))
-        elif X.model_kind == MODEL_QUANT_RRG and X.sk_slices:
-            check(lib().rrrmc_ctx_create_quant_sk(C.byref(self._ctx), X.Nk, X.M, self.R, device, replica0))
-        elif X.model_kind == MODEL_QUANT_RRG and getattr(X, "f64_slices", False):
-            check(lib().rrrmc_ctx_create_quant_f64(C.byref(self._ctx), X.Nk, X.K, X.M, self.R, device, replica0))
-        elif X.model_kind == MODEL_QUANT_RRG:
-            check(lib().rrrmc_ctx_create_quant(C.byref(self._ctx), X.Nk, X.K, X.M, self.R, device, replica0))
+            kind, N, K, M = X._multi_args()
+            check(lib().rrrmc_ctx_create_multi(C.byref(self._ctx), kind, N, K, M, self.R, ids, len(ids), replica0))
         else:
-            check(lib().rrrmc_ctx_create(C.byref(self._ctx), X.model_kind, X.N, X.K, self.R, device, replica0))
+            X._create(C.byref(self._ctx), self.R, device, replica0)
         try:
-            if X.model_kind in MODEL_PERC:
-                check(lib().rrrmc_set_patterns(self._ctx, X.xi.reshape(-1), X.P), self._ctx)
-            elif X.model_kind in MODEL_COMM:
-                _set_comm_patterns(self._ctx, X)
-            elif X.model_kind in MODEL_LE:
-                if X.model_kind in MODEL_LE_COMM:
-                    _set_comm_patterns(self._ctx, X.X1)
-                elif X.model_kind in MODEL_LE_PERC:
-                    check(lib().rrrmc_set_patterns(self._ctx, X.X1.xi.reshape(-1), X.X1.P), self._ctx)
-                elif X.model_kind == MODEL_LE_SK:
-                    check(lib().rrrmc_set_couplings_bits(self._ctx, X.J.reshape(-1)), self._ctx)
-                elif X.model_kind == MODEL_LE_SKN:
-                    check(lib().rrrmc_set_couplings_dense(self._ctx, X.J.reshape(-1)), self._ctx)
-                check(lib().rrrmc_le_set_params(self._ctx, X.gamma, X.beta), self._ctx)
-                X._engine = self                # LEenergies / cenergy / distances inside a hook read this engine's live configuration
-            elif X.model_kind in MODEL_RE:
-                if X.model_kind in MODEL_RE_COMM:
-                    _set_comm_patterns(self._ctx, X.X1)
-                elif X.model_kind in MODEL_RE_PERC:
-                    check(lib().rrrmc_set_patterns(self._ctx, X.X1.xi.reshape(-1), X.X1.P), self._ctx)
-                elif X.model_kind == MODEL_RE_SK:
-                    check(lib().rrrmc_set_couplings_bits(self._ctx, X.J.reshape(-1)), self._ctx)
-                elif X.model_kind == MODEL_RE_SKN:
-                    check(lib().rrrmc_set_couplings_dense(self._ctx, X.J.reshape(-1)), self._ctx)
-                check(lib().rrrmc_re_set_params(self._ctx, X.gamma, X.beta), self._ctx)
-                X._engine = self                # REenergies(X) inside a hook reads this engine's live configuration
-            elif X.model_kind == MODEL_QUANT_RRG:
-                if getattr(X, "skn_slices", False):
-                    check(lib().rrrmc_set_couplings_dense(self._ctx, X.J.reshape(-1)), self._ctx)
-                elif X.sk_slices:
-                    check(lib().rrrmc_set_couplings_bits(self._ctx, X.J.reshape(-1)), self._ctx)
-                elif getattr(X, "f64_slices", False):
-                    check(lib().rrrmc_set_graph_f64(self._ctx, X.A, X.J.reshape(-1)), self._ctx)
-                else:
-                    check(lib().rrrmc_quant_slice_form(self._ctx, 1 if isinstance(X.X1, GraphEA) else 0), self._ctx)
-                    check(lib().rrrmc_set_graph(self._ctx, X.A, X.J), self._ctx)
-                check(lib().rrrmc_quant_set_field(self._ctx, X.beta, X.fourK), self._ctx)
-            elif X.model_kind == MODEL_SPARSE_DISCRETIZED:
-                check(lib().rrrmc_set_graph_discretized(self._ctx, X.A, X.dJ, X.rJ.reshape(-1), np.asarray(X.LEV, np.int32), len(X.LEV),
-                                                        X.ea_form), self._ctx)
-                check(lib().rrrmc_set_level_scale(self._ctx, X.lev_mul, X.lev_div), self._ctx)
-            elif X.model_kind == MODEL_SPARSE_LEVELS:
-                check(lib().rrrmc_set_graph_levels(self._ctx, X.A, X.J, np.asarray(X.LEV, np.int32), len(X.LEV), X.ea_form), self._ctx)
-                check(lib().rrrmc_set_level_scale(self._ctx, X.lev_mul, X.lev_div), self._ctx)
-            elif X.model_kind == MODEL_SPARSE_F64:
-                check(lib().rrrmc_set_graph_f64(self._ctx, X.A, X.J.reshape(-1)), self._ctx)
-            elif X.model_kind == MODEL_SK_BINARY:
-                check(lib().rrrmc_set_couplings_bits(self._ctx, X.J.reshape(-1)), self._ctx)
-            elif self._f64:
-                check(lib().rrrmc_set_couplings_dense(self._ctx, X.J.reshape(-1)), self._ctx)
-            else:
-                check(lib().rrrmc_set_graph(self._ctx, X.A, X.J), self._ctx)
+            X._upload(self._ctx)
+            if hasattr(X, "_engine"):
+                X._engine = self                # REenergies / LEenergies / cenergy / distances inside a hook read this engine's live configuration
         except RRRMCError:
             self.close()
             raise
@@ -172,7 +81,7 @@ class Engine:
         return self.X.energy_value(E) if self._units else E.astype(self.X.energy_dtype, copy=False)
 
     def fields(self):
-        f64 = self.X.model_kind in (MODEL_SK_NORMAL, MODEL_SPARSE_F64)        # GraphSK's cache is integer (SK.jl:33)
+        f64 = self.X._fields_f64
         lf = np.zeros((self.R, self.X.N), np.float64 if f64 else np.int64)
         check((lib().rrrmc_get_fields_f64 if f64 else lib().rrrmc_get_fields)(self._ctx, lf.reshape(-1)), self._ctx)
         return lf
@@ -277,8 +186,8 @@ class Engine:
     def rrr_mc(self, beta, iters, step=1, staged_thr=None, staged_thr_fact=5.0, want_energies=True):
         """rrrMC(X::DoubleGraph, β, iters; step, staged_thr, staged_thr_fact) (src/RRRMC.jl:221-290).
         Returns (Es[R, iters // step], accepted[R], staged_iters[R])."""
-        if staged_thr is None:          # RRRMC.jl:162-164 (SimpleGraph 0.8, DiscrGraph 0.5) and :226 (DoubleGraph 0.5)
-            staged_thr = 0.8 if self.X.model_kind in (MODEL_SK_NORMAL, MODEL_SK_BINARY, MODEL_SPARSE_F64) else 0.5
+        if staged_thr is None:
+            staged_thr = self.X._staged_thr
         check(lib().rrrmc_rrr_mc_async(self._ctx, float(beta), float(getattr(self.X, "fourK", 0.0)), int(iters), int(step),
                                        float(staged_thr), float(staged_thr_fact)), self._ctx)
         self._last = (int(iters), int(step))
@@ -324,10 +233,7 @@ class Engine:
         """(pos[R, N], sizes[R, 4]) of the DeltaECache after the last rrrMC call (GraphQuant); sizes[R, 16] for the DiscrGraphs
         (GraphRRG / GraphEA, rrrMC and bklMC) and the discretised DoubleGraphs, class k of replica r at [r, k]."""
         pos = np.zeros((self.R, self.X.N), np.int8)
-        M = getattr(self.X, "M", 0)
-        ncls = (4 if self.X.model_kind == MODEL_QUANT_RRG else 2 * ((M + 1) // 2) if self.X.model_kind in MODEL_RE
-                else 2 * (M // 2 + 2 if M % 2 == 0 else (M + 1) // 2) if self.X.model_kind in MODEL_LE else 16)
-        sizes = np.zeros((self.R, ncls), np.int32)
+        sizes = np.zeros((self.R, self.X._rrr_classes), np.int32)
         check(lib().rrrmc_rrr_cache(self._ctx, pos.ctypes.data, sizes.ctypes.data), self._ctx)
         return pos, sizes
 
@@ -501,11 +407,14 @@ class _HookRun:
         return Es, self.Cfg
 
 
+@contextlib.contextmanager
 def _setup(X, seed, C0, replicas, device, replica0, engine):
+    """The frame of the five sampler functions: yields (eng, Cfg) — the caller's engine or one made for the call (seeded, with C0 or random
+    spins) and the Config the run returns (C0 itself when given) — and closes the engine it made."""
     own = engine is None
     R = replicas if replicas is not None else (C0.R if C0 is not None else (engine.R if engine else 1))
     if C0 is not None and C0.N != X.N:
-        raise ValueError("Invalid C0, wrong N, expected %d, given: %d" % (X.N, C0.N))       # RRRMC.jl:172,234,320,385,482
+        raise ValueError("Invalid C0, wrong N, expected %d, given: %d" % (X.N, C0.N))       # RRRMC.jl:94,172,234,320,385,482
     eng = engine if engine is not None else Engine(X, R, device=device, replica0=replica0)
     try:
         if seed > 0 or own:
@@ -514,11 +423,10 @@ def _setup(X, seed, C0, replicas, device, replica0, engine):
             eng.set_config(C0)
         elif own:
             eng.init_spins_random()
-    except Exception:
+        yield eng, (C0 if C0 is not None else Config(X.N, eng.R))
+    finally:
         if own:
             eng.close()
-        raise
-    return own, eng, (C0 if C0 is not None else Config(X.N, eng.R))
 
 
 def _nsamples(Es):
@@ -536,8 +444,7 @@ def rrrMC(X, beta, iters, *, seed=DEFAULT_SEED, step=1, hook=None, C0=None, stag
     import math
     if not math.isfinite(beta):
         raise ValueError("β must be finite, given: %r" % beta)                     # RRRMC.jl:166,230
-    own, eng, Cfg = _setup(X, seed, C0, replicas, device, replica0, engine)
-    try:
+    with _setup(X, seed, C0, replicas, device, replica0, engine) as (eng, Cfg):
         iters, step = int(iters), int(step)
         if hook is None:
             Es, acc, staged = eng.rrr_mc(beta, iters, step, staged_thr, staged_thr_fact)
@@ -576,17 +483,13 @@ def rrrMC(X, beta, iters, *, seed=DEFAULT_SEED, step=1, hook=None, C0=None, stag
             print("accept rate = ", float(acc.mean()) / max(it, 1))
             print("frac. staged iters = ", float(staged.mean()) / max(it, 1))
         return Es, Cfg
-    finally:
-        if own:
-            eng.close()
 
 
 def bklMC(X, beta, iters, *, seed=DEFAULT_SEED, step=1, hook=None, C0=None, quiet=False, replicas=None, device=0, replica0=0, engine=None):
     """``bklMC(X, β, iters; seed, step, hook, C0, quiet)`` (src/RRRMC.jl:311-359) for a batch of replicas.  ``hook(nextstep, X, C, accepted, E)``
     (:341) is called at every sample point the skipped iterations pass; the run is cut there and resumed (``it``, ``nextstep`` and the pending
     (skip, move) draw carry on): the hooked run is the un-hooked chain bit for bit."""
-    own, eng, Cfg = _setup(X, seed, C0, replicas, device, replica0, engine)
-    try:
+    with _setup(X, seed, C0, replicas, device, replica0, engine) as (eng, Cfg):
         iters, step = int(iters), int(step)
         nsamp = iters // step
         if hook is None or nsamp == 0:
@@ -613,17 +516,13 @@ def bklMC(X, beta, iters, *, seed=DEFAULT_SEED, step=1, hook=None, C0=None, quie
             print("accept rate = ", float(moves.mean()) / max(iters, 1))
             print("true it = ", float(moves.mean()))
         return Es, Cfg
-    finally:
-        if own:
-            eng.close()
 
 
 def wtmMC(X, beta, samples, *, seed=DEFAULT_SEED, step=1.0, hook=None, C0=None, quiet=False, replicas=None, device=0, replica0=0, engine=None):
     """``wtmMC(X, β, samples; seed, step, hook, C0, quiet)`` (src/RRRMC.jl:376-426) for a batch of replicas.  ``hook(nextstep, X, C, num_moves, E)``
     (:404) is called at every sample time (``nextstep`` = the global time of the sample, k additions of step / N as :391,405 accumulate it);
     the run is cut there and resumed (the heap of waiting times, the global time and ``nextstep`` carry on)."""
-    own, eng, Cfg = _setup(X, seed, C0, replicas, device, replica0, engine)
-    try:
+    with _setup(X, seed, C0, replicas, device, replica0, engine) as (eng, Cfg):
         samples = int(samples)
         if hook is None:
             Es, moves, t = eng.wtm_mc(beta, samples, step)
@@ -654,9 +553,6 @@ def wtmMC(X, beta, samples, *, seed=DEFAULT_SEED, step=1.0, hook=None, C0=None, 
             print("global time = ", float(t.mean()))
             print("ratio = ", float(t.mean()) / max(float(moves.mean()), 1.0))
         return Es, Cfg
-    finally:
-        if own:
-            eng.close()
 
 
 def extremal_opt(X, tau, iters, *, seed=DEFAULT_SEED, step=1, hook=None, C0=None, quiet=False, replicas=None, device=0, replica0=0, engine=None):
@@ -664,8 +560,7 @@ def extremal_opt(X, tau, iters, *, seed=DEFAULT_SEED, step=1, hook=None, C0=None
     any other graph (the generic EOCacheCont).  Returns ``(C, Emin, Cmin, itmin)`` like the reference, with per-replica arrays.
     ``hook(it, X, C, E, Emin)`` (:501 — note the signature) is called every ``step`` iterations, before the move of iteration ``it``; the run is
     cut there and resumed (the ranking, E, Emin / Cmin / itmin carry on)."""
-    own, eng, Cfg = _setup(X, seed, C0, replicas, device, replica0, engine)
-    try:
+    with _setup(X, seed, C0, replicas, device, replica0, engine) as (eng, Cfg):
         iters, step = int(iters), int(step)
         if hook is None:
             _, Emin, Cmin, itmin = eng.extremal_opt(tau, iters, step)
@@ -697,9 +592,6 @@ def extremal_opt(X, tau, iters, *, seed=DEFAULT_SEED, step=1, hook=None, C0=None
             print("iters = ", it)
             print("min [it = %s] = %s" % (np.asarray(itmin).tolist(), np.asarray(Emin).tolist()))
         return Cfg, Emin, Cmin, itmin
-    finally:
-        if own:
-            eng.close()
 
 
 def standardMC(X, beta, iters, *, seed=DEFAULT_SEED, step=1, hook=None, C0=None, quiet=False,
@@ -716,30 +608,15 @@ def standardMC(X, beta, iters, *, seed=DEFAULT_SEED, step=1, hook=None, C0=None,
     return; the others go on, replicas being independent), and the run ends when none is left.  With frozen replicas ``Es`` is a list of
     per-replica vectors of different lengths, as R reference calls would return them.
     """
-    own = engine is None
-    R = replicas if replicas is not None else (C0.R if C0 is not None else (engine.R if engine else 1))
-    if C0 is not None and C0.N != X.N:
-        raise ValueError("Invalid C0, wrong N, expected %d, given: %d" % (X.N, C0.N))   # RRRMC.jl:94
-    eng = engine if engine is not None else Engine(X, R, device=device, replica0=replica0)
-    try:
-        if seed > 0 or own:
-            eng.seed(seed if seed > 0 else 0)
-        if C0 is not None:
-            eng.set_config(C0)
-        elif own:
-            eng.init_spins_random()
-        Cfg = C0 if C0 is not None else Config(X.N, eng.R)
-        accepted = np.zeros(eng.R, np.int64)
-        it = 0
+    with _setup(X, seed, C0, replicas, device, replica0, engine) as (eng, Cfg):
         if hook is None:
             Es, accepted = eng.standard_mc(beta, iters, step)
+            eng.get_config(Cfg)
             it = int(iters)
         else:
-            samples = []
-            frozen = np.zeros(eng.R, bool)                 # replicas whose hook has said "stop" (RRRMC.jl:107), with what they had then
-            frozen_cfg = Config(X.N, eng.R)
-            frozen_nsamp = np.zeros(eng.R, np.int64)
-            frozen_acc = np.zeros(eng.R, np.int64)
+            run = _HookRun(X, eng, Cfg)
+            accepted = np.zeros(eng.R, np.int64)
+            it = 0
             # Run up to the move before iteration k*step, call the hook with that state, continue.  The pieces RESUME one another
             # (Engine.set_resume): the cache and the tracked energy live on across hook calls as in the reference (RRRMC.jl:95-118), so
             # the hooked run of a Float64 model is the un-hooked chain bit for bit and the hook sees the tracked E.
@@ -751,57 +628,26 @@ def standardMC(X, beta, iters, *, seed=DEFAULT_SEED, step=1, hook=None, C0=None,
                     nxt = (it // step + 1) * step          # next sampled iteration
                     n = min(nxt - 1, iters) - it
                     if n > 0:
-                        _, a = eng.standard_mc(beta, n, step=n + 1, want_energies=False)
-                        accepted += a
+                        accepted = accepted + eng.standard_mc(beta, n, step=n + 1, want_energies=False)[1]
                         it += n
                     if nxt > iters:
                         break
                     E = eng.tracked_energy()
-                    samples.append(E)
-                    eng.get_config(Cfg)
-                    # a frozen replica's chain has ended for the caller: the hook keeps seeing the count and configuration it had then
-                    if frozen.any():
-                        Cfg.s[frozen] = frozen_cfg.s[frozen]
-                    go = hook(nxt, X, Cfg, np.where(frozen, frozen_acc, accepted), E)
-                    if np.ndim(go) == 0:
-                        if not go:
-                            it = nxt
-                            break
-                    else:
-                        go = np.asarray(go, bool)
-                        if go.shape != (eng.R,):
-                            raise ValueError("a hook returns one flag, or one per replica (%d)" % eng.R)
-                        new = ~go & ~frozen
-                        frozen_cfg.s[new] = Cfg.s[new]
-                        frozen_nsamp[new] = len(samples)
-                        frozen_acc[new] = accepted[new]
-                        frozen |= new
-                        if frozen.all():
-                            it = nxt
-                            break
-                    _, a = eng.standard_mc(beta, 1, step=2, want_energies=False)   # the move of iteration nxt
-                    accepted += a
                     it = nxt
+                    # the hook sees the live E of every replica, and the count a frozen replica had when it stopped (RRRMC.jl:107)
+                    if not run.call(hook, nxt, E, (run.view("acc", accepted), E), {"acc": accepted}):
+                        break
+                    accepted = accepted + eng.standard_mc(beta, 1, step=2, want_energies=False)[1]   # the move of iteration nxt
             finally:
                 eng.set_resume(False)
-            Es = np.stack(samples, axis=1) if samples else np.zeros((eng.R, 0), X.energy_dtype)
-        eng.get_config(Cfg)
-        if hook is not None and frozen.any():
-            # a frozen replica returns what it had when its hook said stop; the engine is given the same configuration, so that C and the
-            # device agree (its chain went on in the meantime: independent of the others, and discarded here)
-            Cfg.s[frozen] = frozen_cfg.s[frozen]
-            accepted[frozen] = frozen_acc[frozen]
-            eng.set_config(Cfg)
-            Es = [Es[r, :frozen_nsamp[r]] if frozen[r] else Es[r] for r in range(eng.R)]
+            Es, Cfg = run.finish(X.energy_dtype)
+            accepted = run.view("acc", accepted)
         if not quiet:
-            print("samples = ", Es.shape[1] if hasattr(Es, "shape") else [len(e) for e in Es])
+            print("samples = ", _nsamples(Es))
             print("iters = ", it)
-            # a frozen replica's count is over the iterations it ran (frozen_nsamp samples of `step` iterations each)
+            # a frozen replica's count is over the iterations it ran (run.nsamp samples of `step` iterations each)
             ran = np.full(eng.R, max(it, 1), np.float64)
-            if hook is not None and frozen.any():
-                ran[frozen] = np.maximum(frozen_nsamp[frozen] * step, 1)
+            if hook is not None and run.frozen.any():
+                ran[run.frozen] = np.maximum(run.nsamp[run.frozen] * step, 1)
             print("accept rate = ", float((accepted / ran).mean()))
         return Es, Cfg
-    finally:
-        if own:
-            eng.close()

@@ -80,11 +80,37 @@ def level_units(LEV):
     return tuple(x // g for x in t), g, div
 
 
+class _DeviceGraph:
+    """What ``Engine`` asks of a graph to put it on the device: ``_create`` makes the single-device context, ``_multi_args`` names it to
+    ``rrrmc_ctx_create_multi``, ``_upload`` makes the ``rrrmc_set_*`` calls (``_upload_couplings`` alone when the graph is the slice graph
+    of a GraphQuant or of an ensemble), and five facts.  The defaults are those of most families; a class overrides what differs."""
+    _f64 = True             # the device's energy word is Float64 (also behind the Int energies of the perceptrons and committee machines), else Int64
+    _units = False          # device energies are int64 level units: energy_value converts
+    _fields_f64 = False     # the cached local fields are Float64 (GraphSK's are integer: SK.jl:33)
+    _rrr_classes = 16       # ΔE classes in Engine.rrr_cache
+    _staged_thr = 0.5       # rrrMC's default: RRRMC.jl:162-164 (SimpleGraph 0.8, DiscrGraph 0.5) and :226 (DoubleGraph 0.5)
+
+    def _create(self, ctx, R, device, replica0):
+        check(lib().rrrmc_ctx_create(ctx, self.model_kind, self.N, self.K, R, device, replica0))
+
+    def _multi_args(self):
+        """(kind, N, K, M) of rrrmc_ctx_create_multi"""
+        return self.model_kind, self.N, self.K, 0
+
+    def _upload(self, ctx):
+        self._upload_couplings(ctx)
+
+
 class _SparseLevelsGraph:
     """GraphRRG{ET,LEV,K} / GraphEA{ET,LEV,2D} with levels other than (-1, 1) (RRG.jl:116-162, EA.jl:138-193): couplings in level
     units, energies come back from the device in units and are returned as ``units * lev_mul / lev_div`` (exact integers for Int
     levels, the Float64 value of the reference's DFloat64 / Rational otherwise)."""
     model_kind = 7          # RRRMC_MODEL_SPARSE_LEVELS
+    _f64, _units = False, True
+
+    def _upload(self, ctx):
+        check(lib().rrrmc_set_graph_levels(ctx, self.A, self.J, np.asarray(self.LEV, np.int32), len(self.LEV), self.ea_form), ctx)
+        check(lib().rrrmc_set_level_scale(ctx, self.lev_mul, self.lev_div), ctx)
 
     def _init_levels(self, A, J, LEV, ea_form):
         self.levels = tuple(LEV)
@@ -114,10 +140,18 @@ class _SparseLevelsGraph:
         return u if self.lev_div == 1.0 else u / self.lev_div
 
 
-class _SparsePM1Graph:
+class _SparsePM1Graph(_DeviceGraph):
     """Common part of GraphRRG / GraphEA with LEV = (-1, 1): neighbour table A[N, K], couplings J[N, K]."""
     model_kind = 1          # RRRMC_MODEL_SPARSE_PM1
     energy_dtype = np.int64
+    _f64 = False
+
+    def _upload(self, ctx):
+        check(lib().rrrmc_set_graph(ctx, self.A, self.J), ctx)
+
+    def _upload_couplings(self, ctx):
+        check(lib().rrrmc_quant_slice_form(ctx, 1 if isinstance(self, GraphEA) else 0), ctx)
+        check(lib().rrrmc_set_graph(ctx, self.A, self.J), ctx)
 
     def __init__(self, A, J):
         A = np.ascontiguousarray(A, np.int32)
@@ -222,10 +256,14 @@ class GraphEALevels(_SparseLevelsGraph, GraphEA):
         self.L, self.D = int(L), int(D)
 
 
-class _SparseF64Graph:
+class _SparseF64Graph(_DeviceGraph):
     """Common part of GraphRRGNormal / GraphEANormal: neighbour table A[N, K], Float64 couplings J[N, K]."""
     model_kind = 5          # RRRMC_MODEL_SPARSE_F64
     energy_dtype = np.float64
+    _fields_f64, _staged_thr = True, 0.8
+
+    def _upload_couplings(self, ctx):
+        check(lib().rrrmc_set_graph_f64(ctx, self.A, self.J.reshape(-1)), ctx)
 
     def __init__(self, A, J):
         A = np.ascontiguousarray(A, np.int32)
@@ -314,11 +352,16 @@ class GraphEANormal(_SparseF64Graph):
         return L, D, A, J
 
 
-class _DiscretizedGraph:
+class _DiscretizedGraph(_DeviceGraph):
     """Common part of Graph{RRG,EA}NormalDiscretized: ``A``, the Gaussian couplings ``cJ`` and their split
     ``dJ`` (levels, the inner DiscrGraph ``X0``) + ``rJ`` (residuals) by ``discretize`` (src/Common.jl:38-72)."""
     model_kind = 6          # RRRMC_MODEL_SPARSE_DISCRETIZED
     energy_dtype = np.float64
+
+    def _upload(self, ctx):
+        check(lib().rrrmc_set_graph_discretized(ctx, self.A, self.dJ, self.rJ.reshape(-1), np.asarray(self.LEV, np.int32), len(self.LEV),
+                                                self.ea_form), ctx)
+        check(lib().rrrmc_set_level_scale(ctx, self.lev_mul, self.lev_div), ctx)
 
     def _split(self, A, cJ, LEV):
         LEV = tuple(LEV)
@@ -364,7 +407,7 @@ class GraphEANormalDiscretized(_DiscretizedGraph):
         self.L, self.D = int(L), int(D)
 
 
-class GraphSKNormal:
+class GraphSKNormal(_DeviceGraph):
     """``GraphSKNormal(N)`` — Sherrington-Kirkpatrick model, couplings ~ Normal(0, 1/N) (src/graphs/SK.jl:181-210).
 
     ``GraphSKNormal.from_J(J)`` is ``GraphSKNormal(J; check=true)`` (SK.jl:184-197): J must be symmetric with a
@@ -373,6 +416,10 @@ class GraphSKNormal:
     model_kind = 2          # RRRMC_MODEL_SK_NORMAL
     energy_dtype = np.float64
     K = 0
+    _fields_f64, _staged_thr = True, 0.8
+
+    def _upload_couplings(self, ctx):
+        check(lib().rrrmc_set_couplings_dense(ctx, self.J.reshape(-1)), ctx)
 
     def __init__(self, N, seed=DEFAULT_SEED):
         J = np.zeros((int(N), int(N)), np.float64)
@@ -393,13 +440,17 @@ class GraphSKNormal:
         return self
 
 
-class GraphSK:
+class GraphSK(_DeviceGraph):
     """``GraphSK(N)`` — Sherrington-Kirkpatrick model with binary couplings J in {-1/sqrt(N), 1/sqrt(N)}
     (src/graphs/SK.jl:28-60).  ``J`` holds N BitVector rows ([N, ceil(N/64)] chunks, bit = 1 means +1/sqrt(N)).
     ``ET = Float64``; the cache is integer (lfields = sqrt(N) * delta_energy, SK.jl:137-140)."""
     model_kind = 4          # RRRMC_MODEL_SK_BINARY
     energy_dtype = np.float64
     K = 0
+    _staged_thr = 0.8
+
+    def _upload_couplings(self, ctx):
+        check(lib().rrrmc_set_couplings_bits(ctx, self.J.reshape(-1)), ctx)
 
     def __init__(self, N, seed=DEFAULT_SEED):
         J = np.zeros((int(N), nchunks(N)), np.uint64)
@@ -407,7 +458,7 @@ class GraphSK:
         self.N, self.J = int(N), J
 
 
-class GraphQuant:
+class GraphQuant(_DeviceGraph):
     """``GraphQuant(Nk, M, Γ, β, GraphRRG, Nk, K)`` — quantum Ising model in a transverse field Γ via the Suzuki-Trotter
     transformation: M coupled copies ("slices") of a classical graph (src/graphs/QT.jl:126-170).
 
@@ -418,6 +469,23 @@ class GraphQuant:
     """
     model_kind = 3          # RRRMC_MODEL_QUANT_RRG
     energy_dtype = np.float64
+    _rrr_classes = 4
+
+    def _create(self, ctx, R, device, replica0):
+        L = lib()
+        if self.sk_slices or self.skn_slices:
+            check((L.rrrmc_ctx_create_quant_skn if self.skn_slices else L.rrrmc_ctx_create_quant_sk)(ctx, self.Nk, self.M, R, device, replica0))
+        else:
+            check((L.rrrmc_ctx_create_quant_f64 if self.f64_slices else L.rrrmc_ctx_create_quant)(ctx, self.Nk, self.K, self.M, R, device, replica0))
+
+    def _multi_args(self):
+        # a GraphQuant over other slice families is made per device by rrrmc_ctx_create_quant_skn / _sk / _f64: the header's selectors
+        # RRRMC_MODEL_QUANT_SKN / _SK / _F64
+        return (9 if self.skn_slices else 8 if self.sk_slices else 10 if self.f64_slices else 3), self.Nk, self.K, self.M
+
+    def _upload(self, ctx):
+        self.X1._upload_couplings(ctx)
+        check(lib().rrrmc_quant_set_field(ctx, self.beta, self.fourK), ctx)
 
     def __init__(self, X1, M, Gamma, beta):
         import math
@@ -488,12 +556,18 @@ def GraphQSKT(Nk, M, Gamma, beta, seed=DEFAULT_SEED):
     return GraphQuant(GraphSK(Nk, seed=seed), M, Gamma, beta)
 
 
-class _GraphPerc:
+class _GraphPerc(_DeviceGraph):
     """The binary perceptron with ``N`` (odd) binary synapses trained on ``P`` random ±1 patterns (src/graphs/PercStep.jl, PercLinear.jl).
     ``xi`` holds the patterns as P rows of ceil(N/64) chunks, bit i of row a = ξ[a, i] (the ξv representation of gen_ξ; 1 means +1).  The
     reference draws them with an unpinned ``bitrand``: here ``seed`` names them (``rrrmc_gen_patterns``, host only), and
     ``from_patterns(ξ)`` takes an explicit P x N 0/1 matrix, as ``GraphPercStep(ξ, ξv)`` does."""
     K = 0
+
+    def _create(self, ctx, R, device, replica0):
+        check(lib().rrrmc_ctx_create_perc(ctx, self.N, int(self.linear), R, device, replica0))
+
+    def _upload_couplings(self, ctx):
+        check(lib().rrrmc_set_patterns(ctx, self.xi.reshape(-1), self.P), ctx)
 
     def __init__(self, N, P, seed=DEFAULT_SEED):
         N, P = int(N), int(P)
@@ -541,6 +615,7 @@ class GraphPercStep(_GraphPerc):
     """``GraphPercStep(N, P)`` (src/graphs/PercStep.jl:62-72): the energy is the number of misclassified patterns.  ``ET = Int``."""
     model_kind = 17         # RRRMC_MODEL_PERC_STEP
     energy_dtype = np.int64
+    linear = False
     __doc__ += _GraphPerc.__doc__
 
 
@@ -549,16 +624,23 @@ class GraphPercLinear(_GraphPerc):
     satisfy it, in units of 2 / sqrt(N).  ``ET = Float64``."""
     model_kind = 18         # RRRMC_MODEL_PERC_LINEAR
     energy_dtype = np.float64
+    linear = True
     __doc__ += _GraphPerc.__doc__
 
 
-class _GraphComm:
+class _GraphComm(_DeviceGraph):
     """A two-layer binary committee machine: ``K2`` hidden units of ``K1`` binary synapses each, N = K1 K2 (unit k owns synapses
     k K1 .. (k + 1) K1 - 1), trained on ``P`` random ±1 patterns.  ``xi`` holds the patterns as P rows of ceil(N/64) chunks (the layout of
     ``GraphPercStep``), ``y`` (GraphCommReLU only) the P labels as ceil(P/64) words.  ``fc=True`` draws each pattern over K1 inputs and
     repeats its columns K2 times (CommStep.jl:85-93).  ``seed`` names the draw (``rrrmc_gen_comm_patterns``, host only);
     ``from_patterns(K2, ξ[, y])`` takes an explicit P x N 0/1 matrix (and P labels), as ``GraphCommStep(K2, ξ, ξv)`` does."""
     relu = False
+
+    def _create(self, ctx, R, device, replica0):
+        check(lib().rrrmc_ctx_create_comm(ctx, self.K1, self.K2, int(self.relu), R, device, replica0))
+
+    def _upload_couplings(self, ctx):
+        check(lib().rrrmc_set_comm_patterns(ctx, self.K2, self.xi.reshape(-1), self.y, self.P), ctx)
 
     def __init__(self, K1, K2, P, fc=False, seed=DEFAULT_SEED):
         K1, K2, P = int(K1), int(K2), int(P)
@@ -644,84 +726,68 @@ def _ensemble_slice_kind(slice_graph):
             else 5 if isinstance(slice_graph, GraphCommStep) else 6)
 
 
-def _perc_ensemble(ens, G, args, seed):
-    """the reference's two signatures (src/REAliases.jl, src/LEAliases.jl): (N, P, M, γ, β) draws the patterns, (X, M, γ, β) takes X's"""
-    if isinstance(args[0], _GraphPerc):
+def _pattern_ensemble(ens, G, sig, args, **kw):
+    """the reference's two signatures (src/REAliases.jl:126-166, src/LEAliases.jl:126-189): (``sig``, M, γ, β) draws the patterns with
+    ``G(sig...; kw...)``, (X, M, γ, β) takes X's"""
+    if isinstance(args[0], G.__base__):
         if len(args) != 4:
             raise TypeError("expected (X, M, γ, β)")
         X, M, gamma, beta = args
         if not isinstance(X, G):
             raise TypeError("expected a %s, given a %s" % (G.__name__, type(X).__name__))
     else:
-        if len(args) != 5:
-            raise TypeError("expected (N, P, M, γ, β) or (X, M, γ, β)")
-        N, P, M, gamma, beta = args
-        X = G(N, P, seed=seed)
-    return ens(X.N, M, gamma, beta, X)
-
-
-def _comm_ensemble(ens, G, args, fc, seed):
-    """the reference's two signatures (src/REAliases.jl:126-166, src/LEAliases.jl:126-189): (K1, K2, P, M, γ, β; fc) draws the patterns,
-    (X, M, γ, β) takes X's"""
-    if isinstance(args[0], _GraphComm):
-        if len(args) != 4:
-            raise TypeError("expected (X, M, γ, β)")
-        X, M, gamma, beta = args
-        if not isinstance(X, G):
-            raise TypeError("expected a %s, given a %s" % (G.__name__, type(X).__name__))
-    else:
-        if len(args) != 6:
-            raise TypeError("expected (K1, K2, P, M, γ, β) or (X, M, γ, β)")
-        K1, K2, P, M, gamma, beta = args
-        X = G(K1, K2, P, fc=fc, seed=seed)
+        if len(args) != sig.count(",") + 4:
+            raise TypeError("expected (%s, M, γ, β) or (X, M, γ, β)" % sig)
+        *cargs, M, gamma, beta = args
+        X = G(*cargs, **kw)
     return ens(X.N, M, gamma, beta, X)
 
 
 def GraphCommStepRE(*args, fc=False, seed=DEFAULT_SEED):
     """``GraphCommStepRE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommStepRE(X::GraphCommStep, M, γ, β)`` (src/REAliases.jl:126-145): a Robust
     Ensemble of M committee machines that share one pattern matrix."""
-    return _comm_ensemble(GraphRobustEnsemble, GraphCommStep, args, fc, seed)
+    return _pattern_ensemble(GraphRobustEnsemble, GraphCommStep, "K1, K2, P", args, fc=fc, seed=seed)
 
 
 def GraphCommReLURE(*args, fc=False, seed=DEFAULT_SEED):
     """``GraphCommReLURE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommReLURE(X::GraphCommReLU, M, γ, β)`` (src/REAliases.jl:147-166)."""
-    return _comm_ensemble(GraphRobustEnsemble, GraphCommReLU, args, fc, seed)
+    return _pattern_ensemble(GraphRobustEnsemble, GraphCommReLU, "K1, K2, P", args, fc=fc, seed=seed)
 
 
 def GraphCommStepLE(*args, fc=False, seed=DEFAULT_SEED):
     """``GraphCommStepLE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommStepLE(X::GraphCommStep, M, γ, β)`` (src/LEAliases.jl): a Local Entropy
     ensemble of M committee machines and a centre that share one pattern matrix."""
-    return _comm_ensemble(GraphLocalEntropy, GraphCommStep, args, fc, seed)
+    return _pattern_ensemble(GraphLocalEntropy, GraphCommStep, "K1, K2, P", args, fc=fc, seed=seed)
 
 
 def GraphCommReLULE(*args, fc=False, seed=DEFAULT_SEED):
     """``GraphCommReLULE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommReLULE(X::GraphCommReLU, M, γ, β)`` (src/LEAliases.jl)."""
-    return _comm_ensemble(GraphLocalEntropy, GraphCommReLU, args, fc, seed)
+    return _pattern_ensemble(GraphLocalEntropy, GraphCommReLU, "K1, K2, P", args, fc=fc, seed=seed)
 
 
 def GraphPercStepRE(*args, seed=DEFAULT_SEED):
     """``GraphPercStepRE(N, P, M, γ, β)`` / ``GraphPercStepRE(X::GraphPercStep, M, γ, β)`` (src/REAliases.jl): a Robust Ensemble of M
     perceptrons that share one pattern matrix."""
-    return _perc_ensemble(GraphRobustEnsemble, GraphPercStep, args, seed)
+    return _pattern_ensemble(GraphRobustEnsemble, GraphPercStep, "N, P", args, seed=seed)
 
 
 def GraphPercLinearRE(*args, seed=DEFAULT_SEED):
     """``GraphPercLinearRE(N, P, M, γ, β)`` / ``GraphPercLinearRE(X::GraphPercLinear, M, γ, β)`` (src/REAliases.jl)."""
-    return _perc_ensemble(GraphRobustEnsemble, GraphPercLinear, args, seed)
+    return _pattern_ensemble(GraphRobustEnsemble, GraphPercLinear, "N, P", args, seed=seed)
 
 
 def GraphPercStepLE(*args, seed=DEFAULT_SEED):
     """``GraphPercStepLE(N, P, M, γ, β)`` / ``GraphPercStepLE(X::GraphPercStep, M, γ, β)`` (src/LEAliases.jl): a Local Entropy ensemble of M
     perceptrons and a centre that share one pattern matrix."""
-    return _perc_ensemble(GraphLocalEntropy, GraphPercStep, args, seed)
+    return _pattern_ensemble(GraphLocalEntropy, GraphPercStep, "N, P", args, seed=seed)
 
 
 def GraphPercLinearLE(*args, seed=DEFAULT_SEED):
     """``GraphPercLinearLE(N, P, M, γ, β)`` / ``GraphPercLinearLE(X::GraphPercLinear, M, γ, β)`` (src/LEAliases.jl)."""
-    return _perc_ensemble(GraphLocalEntropy, GraphPercLinear, args, seed)
+    return _pattern_ensemble(GraphLocalEntropy, GraphPercLinear, "N, P", args, seed=seed)
 
 
-class GraphRobustEnsemble:
+class GraphRobustEnsemble(_DeviceGraph):
     """``GraphRobustEnsemble(Nk, M, γ, β, slice_graph)`` — the Robust Ensemble (src/graphs/RE.jl:215-263): M replicas of one graph (the
     slices, which share one coupling set as ``Gconstr(args...)`` with the same ``args`` gives them) coupled by ``GraphRE{M,γ,β}`` through
     μ_i = Σ_k σ_(i,k), energy Σ_i −log(2 cosh(γ μ_i)) / β.  ``slice_graph`` is ``None`` (GraphEmpty: ``Graph0RE``), a binary ``GraphSK``
@@ -729,6 +795,18 @@ class GraphRobustEnsemble:
     j % M (RE.jl:76-95).  β here is the graph's (inside fk), not a sampler's.  ``ET = Float64``.  See ``REenergies``."""
     energy_dtype = np.float64
     K = 0
+    _rrr_classes = property(lambda self: 2 * ((self.M + 1) // 2))
+
+    def _create(self, ctx, R, device, replica0):
+        check(lib().rrrmc_ctx_create_re(ctx, self.Nk, self.M, self.slice_kind, R, device, replica0))
+
+    def _multi_args(self):
+        return self.model_kind, self.Nk, self.K, self.M
+
+    def _upload(self, ctx):
+        if self.X1 is not None:
+            self.X1._upload_couplings(ctx)
+        check(lib().rrrmc_re_set_params(ctx, self.gamma, self.beta), ctx)
 
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
@@ -769,18 +847,10 @@ def REenergies(X, C=None):
     """``REenergies(X)`` (RE.jl:285-301): the energy of every replica of the ensemble as its own graph defines it — shape (M,) for one
     replica of the batch, (R, M) otherwise — computed on the device from the CURRENT configuration of the engine that runs ``X`` (inside a
     hook: the sample's configuration).  With ``C`` (a ``Config`` of N = Nk M spins) it is evaluated for that configuration instead."""
-    from .engine import Engine
-    if C is not None:
-        with Engine(X, C.R) as eng:
-            eng.set_config(C)
-            return eng.re_energies()
-    eng = getattr(X, "_engine", None)
-    if eng is None or not eng._ctx:
-        raise RuntimeError("REenergies(X): no engine is running this graph; pass a configuration: REenergies(X, C)")
-    return eng.re_energies()
+    return _le_observable(X, C, "REenergies", "re_energies")
 
 
-class GraphLocalEntropy:
+class GraphLocalEntropy(_DeviceGraph):
     """``GraphLocalEntropy(Nk, M, γ, β, slice_graph)`` — the Local Entropy ensemble (src/graphs/LE.jl:183-318): M replicas of one graph (the
     slices), each coupled to an explicit reference configuration (the "centre", under a graph of the same kind, all sharing one coupling set)
     by ``GraphLE{M,γT}`` with γT = γ / β: ΔE0 = 2γT σc σ_(i,k) on a replica site and 2γT σc μ_i (μ_i = Σ_k σ_(i,k)) on the centre.
@@ -790,6 +860,18 @@ class GraphLocalEntropy:
     of the ensemble's energy.  See ``LEenergies``, ``cenergy`` and ``distances``."""
     energy_dtype = np.float64
     K = 0
+    _rrr_classes = property(lambda self: 2 * (self.M // 2 + 2 if self.M % 2 == 0 else (self.M + 1) // 2))
+
+    def _create(self, ctx, R, device, replica0):
+        check(lib().rrrmc_ctx_create_le(ctx, self.Nk, self.M, self.slice_kind, R, device, replica0))
+
+    def _multi_args(self):
+        return self.model_kind, self.Nk, self.K, self.M
+
+    def _upload(self, ctx):
+        if self.X1 is not None:
+            self.X1._upload_couplings(ctx)
+        check(lib().rrrmc_le_set_params(ctx, self.gamma, self.beta), ctx)
 
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
