@@ -89,7 +89,13 @@ enum rrrmc_model {
     RRRMC_MODEL_RE_COMM_STEP = 25,   /* GraphCommStepRE */
     RRRMC_MODEL_RE_COMM_RELU = 26,   /* GraphCommReLURE */
     RRRMC_MODEL_LE_COMM_STEP = 27,   /* GraphCommStepLE */
-    RRRMC_MODEL_LE_COMM_RELU = 28    /* GraphCommReLULE */
+    RRRMC_MODEL_LE_COMM_RELU = 28,   /* GraphCommReLULE */
+    /* GraphQuant over pattern-machine slices that share one pattern matrix (src/QAliases.jl:85-159): selectors of rrrmc_ctx_create_multi only
+       (N = Nk, K = K2 — ignored for the perceptrons —, M: rrrmc_ctx_create_quant_pattern per device; the contexts report RRRMC_MODEL_QUANT_RRG) */
+    RRRMC_MODEL_QUANT_PERC_STEP = 29,   /* GraphQPercStepT */
+    RRRMC_MODEL_QUANT_PERC_LINEAR = 30, /* GraphQPercLinearT */
+    RRRMC_MODEL_QUANT_COMM_STEP = 31,   /* GraphQCommStepT */
+    RRRMC_MODEL_QUANT_COMM_RELU = 32    /* GraphQCommReLUT */
 };
 
 /* slice families of rrrmc_ctx_create_re */
@@ -259,6 +265,19 @@ RRRMC_API int32_t rrrmc_ctx_create_quant_skn(rrrmc_ctx **out, int64_t Nk, int64_
  * the generic caches over all Nk * M spins — rrrmc_bkl_mc_async, rrrmc_wtm_mc_async, rrrmc_extremal_opt_async (neighbors = the two Trotter
  * neighbours, then the slice graph's, QT.jl:288-321); one thread per replica.  rrrmc_quant_observables is not wired for these slices. */
 RRRMC_API int32_t rrrmc_ctx_create_quant_f64(rrrmc_ctx **out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0);
+/* GraphQuant over M pattern machines that share one pattern matrix — GraphQPercStepT, GraphQPercLinearT, GraphQCommStepT, GraphQCommReLUT
+ * (src/QAliases.jl:85-159).  slice_kind is RRRMC_RE_SLICE_PERC_STEP / _PERC_LINEAR / _COMM_STEP / _COMM_RELU; Nk synapses per slice, for the
+ * committee machines Nk = K1*K2 (K2 is ignored for the perceptrons).  RRRMC_ERR_INVALID_ARG: Nk even (perceptrons); K1, K2 even (step) or odd
+ * (ReLU), Nk not a multiple of K2; M <= 2 (QT.jl:47).  RRRMC_ERR_UNSUPPORTED: Nk > 32767, N = Nk*M > 65535.  Then rrrmc_set_patterns
+ * (perceptrons) or rrrmc_set_comm_patterns (committee machines; 1 <= P <= 4096) and rrrmc_quant_set_field, without which every sampler,
+ * energy and observable call answers RRRMC_ERR_STATE.  Sites are GraphQuant's, x = k*Nk + i.  energy = energy(GraphQT) + sum_k
+ * energy(X1[k]) / M (QT.jl:185-199); delta_energy_residual = delta_energy(X1[k], C1[k], i) / M (QT.jl:270-281).  Served by rrrmc_rrr_mc_async
+ * (rrrMC(X::DoubleGraph), the DeltaECache over GraphQT only), rrrmc_standard_mc_async, rrrmc_energy_f64, rrrmc_set_resume,
+ * rrrmc_set_debug_checks (Stabilities, masks and E recomputed after a call), rrrmc_rrr_cache, the spin / snapshot / overlap calls,
+ * rrrmc_quant_observables and rrrmc_quant_renergies; one wavefront or one thread per replica (rrrmc_quant_pattern_build).  rrrmc_bkl_mc_async, rrrmc_wtm_mc_async and
+ * rrrmc_extremal_opt_async answer RRRMC_ERR_UNSUPPORTED (DeltaECacheCont over AllButOne neighbourhoods, as on the stand-alone graphs). */
+RRRMC_API int32_t rrrmc_ctx_create_quant_pattern(rrrmc_ctx **out, int32_t slice_kind, int64_t Nk, int64_t K2, int64_t M, int64_t R,
+                                                 int32_t device, uint32_t replica0);
 /* The Trotter coupling fourK (a type parameter of GraphQuant in the reference, QT.jl:126) and the beta it was derived
  * from: needed by rrrmc_energy_f64 before the first rrrMC call, and by rrrmc_standard_mc_async — standardMC on the GraphQuant
  * (src/RRRMC.jl:81-127 with delta_energy = delta_energy(X0) + delta_energy_residual, QT.jl:283-286; SITE + ACCEPT_F64 streams),
@@ -544,6 +563,16 @@ RRRMC_API int32_t rrrmc_overlaps(rrrmc_ctx *ctx, int64_t npairs, const int32_t *
  * Any output may be NULL.  The integer sums run on the device; the Float64 tail follows the reference's operation order. */
 RRRMC_API int32_t rrrmc_quant_observables(rrrmc_ctx *ctx, double beta, double Gamma, double *Qenergy_out, double *tmag_out,
                                           double *ovs_out);
+/* Renergies(X) (QT.jl:201-211) of a context made by rrrmc_ctx_create_quant_pattern: out[R * M] = energy(X1[k], C1[k]) of every slice of
+ * the live configuration — the training errors (GraphPercLinear: in its units of 2 / sqrt(Nk)) — recomputed from the configuration on the
+ * device.  Read-only: a run the context continues is not disturbed. */
+RRRMC_API int32_t rrrmc_quant_renergies(rrrmc_ctx *ctx, double *out);
+/* Which build of the sampler kernels the last rrrmc_rrr_mc_async / rrrmc_standard_mc_async call on a context made by
+ * rrrmc_ctx_create_quant_pattern ran (the first shard of a multi-device context): 0 = one thread per replica, 1 = one wavefront per replica
+ * with the slices' Stabilities in HBM/L2, 2 = one wavefront per replica with them staged in LDS.  Chosen by the rule of the other GraphQuants:
+ * up to 2048 replicas (RRRMC_QUANT_WAVE_MAX_R) run a wave build unless RRRMC_QUANT_NO_WAVE=1, with LDS staging when the state fits 160 KB
+ * unless RRRMC_QUANT_NO_LDS=1.  The builds give the same bits, and any of them continues a run another began (rrrmc_set_resume). */
+RRRMC_API int32_t rrrmc_quant_pattern_build(rrrmc_ctx *ctx, int32_t *build_out);
 
 /* ---- host-side graph constructors (setup, not hot): the disorder formats of SURVEY.md §8 a7/a8 ---- */
 /* gen_RRG (src/graphs/RRG.jl:26-69): A_out[N*K] 0-based, rows ascending. GRAPH stream of `seed`. */

@@ -58,6 +58,7 @@ const RE_EMPTY, RE_SK, RE_SKN = 11, 12, 13            # GraphRobustEnsemble over
 const LE_EMPTY, LE_SK, LE_SKN = 14, 15, 16            # GraphLocalEntropy over GraphEmpty / GraphSK / GraphSKNormal (rrrmc_ctx_create_le; multi selectors)
 const PERC_STEP, PERC_LINEAR = 17, 18                 # GraphPercStep, GraphPercLinear (rrrmc_ctx_create_perc; multi selectors)
 const COMM_STEP, COMM_RELU = 23, 24                   # GraphCommStep, GraphCommReLU (rrrmc_ctx_create_comm; multi selectors, N = K1 K2, K = K2)
+const QUANT_PAT_MODELS = (29, 30, 31, 32)              # by slice kind 3..6: GraphQPercStepT, GraphQPercLinearT, GraphQCommStepT, GraphQCommReLUT (multi selectors)
 const RE_MODELS = (RE_EMPTY, RE_SK, RE_SKN, 19, 20, 25, 26)   # by slice kind 0..6 (3, 4: GraphPercStep, GraphPercLinear; 5, 6: GraphCommStep, GraphCommReLU)
 const LE_MODELS = (LE_EMPTY, LE_SK, LE_SKN, 21, 22, 27, 28)
 const CommGraph = Union{RRRMC.CommStep.GraphCommStep,RRRMC.CommReLU.GraphCommReLU}
@@ -207,6 +208,17 @@ function Ctx(X::RRRMC.QT.GraphQuant{fourK,G}, R::Integer, β::Real; device = 0, 
         ctx = Ctx(ref[], R, Nk * M, true)
         Jm = Matrix{Float64}(undef, Nk, Nk); for i = 1:Nk; Jm[:, i] = X1.J[i]; end
         GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
+    elseif G <: Union{PercGraph,CommGraph}
+        # GraphQPercStepT / GraphQPercLinearT / GraphQCommStepT / GraphQCommReLUT (src/QAliases.jl:85-159): pattern machines on one pattern matrix
+        kind = ens_kind(G, "GraphQuant")
+        K2 = G <: CommGraph ? X1.K2 : 0
+        if devices === nothing
+            check(ccall((:rrrmc_ctx_create_quant_pattern, LIB), Int32, (Ref{Ptr{Cvoid}}, Int32, Int64, Int64, Int64, Int64, Int32, UInt32),
+                        ref, kind, Nk, K2, M, R, device, replica0))
+        else
+            ref[] = create(QUANT_PAT_MODELS[kind - 2], Nk, K2, M, R; replica0 = replica0, devices = devices)
+        end
+        ctx = set_patterns!(Ctx(ref[], R, Nk * M, true), X1)
     elseif G <: F64Graph
         # GraphQEAT = GraphQuant{fourK,GraphEANormal{twoD}} (src/QAliases.jl:50-83), and the same over a GraphRRGNormal: sparse Float64 slices
         K = length(X1.A[1])
@@ -293,7 +305,24 @@ function re_slices!(X::RRRMC.RE.GraphRobustEnsemble{M}, C::RRRMC.Config) where {
     end
     return X
 end
+# Renergies (QT.jl:201-211) of every replica of the batch of a GraphQuant over pattern machines, recomputed on the device from the live
+# configuration: column r = replica r
+function quant_renergies(ctx::Ctx, M::Integer)
+    out = Matrix{Float64}(undef, M, ctx.R)
+    check(ccall((:rrrmc_quant_renergies, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, out), ctx.p)
+    return out
+end
+# the slices' configurations C1[k] of a GraphQuant from a configuration of the whole graph (what energy(X, C) does, QT.jl:192-194): before
+# a user's hook runs, so that the reference's own RRRMC.QT.Renergies(X) / Qenergy(X, C) / overlaps(X) read the sample's configuration
+function quant_slices!(X::RRRMC.QT.GraphQuant, C::RRRMC.Config)
+    for k = 1:X.M
+        copyto!(X.C1[k].s, 1, C.s, (k - 1) * X.Nk + 1, X.Nk)
+    end
+    return X
+end
 re_hook(X, hook) = hook
+re_hook(X::RRRMC.QT.GraphQuant, hook::Nothing) = hook
+re_hook(X::RRRMC.QT.GraphQuant, hook) = (it, X_, C, a, b) -> (quant_slices!(X, C); hook(it, X_, C, a, b))
 re_hook(X::RRRMC.RE.GraphRobustEnsemble, hook::Nothing) = hook
 re_hook(X::RRRMC.RE.GraphRobustEnsemble, hook) = (it, X_, C, a, b) -> (re_slices!(X, C); hook(it, X_, C, a, b))
 
@@ -891,6 +920,20 @@ end
 OnGPU(X::RRRMC.Interface.AbstractGraph; replicas::Integer = 1, device::Integer = 0, devices = nothing, replica0::Integer = 0) =
     OnGPU{typeof(X)}(X, replicas, device, devices === nothing ? nothing : collect(Int, devices), replica0)
 RRRMC.getN(G::OnGPU) = RRRMC.getN(G.X)
+
+"`Renergies(OnGPU(X), C)`: the reference's `Renergies(X)` (src/graphs/QT.jl:201-211) of the configuration(s) `C` of a GraphQuant over pattern machines, computed by the library"
+function RRRMC.QT.Renergies(G::OnGPU, C::Union{RRRMC.Config,Vector{RRRMC.Config}})
+    X = G.X::RRRMC.QT.GraphQuant
+    Cs = C isa RRRMC.Config ? RRRMC.Config[C] : C
+    ctx = Ctx(X, length(Cs), X.β; device = G.device, replica0 = G.replica0, devices = G.devices)
+    try
+        set_configs!(ctx, Cs)
+        Es = quant_renergies(ctx, X.M)
+        return C isa RRRMC.Config ? Es[:, 1] : Es
+    finally
+        finalize(ctx)
+    end
+end
 
 # one context per call (β is needed by a GraphQuant's context only)
 function with_ctx(f, G::OnGPU, β::Real)

@@ -38,6 +38,7 @@ SYMBOLS = [
     "rrrmc_ctx_create_le", "rrrmc_le_set_params", "rrrmc_le_energies", "rrrmc_le_cenergy", "rrrmc_le_distances", "rrrmc_le_tables",
     "rrrmc_ctx_create_perc", "rrrmc_set_patterns", "rrrmc_gen_patterns",
     "rrrmc_ctx_create_comm", "rrrmc_set_comm_patterns", "rrrmc_gen_comm_patterns",
+    "rrrmc_ctx_create_quant_pattern", "rrrmc_quant_renergies", "rrrmc_quant_pattern_build",
 ]
 
 
@@ -238,6 +239,12 @@ def lib():
     L.rrrmc_set_comm_patterns.argtypes = [vp, C.c_int64, u64p, _U64OrNull, C.c_int64]
     L.rrrmc_gen_comm_patterns.restype = C.c_int32
     L.rrrmc_gen_comm_patterns.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, u64p, _U64OrNull]
+    L.rrrmc_ctx_create_quant_pattern.restype = C.c_int32
+    L.rrrmc_ctx_create_quant_pattern.argtypes = [C.POINTER(vp), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_uint32]
+    L.rrrmc_quant_pattern_build.restype = C.c_int32
+    L.rrrmc_quant_pattern_build.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.rrrmc_quant_renergies.restype = C.c_int32
+    L.rrrmc_quant_renergies.argtypes = [vp, f64p]
     L.rrrmc_le_distances.restype = C.c_int32
     L.rrrmc_le_distances.argtypes = [vp, i64p]
     L.rrrmc_le_tables.restype = C.c_int32

@@ -40,10 +40,12 @@ double host_det_exp(double x)
 }
 
 // energy(X, C) + gen_ΔEcache (RRRMC.jl:237-240): E into sk_E, cache arrays rebuilt
+int32_t quant_pat_run_init(rrrmc_ctx* ctx, const RrrParams& P);          // host_quant_pat.hpp
 int32_t quant_run_init(rrrmc_ctx* ctx, double beta, double fourK)
 {
     RrrParams P = quant_params(ctx, beta, fourK);
     P.ft1 = host_det_exp(-beta * fourK);
+    if (ctx->q_pat) return quant_pat_run_init(ctx, P);          // pattern-machine slices: the Stabilities of every slice too
     if (ctx->q_skn) {              // GraphSKNormal slices: Float64 slice caches rebuilt in the reference's summation order
         if ((size_t)ctx->qM * sizeof(long long) > 32768) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "M = %lld slices exceed the init kernel's LDS", (long long)ctx->qM);
         hipLaunchKernelGGL(rrr_init_skn_kernel, dim3((unsigned)ctx->R), dim3(kInitThreads), (size_t)ctx->qM * sizeof(long long), ctx->stream, P);

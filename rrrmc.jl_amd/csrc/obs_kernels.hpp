@@ -82,6 +82,8 @@ __global__ __launch_bounds__(64) void overlap_chunks_kernel(const uint32_t* cons
 //   e0[r]            = energy0(X0, C) = -sum_j sigma_j sigma_{j+Nk}                       (QT.jl:68-82)
 //   Eslice[r][k]     = energy(X1[k], C1[k]) (RRG.jl:164-189), or its integer n for GraphSK slices: E = n / sqrt(Nk) (SK.jl:62-96)
 //   ovs_raw[r][d-1]  = sum over slice pairs at ring distance d of pm1dot(slice k1, slice k2)   (QT.jl:213-233)
+// Slices without (A, J) or Jb — pattern machines, whose energies come from quant_pat_energies_kernel — pass K = 0, Jb = null and A = J = null:
+// the loop over the K neighbours is then the only reader of A and J and makes no pass, and Eslice comes out 0.  Keep it that way.
 __global__ __launch_bounds__(256) void quant_observables_kernel(const uint32_t* __restrict__ spins, const int32_t* __restrict__ A,
                                                                 const int8_t* __restrict__ J, const uint32_t* __restrict__ Jb, int Wk,
                                                                 int Nk, int M, int K, int W,

@@ -239,6 +239,24 @@ __device__ __forceinline__ void slice_cache_update(const RrrView& v, int move)
     if (v.Jd) skn_update(v, move);
     else if (v.Jf) spf_slice_update(v, move);
 }
+// What the GraphQuant kernels below ask of the slice graph: a policy SL, built per replica from the kernel's second argument.  This one serves
+// the slice families RrrParams carries (told apart at run time by the pointers of RrrView; no argument of its own); the pattern machines
+// bring theirs in quant_pat_kernels.hpp.
+//   kOnAccept = false: update_cache! runs with every spin flip, the undo of a rejected direct move included (the Float64 slices take their
+//   swap path there); true: the cache is a pure function of the configuration, so the direct branch updates it for an accepted move only.
+//   kWave (the LDS build only): the slice code is written for a whole wavefront, so all 64 lanes run the chain with identical values
+//   (wave-uniform control flow; stores of the chain's state name one address wave-wide) instead of lane 0 alone.  attach() is given the
+//   LDS behind the kernel's own arrays and may stage slice state there, detach() writes it back at the end of the call.
+struct QuantSlices {
+    struct Params {};
+    static constexpr bool kOnAccept = false;
+    static constexpr bool kWave = false;
+    __device__ __forceinline__ void attach(uint32_t* /*lds*/) {}
+    __device__ __forceinline__ void detach() {}
+    __device__ __forceinline__ QuantSlices(const Params&, int /*replica*/) {}
+    __device__ __forceinline__ double residual(const RrrView& v, int move) const { return any_residual(v, move); }
+    __device__ __forceinline__ void update(const RrrView& v, int move) const { slice_cache_update(v, move); }
+};
 
 // ArraySet delete! / push! (ArraySets.jl:56-76); one position array serves the four sets (membership is exclusive)
 __device__ __forceinline__ void set_move(const RrrView& v, int j, int k0, int k1)
@@ -579,8 +597,9 @@ inline size_t rrr_quant_lds_bytes(int64_t N, int64_t W, int64_t Nk, int64_t K)
 //   per slice site: 115 KB at config 5) by all 64 lanes; lane 0 then runs the chain.  Only the ArraySet member arrays (sv, 8 bytes
 //   per spin) are left in HBM/L2.  Same arithmetic, same order: results are unchanged.  (Worth 10 % at config 5: a chain on one
 //   lane is bound by its instruction stream — 5 cycles per instruction — more than by the loads.)
-template <bool LDS>
-__global__ __launch_bounds__(kRrrThreads) void rrr_quant_kernel(RrrParams P)
+// SL: the slice policy (QuantSlices above, or a pattern machine's): the slice calls are resolved at compile time, one kernel per family.
+template <bool LDS, class SL = QuantSlices>
+__global__ __launch_bounds__(kRrrThreads) void rrr_quant_kernel(RrrParams P, typename SL::Params Q)
 {
     extern __shared__ uint32_t q_lds[];
     int r;
@@ -591,6 +610,7 @@ __global__ __launch_bounds__(kRrrThreads) void rrr_quant_kernel(RrrParams P)
         if (r >= P.R) return;
     }
     RrrView v = rrr_view(P, r);
+    SL sl(Q, r);
     uint32_t* l_rng = nullptr;
     uint32_t* g_sp = v.sp; uint8_t* g_cls = v.cls; uint16_t* g_spos = static_cast<uint16_t*>(v.spos); int32_t* g_t = v.t;      // (the LDS build is 16-bit only)
     if constexpr (LDS) {
@@ -608,8 +628,9 @@ __global__ __launch_bounds__(kRrrThreads) void rrr_quant_kernel(RrrParams P)
         if (tid < 4) l_t[tid] = g_t[tid];
         __syncthreads();
         v.sp = l_sp; v.spos = l_spos; v.cls = l_cls; v.t = l_t; v.A = l_A; v.J = l_J;
+        sl.attach(l_rng + kRrrThreads * 8);
     }
-    const bool worker = !LDS || threadIdx.x == 0;
+    const bool worker = !LDS || threadIdx.x == 0 || SL::kWave;
     const uint32_t rep = P.replica0 + (uint32_t)r;
     double T[4], z = P.zz[r], E = P.E_cur[r], acc_rate = P.acc_rate[r];
     for (int k = 0; k < 4; ++k) T[k] = P.T[(size_t)r * 4 + k];
@@ -679,7 +700,7 @@ __global__ __launch_bounds__(kRrrThreads) void rrr_quant_kernel(RrrParams P)
                 zp += f1 - f0;
             }
             const double c = z / zp;
-            const double dE1 = any_residual(v, move);                      // delta_energy_residual, QT.jl:270-281
+            const double dE1 = sl.residual(v, move);                       // delta_energy_residual, QT.jl:270-281
             const double x = -P.beta * dE1;
             bool ok = (c >= 1 && x >= 0);
             if (!ok) {                                                                 // accept(c, x), RRRMC.jl:40-44
@@ -694,7 +715,7 @@ __global__ __launch_bounds__(kRrrThreads) void rrr_quant_kernel(RrrParams P)
             }
             if (ok) {
                 sflip(v.sp, move);                                                     // spinflip!(X, C, move)
-                slice_cache_update(v, move);
+                sl.update(v, move);
                 for (int q = 0; q < nst; ++q) set_move(v, sj[q], s0[q], s1[q]);        // apply_staged!
                 for (int q = 0; q < 4; ++q) T[q] = Tp[q];
                 z = zp;
@@ -704,11 +725,11 @@ __global__ __launch_bounds__(kRrrThreads) void rrr_quant_kernel(RrrParams P)
             }
         } else {
             // direct branch: apply_move! (DeltaE.jl:232-295), undone by a second apply_move! on rejection
-            const double dE1 = any_residual(v, move);
+            const double dE1 = sl.residual(v, move);
             double c = 0.0;
             for (int pass = 0; pass < 2; ++pass) {
                 sflip(v.sp, move);
-                slice_cache_update(v, move);                                          // the undo pass takes the swap path (move_last == move)
+                if constexpr (!SL::kOnAccept) sl.update(v, move);                     // the undo pass takes the swap path (move_last == move)
                 double zp = z;
                 for (int q = 0; q < 2; ++q) {
                     const int j = nb[q];
@@ -744,7 +765,11 @@ __global__ __launch_bounds__(kRrrThreads) void rrr_quant_kernel(RrrParams P)
                         ok = (double)((((uint64_t)o2.w[0] << 32) | o2.w[1]) >> 11) * 0x1.0p-53 < a;
                     }
                 }
-                if (ok) { E += dE0 + dE1; accepted += 1; acc = true; break; }
+                if (ok) {
+                    if constexpr (SL::kOnAccept) sl.update(v, move);
+                    E += dE0 + dE1; accepted += 1; acc = true;
+                    break;
+                }
             }
         }
         acc_rate = acc_rate * (1 - P.lambda) + (acc ? 1.0 : 0.0) * P.lambda;             // RRRMC.jl:281
@@ -761,16 +786,19 @@ __global__ __launch_bounds__(kRrrThreads) void rrr_quant_kernel(RrrParams P)
         for (int i = tid; i < P.W; i += nt) g_sp[i] = v.sp[i];
         for (int i = tid; i < P.N; i += nt) { g_spos[i] = static_cast<uint16_t*>(v.spos)[i]; g_cls[i] = v.cls[i]; }
         if (tid < 4) g_t[tid] = v.t[tid];
+        sl.detach();
     }
 }
 
 // standardMC (src/RRRMC.jl:81-127) on GraphQuant: delta_energy(X, C, move) = delta_energy(X0) + delta_energy_residual (QT.jl:283-286);
 // common site (SITE stream), rand53 < exp(-beta dE) (ACCEPT_F64 stream).  Runs after rrr_init_kernel (which leaves energy(X, C) in E_cur).
-__global__ __launch_bounds__(kRrrThreads) void quant_standard_kernel(RrrParams P)
+template <class SL = QuantSlices>
+__global__ __launch_bounds__(kRrrThreads) void quant_standard_kernel(RrrParams P, typename SL::Params Q)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= P.R) return;
     const RrrView v = rrr_view(P, r);
+    const SL sl(Q, r);
     const uint32_t rep = P.replica0 + (uint32_t)r;
     double E = P.E_cur[r];
     int64_t accepted = 0, ns = 0;
@@ -779,10 +807,10 @@ __global__ __launch_bounds__(kRrrThreads) void quant_standard_kernel(RrrParams P
         if (it == next_sample) { next_sample += P.step; P.Es[ns * P.R + r] = E; ns += 1; }
         const uint64_t g = P.g0 + (uint64_t)it;
         const int move = (int)site_of(P.k0, P.k1, g, (uint32_t)P.N);
-        const double dE = (double)qt_delta(v, move) * P.fourK + any_residual(v, move);
+        const double dE = (double)qt_delta(v, move) * P.fourK + sl.residual(v, move);
         const double x = -P.beta * dE;
         const bool acc = (x >= 0.0) || (rand53(P.k0, P.k1, g, rep) < det_exp(x));        // RRRMC.jl:39
-        if (acc) { sflip(v.sp, move); slice_cache_update(v, move); E += dE; accepted += 1; }
+        if (acc) { sflip(v.sp, move); sl.update(v, move); E += dE; accepted += 1; }
     }
     P.E_cur[r] = E;
     P.stats[(size_t)r * 2] = accepted; P.stats[(size_t)r * 2 + 1] = 0;

@@ -36,6 +36,7 @@
 #include "cont_wave_kernel.hpp"
 #include "perc_kernels.hpp"
 #include "comm_kernels.hpp"
+#include "quant_pat_kernels.hpp"
 #include "re_kernels.hpp"
 #include "le_kernels.hpp"
 
@@ -185,6 +186,9 @@ struct rrrmc_ctx {
     double* q_flf = nullptr;              // [R][M][Nk]
     double* q_fundo = nullptr;            // [R][M][K+1]
     int32_t* q_fml = nullptr;             // [R][M]
+    int q_pat_build = -1;                 // the build the last sampler call on a q_pat context ran (host_quant_pat.hpp: 0 thread, 1 wave, 2 wave + LDS), -1 none
+    int32_t q_pat = 0;                    // GraphQuant over pattern machines (GraphQPercStepT ..., src/QAliases.jl:85-159): the RRRMC_RE_SLICE_* kind, else 0;
+                                          // patterns and the slices' Stabilities in the pc_* / cm_* buffers below with rows = M (host_quant_pat.hpp)
     uint32_t* q_spins = nullptr;
     uint8_t* q_cls = nullptr;
     uint16_t* q_sv = nullptr;
@@ -596,6 +600,7 @@ inline void smp_commit(rrrmc_ctx* ctx, int kind, int64_t n) { ctx->smp_kind = ki
 #include "host_spf_fast.hpp"
 #include "host_perc.hpp"
 #include "host_comm.hpp"
+#include "host_quant_pat.hpp"
 #include "host_re.hpp"
 #include "host_le.hpp"
 int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact);
@@ -936,6 +941,8 @@ int32_t rrrmc_set_graph(rrrmc_ctx* ctx, const int32_t* A, const int8_t* J)
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph is for sparse +-J models; use rrrmc_set_couplings_dense%s", is_re(ctx) || is_le(ctx) ? " / rrrmc_set_couplings_bits (GraphRobustEnsemble, GraphLocalEntropy)" : "");
     if (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk)
         return fail(ctx, RRRMC_ERR_STATE, "this GraphQuant has binary GraphSK slices: give their couplings with rrrmc_set_couplings_bits");
+    if (quant_pat(ctx))
+        return fail(ctx, RRRMC_ERR_STATE, "this GraphQuant has pattern-machine slices: give their patterns with rrrmc_set_patterns / rrrmc_set_comm_patterns");
     if (!A || !J) return fail(ctx, RRRMC_ERR_INVALID_ARG, "A and J must not be NULL");
     const int64_t N = ctx->model == RRRMC_MODEL_QUANT_RRG ? ctx->qNk : ctx->N, K = ctx->K;
     for (int64_t q = 0; q < N * K; ++q) {
@@ -1264,8 +1271,8 @@ int32_t rrrmc_set_debug_checks(rrrmc_ctx* ctx, int32_t on)
 {
     RRRMC_MULTI(ctx, false, rrrmc_set_debug_checks(c, on));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_perc(ctx) && !is_comm(ctx))
-        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy, the perceptron and the committee machine graphs");
+    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_perc(ctx) && !is_comm(ctx) && !quant_pat(ctx))
+        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy, the perceptron and the committee machine graphs, and GraphQuant over the latter two");
     ctx->debug_checks = on != 0;
     return RRRMC_OK;
 }
@@ -1578,7 +1585,7 @@ int32_t rrrmc_colored_sweeps_async(rrrmc_ctx* ctx, double beta, int64_t sweeps, 
 // ---- GraphQuant + rrrMC: exported entry points ---------------------------------------------------------------------
 
 namespace {
-int32_t quant_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0, bool sk, bool skn = false, bool spf = false);
+int32_t quant_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0, bool sk, bool skn = false, bool spf = false, int32_t pat = 0);
 }
 int32_t rrrmc_ctx_create_quant(rrrmc_ctx** out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0)
 {
@@ -1596,6 +1603,11 @@ int32_t rrrmc_ctx_create_quant_f64(rrrmc_ctx** out, int64_t Nk, int64_t K, int64
 int32_t rrrmc_ctx_create_quant_skn(rrrmc_ctx** out, int64_t Nk, int64_t M, int64_t R, int32_t device, uint32_t replica0)
 {
     return quant_ctx_create(out, Nk, 0, M, R, device, replica0, false, true);
+}
+
+int32_t rrrmc_ctx_create_quant_pattern(rrrmc_ctx** out, int32_t slice_kind, int64_t Nk, int64_t K2, int64_t M, int64_t R, int32_t device, uint32_t replica0)
+{
+    return quant_pat_ctx_create(out, slice_kind, Nk, K2, M, R, device, replica0);
 }
 
 // ---- GraphRobustEnsemble: exported entry points (host_re.hpp) ---------------------------------------------------------------------
@@ -1673,8 +1685,8 @@ int32_t rrrmc_set_patterns(rrrmc_ctx* ctx, const uint64_t* xi, int64_t P)
     RRRMC_MULTI(ctx, false, rrrmc_set_patterns(c, xi, P));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (!is_perc(ctx) && !perc_slices(ctx))
-        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_patterns is for contexts made by rrrmc_ctx_create_perc, or by rrrmc_ctx_create_re / _le with a perceptron slice kind");
+    if (!is_perc(ctx) && !perc_slices(ctx) && !quant_pat_perc(ctx))
+        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_patterns is for contexts made by rrrmc_ctx_create_perc, or by rrrmc_ctx_create_re / _le / _quant_pattern with a perceptron slice kind");
     return perc_set_patterns(ctx, xi, P, is_perc(ctx) ? 1 : is_le(ctx) ? ctx->qM + 1 : ctx->qM);
 }
 
@@ -1689,8 +1701,8 @@ int32_t rrrmc_set_comm_patterns(rrrmc_ctx* ctx, int64_t K2, const uint64_t* xi, 
     RRRMC_MULTI(ctx, false, rrrmc_set_comm_patterns(c, K2, xi, y, P));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (!is_comm(ctx) && !comm_slices(ctx))
-        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_comm_patterns is for contexts made by rrrmc_ctx_create_comm, or by rrrmc_ctx_create_re / _le with a committee machine slice kind");
+    if (!is_comm(ctx) && !comm_slices(ctx) && !quant_pat_comm(ctx))
+        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_comm_patterns is for contexts made by rrrmc_ctx_create_comm, or by rrrmc_ctx_create_re / _le / _quant_pattern with a committee machine slice kind");
     return comm_set_patterns(ctx, K2, xi, y, P, is_comm(ctx) ? 1 : is_le(ctx) ? ctx->qM + 1 : ctx->qM);
 }
 
@@ -1797,7 +1809,9 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     if (replica0 % 32) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "replica0 must be a multiple of 32 (given %u)", replica0);
     rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
     if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
-    const bool quant = model == RRRMC_MODEL_QUANT_RRG || model == RRRMC_MODEL_QUANT_SK || model == RRRMC_MODEL_QUANT_SKN || model == RRRMC_MODEL_QUANT_F64;
+    const int32_t qpat = model == RRRMC_MODEL_QUANT_PERC_STEP ? RRRMC_RE_SLICE_PERC_STEP : model == RRRMC_MODEL_QUANT_PERC_LINEAR ? RRRMC_RE_SLICE_PERC_LINEAR
+                         : model == RRRMC_MODEL_QUANT_COMM_STEP ? RRRMC_RE_SLICE_COMM_STEP : model == RRRMC_MODEL_QUANT_COMM_RELU ? RRRMC_RE_SLICE_COMM_RELU : 0;
+    const bool quant = model == RRRMC_MODEL_QUANT_RRG || model == RRRMC_MODEL_QUANT_SK || model == RRRMC_MODEL_QUANT_SKN || model == RRRMC_MODEL_QUANT_F64 || qpat;
     const bool re = model == RRRMC_MODEL_RE_EMPTY || model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_RE_SKN || model == RRRMC_MODEL_RE_PERC_STEP || model == RRRMC_MODEL_RE_PERC_LINEAR ||
                     model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_RE_COMM_RELU;
     const bool le = model == RRRMC_MODEL_LE_EMPTY || model == RRRMC_MODEL_LE_SK || model == RRRMC_MODEL_LE_SKN || model == RRRMC_MODEL_LE_PERC_STEP || model == RRRMC_MODEL_LE_PERC_LINEAR ||
@@ -1820,7 +1834,8 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     if (re || le) { ctx->qNk = N; ctx->qM = M; }
     if (pc) { ctx->qNk = N; ctx->qM = 1; }
     if (cm) { ctx->qNk = N; ctx->qM = 1; ctx->cm_K2 = K; ctx->K = 0; }
-    if (quant) { ctx->qNk = N; ctx->qM = M; ctx->q_sk = model == RRRMC_MODEL_QUANT_SK; ctx->q_skn = model == RRRMC_MODEL_QUANT_SKN; ctx->q_spf = model == RRRMC_MODEL_QUANT_F64; }
+    if (quant) { ctx->qNk = N; ctx->qM = M; ctx->q_sk = model == RRRMC_MODEL_QUANT_SK; ctx->q_skn = model == RRRMC_MODEL_QUANT_SKN; ctx->q_spf = model == RRRMC_MODEL_QUANT_F64; ctx->q_pat = qpat; }
+    if (qpat >= RRRMC_RE_SLICE_COMM_STEP) { ctx->cm_K2 = K; ctx->K = 0; }
     for (int32_t d = 0; d < ndev; ++d) {
         int64_t b0 = 0, b1 = 0;
         shard_bounds(R, ndev, d, &b0, &b1);
@@ -1830,6 +1845,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : model == RRRMC_MODEL_QUANT_SK  ? rrrmc_ctx_create_quant_sk(&c, N, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_QUANT_SKN ? rrrmc_ctx_create_quant_skn(&c, N, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_QUANT_F64 ? rrrmc_ctx_create_quant_f64(&c, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : qpat ? rrrmc_ctx_create_quant_pattern(&c, qpat, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : re ? rrrmc_ctx_create_re(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : le ? rrrmc_ctx_create_le(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : pc ? rrrmc_ctx_create_perc(&c, N, model == RRRMC_MODEL_PERC_LINEAR, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
@@ -1847,11 +1863,11 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     return RRRMC_OK;
 }
 namespace {
-int32_t quant_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0, bool sk, bool skn, bool spf)
+int32_t quant_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0, bool sk, bool skn, bool spf, int32_t pat)
 {
     if (!out) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
-    if (Nk < 1 || (!sk && !skn && K < 1) || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "Nk, K, R must be >= 1");
+    if (Nk < 1 || (!sk && !skn && !pat && K < 1) || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "Nk, K, R must be >= 1");
     if (M <= 2) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "M must be greater than 2, given: %lld", (long long)M);   // QT.jl:47
     if (spf && K > kContKmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "K=%lld: the Float64 sparse slice kernels cover K <= %d", (long long)K, kContKmax);
     if (Nk * M > (int64_t)1 << 28) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N = Nk*M = %lld is beyond the GraphQuant kernels (N <= 2^28)", (long long)(Nk * M));
@@ -1863,7 +1879,7 @@ int32_t quant_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t K, int64_t M, int6
     if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
     ctx->model = RRRMC_MODEL_QUANT_RRG; ctx->N = Nk * M; ctx->K = K; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = Nk; ctx->qM = M; ctx->qW = 2 * ((Nk * M + 63) / 64);
-    ctx->q_sk = sk; ctx->q_skn = skn; ctx->q_spf = spf; ctx->q_Wk = 2 * ((Nk + 63) / 64);
+    ctx->q_sk = sk; ctx->q_skn = skn; ctx->q_spf = spf; ctx->q_pat = pat; ctx->q_Wk = 2 * ((Nk + 63) / 64);
     ctx->device = device; ctx->replica0 = replica0;
     const int64_t N = ctx->N;
 #define Q_TRY(expr)                                                                                              \
@@ -1892,6 +1908,8 @@ int32_t quant_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t K, int64_t M, int6
         Q_TRY(hipMalloc(&ctx->q_flf, sizeof(double) * (size_t)R * (size_t)M * (size_t)Nk));
         Q_TRY(hipMalloc(&ctx->q_fundo, sizeof(double) * (size_t)R * (size_t)M * (size_t)(K + 1)));
         Q_TRY(hipMalloc(&ctx->q_fml, sizeof(int32_t) * (size_t)R * (size_t)M));
+    } else if (pat) {
+        // (patterns, labels and Stabilities are allocated by rrrmc_set_patterns / rrrmc_set_comm_patterns)
     } else {
         Q_TRY(hipMalloc(&ctx->d_A, sizeof(int32_t) * Nk * K));
         Q_TRY(hipMalloc(&ctx->d_J, sizeof(int8_t) * Nk * K));
@@ -1958,7 +1976,11 @@ int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK,
     P.lambda = staged_thr_fact / (double)ctx->N;              // RRRMC.jl:243
     P.g0 = ctx->it_done; P.iters = iters; P.step = step; P.samp0 = S.samp0;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_sweep[0], st));
-    if (standard) {
+    if (ctx->q_pat) {
+        // pattern-machine slices (quant_pat_kernels.hpp): a wavefront or a thread per replica (quant_pat_build)
+        rc = quant_pat_launch(ctx, standard, P);
+        if (rc) return rc;
+    } else if (standard) {
         // few replicas (the reference's test_QIsing runs a handful): one wavefront per replica, 64 iterations prepared at a time
         // (quant_standard_wave_kernel); many replicas: one thread per replica fills the chip better
         const QsLayout sl = qs_layout(ctx->qW, ctx->qNk, ctx->K, ctx->q_Wk, ctx->q_sk);
@@ -1979,7 +2001,7 @@ int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK,
                 hipLaunchKernelGGL(quant_standard_wave_kernel<false>, dim3((unsigned)ctx->R), dim3(kRrrThreads), sl.bytes, st, P, X);
             }
         } else {
-            hipLaunchKernelGGL(quant_standard_kernel, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P);
+            hipLaunchKernelGGL(quant_standard_kernel<>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P, QuantSlices::Params{});
         }
     } else {
         // Few replicas of a cache that fits LDS (config 5: 128 x (Nk = 1024, M = 32)): one WAVEFRONT per replica, wave-uniform chain,
@@ -2014,13 +2036,14 @@ int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK,
                 HIP_TRY(ctx, raise_lds_attr(reinterpret_cast<const void*>(rrr_quant_kernel<true>), lds));
                 ctx->q_lds_attr = true;
             }
-            hipLaunchKernelGGL(rrr_quant_kernel<true>, dim3((unsigned)ctx->R), dim3(kRrrThreads), lds, st, P);
+            hipLaunchKernelGGL(rrr_quant_kernel<true>, dim3((unsigned)ctx->R), dim3(kRrrThreads), lds, st, P, QuantSlices::Params{});
         } else {
-            hipLaunchKernelGGL(rrr_quant_kernel<false>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P);
+            hipLaunchKernelGGL(rrr_quant_kernel<false>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P, QuantSlices::Params{});
         }
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_sweep[1], st));
+    if (ctx->q_pat && ctx->debug_checks) { rc = quant_pat_check(ctx, P); if (rc) return rc; }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_end, st));
     ctx->sweep_launches = 1;
     ctx->nsamp = nsamp;
@@ -2051,6 +2074,7 @@ int32_t rrrmc_rrr_mc_async(rrrmc_ctx* ctx, double beta, double fourK, int64_t it
     if (is_re(ctx)) return re_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (is_le(ctx)) return le_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model != RRRMC_MODEL_QUANT_RRG) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not available for model kind %d", ctx->model);
+    if (ctx->q_pat && !(ctx->last_fourK > 0.0)) return fail(ctx, RRRMC_ERR_STATE, "a GraphQuant over pattern machines needs (beta, fourK): call rrrmc_quant_set_field first");
     return quant_mc_async(ctx, false, beta, fourK, iters, step, staged_thr, staged_thr_fact);
 }
 
@@ -2064,6 +2088,7 @@ int32_t rrrmc_bkl_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t s
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
+    if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for a GraphQuant over pattern machines (DeltaECacheCont over AllButOne neighbourhoods): rrrMC and standardMC are");
     if (!std::isfinite(beta)) return fail(ctx, RRRMC_ERR_INVALID_ARG, "beta must be finite, given: %g", beta);
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
         return spf_cont_async(ctx, 1, beta, iters, step, 1.0, 0.0, 5.0);
@@ -2077,7 +2102,7 @@ int32_t rrrmc_quant_slice_form(rrrmc_ctx* ctx, int32_t ea_form)
     RRRMC_MULTI(ctx, false, rrrmc_quant_slice_form(c, ea_form));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (ctx->model != RRRMC_MODEL_QUANT_RRG || ctx->q_sk) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_quant_slice_form is for a GraphQuant over GraphRRG / GraphEA slices");
+    if (ctx->model != RRRMC_MODEL_QUANT_RRG || ctx->q_sk || ctx->q_pat) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_quant_slice_form is for a GraphQuant over GraphRRG / GraphEA slices");
     if (ctx->graph_set) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_quant_slice_form must precede rrrmc_set_graph");
     ctx->db_ea_form = ea_form ? 1 : 0;
     return RRRMC_OK;
@@ -2105,6 +2130,7 @@ int32_t rrrmc_wtm_mc_async(rrrmc_ctx* ctx, double beta, int64_t samples, double 
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
+    if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for a GraphQuant over pattern machines (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
         return spf_cont_async(ctx, 2, beta, samples, 1, step, 0.0, 5.0);
     if (ctx->model == RRRMC_MODEL_SK_NORMAL || ctx->model == RRRMC_MODEL_SK_BINARY) return sk_rrr_mc_async(ctx, beta, samples, 1, 0.0, 5.0, 2, step);
@@ -2134,6 +2160,7 @@ int32_t rrrmc_extremal_opt_async(rrrmc_ctx* ctx, const double* ftau, int64_t ite
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
+    if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for a GraphQuant over pattern machines (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)        // not DiscrGraphs: EOCacheCont
         return spf_cont_async(ctx, 3, 0.0, iters, step, 1.0, 0.0, 0.0, ftau);
     if (ctx->model == RRRMC_MODEL_SK_NORMAL || ctx->model == RRRMC_MODEL_SK_BINARY)                 // EOCacheCont, every spin a neighbour
@@ -2547,11 +2574,20 @@ int32_t rrrmc_quant_observables(rrrmc_ctx* ctx, double beta, double Gamma, doubl
     int32_t* d_e0 = ctx->d_qobs;
     int32_t* d_es = d_e0 + R;
     int32_t* d_ov = d_es + R * M;
+    // (pattern-machine slices have no (A, J): K = 0 leaves the kernel's slice energies at 0, and the slices' own energies — the training
+    //  errors, recomputed from the configuration — come from quant_pat_energies_kernel)
     hipLaunchKernelGGL(quant_observables_kernel, dim3((unsigned)R), dim3(256), lds, ctx->stream, ctx->q_spins, ctx->d_A, ctx->d_J,
                        ctx->q_sk ? ctx->q_Jb : nullptr, (int)ctx->q_Wk, (int)Nk, (int)M, (int)ctx->K, (int)ctx->qW, d_e0, d_es, d_ov);
     HIP_TRY(ctx, hipGetLastError());
     std::vector<int32_t> h((size_t)R * (size_t)(1 + M + H));
     HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->d_qobs, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<double> hp;
+    if (ctx->q_pat) {
+        rc = quant_pat_energies(ctx);
+        if (rc) return rc;
+        hp.resize((size_t)(R * M));
+        HIP_TRY(ctx, hipMemcpyAsync(hp.data(), ctx->re_Eslice, sizeof(double) * hp.size(), hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // Float64 tail in the reference's operation order (QT.jl:113-122, 235-251, 253-268); beta here is the caller's, as in
     // transverse_mag(X0, C, beta), fourK the context's
@@ -2563,7 +2599,7 @@ int32_t rrrmc_quant_observables(rrrmc_ctx* ctx, double beta, double Gamma, doubl
         double E = -Gamma * tm;
         const double sN = std::sqrt((double)Nk);                  // GraphSK slices: energy(X1[k], C1[k]) = n / sqrt(Nk), SK.jl:49,95
         for (int64_t k = 0; k < M; ++k) {
-            const double Ek = ctx->q_sk ? (double)h[(size_t)(R + r * M + k)] / sN : (double)h[(size_t)(R + r * M + k)];
+            const double Ek = ctx->q_pat ? hp[(size_t)(r * M + k)] : ctx->q_sk ? (double)h[(size_t)(R + r * M + k)] / sN : (double)h[(size_t)(R + r * M + k)];
             E += Ek / (double)N;
         }
         if (tmag_out) tmag_out[r] = tm;
@@ -2577,6 +2613,34 @@ int32_t rrrmc_quant_observables(rrrmc_ctx* ctx, double beta, double Gamma, doubl
             }
         }
     }
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_quant_pattern_build(rrrmc_ctx* ctx, int32_t* build_out)
+{
+    if (!ctx || !build_out) return RRRMC_ERR_INVALID_ARG;
+    if (is_multi(ctx)) return rrrmc_quant_pattern_build(ctx->kids[0], build_out);
+    if (!quant_pat(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_quant_pattern_build is for contexts made by rrrmc_ctx_create_quant_pattern");
+    if (ctx->q_pat_build < 0) return fail(ctx, RRRMC_ERR_STATE, "no sampler call has been made");
+    *build_out = ctx->q_pat_build;
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_quant_renergies(rrrmc_ctx* ctx, double* out)
+{
+    RRRMC_MULTI(ctx, true, rrrmc_quant_renergies(c, at_row(out, r0 * c->qM)));
+    int32_t rc = ensure_state(ctx, true);
+    if (rc) return rc;
+    if (!quant_pat(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_quant_renergies is for contexts made by rrrmc_ctx_create_quant_pattern");
+    if (!(ctx->last_fourK > 0.0)) return fail(ctx, RRRMC_ERR_STATE, "a GraphQuant over pattern machines needs (beta, fourK): call rrrmc_quant_set_field first");
+    if (!out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "out is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    { const int32_t rcp = post_sync_checks(ctx); if (rcp) return rcp; }
+    rc = quant_pat_energies(ctx);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->re_Eslice, sizeof(double) * (size_t)(ctx->R * ctx->qM), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RRRMC_OK;
 }
 

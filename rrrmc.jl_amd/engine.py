@@ -297,6 +297,20 @@ class Engine:
                                             Q.ctypes.data, tm.ctypes.data, ov.ctypes.data), self._ctx)
         return Q, tm, ov
 
+    def quant_renergies(self):
+        """Renergies (QT.jl:201-211) of the live configuration of a GraphQuant over pattern machines: (M,) for one replica, (R, M)
+        otherwise.  Read-only: a run the engine continues is not disturbed."""
+        out = np.zeros((self.R, self.X.M), np.float64)
+        check(lib().rrrmc_quant_renergies(self._ctx, out.reshape(-1)), self._ctx)
+        return out[0] if self.R == 1 else out
+
+    def quant_pattern_build(self):
+        """The kernel build the last rrrMC / standardMC call on a GraphQuant over pattern machines ran: 0 = one thread per replica, 1 = one
+        wavefront per replica, 2 = one wavefront per replica with the slice state staged in LDS."""
+        b = C.c_int32(-1)
+        check(lib().rrrmc_quant_pattern_build(self._ctx, C.byref(b)), self._ctx)
+        return b.value
+
     def spf_team_build(self):
         """(waves, width, slots) of the spf_team_kernel build the default standardMC of a GraphRRGNormal / GraphEANormal launches here;
         zeros when the one-wavefront kernel runs instead."""

@@ -458,6 +458,10 @@ class GraphSK(_DeviceGraph):
         self.N, self.J = int(N), J
 
 
+# RRRMC_RE_SLICE_* kind of a pattern machine -> the rrrmc_ctx_create_multi selector of the GraphQuant over it (RRRMC_MODEL_QUANT_PERC_STEP ...)
+_QUANT_PAT_MODELS = {3: 29, 4: 30, 5: 31, 6: 32}
+
+
 class GraphQuant(_DeviceGraph):
     """``GraphQuant(Nk, M, Γ, β, GraphRRG, Nk, K)`` — quantum Ising model in a transverse field Γ via the Suzuki-Trotter
     transformation: M coupled copies ("slices") of a classical graph (src/graphs/QT.jl:126-170).
@@ -465,7 +469,8 @@ class GraphQuant(_DeviceGraph):
     As the in-tree aliases do (src/QAliases.jl:43-67) the disorder is generated ONCE and shared by all slices:
     ``GraphQuant(X1, M, Γ, β)`` with ``X1`` a ``GraphRRG`` / ``GraphEA`` (±J), or a binary ``GraphSK`` — the reference's
     ``GraphQSKT(Nk, M, Γ, β)`` (src/QAliases.jl:34-43), the graph of ``scripts.jl:test_QIsing``.  ``N = Nk * M`` spins, slice-major.
-    ``ET = Float64``.
+    ``ET = Float64``.  ``X1`` may also be a pattern machine — ``GraphPercStep``, ``GraphPercLinear``, ``GraphCommStep``, ``GraphCommReLU`` — whose
+    pattern matrix all slices share: the reference's ``GraphQPercStepT`` ... (src/QAliases.jl:85-159).
     """
     model_kind = 3          # RRRMC_MODEL_QUANT_RRG
     energy_dtype = np.float64
@@ -473,7 +478,9 @@ class GraphQuant(_DeviceGraph):
 
     def _create(self, ctx, R, device, replica0):
         L = lib()
-        if self.sk_slices or self.skn_slices:
+        if self.pat_slices:
+            check(L.rrrmc_ctx_create_quant_pattern(ctx, self.pat_slices, self.Nk, self.K, self.M, R, device, replica0))
+        elif self.sk_slices or self.skn_slices:
             check((L.rrrmc_ctx_create_quant_skn if self.skn_slices else L.rrrmc_ctx_create_quant_sk)(ctx, self.Nk, self.M, R, device, replica0))
         else:
             check((L.rrrmc_ctx_create_quant_f64 if self.f64_slices else L.rrrmc_ctx_create_quant)(ctx, self.Nk, self.K, self.M, R, device, replica0))
@@ -481,6 +488,9 @@ class GraphQuant(_DeviceGraph):
     def _multi_args(self):
         # a GraphQuant over other slice families is made per device by rrrmc_ctx_create_quant_skn / _sk / _f64: the header's selectors
         # RRRMC_MODEL_QUANT_SKN / _SK / _F64
+        # ... and RRRMC_MODEL_QUANT_PERC_STEP / _PERC_LINEAR / _COMM_STEP / _COMM_RELU = 29 .. 32 (K = K2) for the pattern machines
+        if self.pat_slices:
+            return _QUANT_PAT_MODELS[self.pat_slices], self.Nk, self.K, self.M
         return (9 if self.skn_slices else 8 if self.sk_slices else 10 if self.f64_slices else 3), self.Nk, self.K, self.M
 
     def _upload(self, ctx):
@@ -497,10 +507,14 @@ class GraphQuant(_DeviceGraph):
         self.sk_slices = isinstance(X1, GraphSK)
         self.skn_slices = isinstance(X1, GraphSKNormal)                    # GraphQSKNormalT (QAliases.jl:45-46; test/runtests.jl:80)
         self.f64_slices = isinstance(X1, _SparseF64Graph)                  # GraphQEAT = GraphQuant{fourK,GraphEANormal{twoD}} (QAliases.jl:50-83)
-        dense = self.sk_slices or self.skn_slices
-        self.Nk, self.K = X1.N, (0 if dense else X1.K)
+        # pattern machines (GraphQPercStepT ..., QAliases.jl:85-159): the RRRMC_RE_SLICE_* kind; K = K2 for the committee machines
+        self.pat_slices = _ensemble_slice_kind(X1) if isinstance(X1, (_GraphPerc, _GraphComm)) else 0
+        dense = self.sk_slices or self.skn_slices or bool(self.pat_slices)
+        self.Nk, self.K = X1.N, (X1.K if not dense or isinstance(X1, _GraphComm) else 0)
         self.N = self.Nk * self.M
-        self.A, self.J = (None if dense else X1.A), X1.J                   # GraphSK slices: J = the bit-packed rows (SK.jl:32); GraphSKNormal: N x N Float64
+        if self.pat_slices:
+            self._engine = None                                            # the Engine running this graph: Renergies / Qenergy ... read its live configuration
+        self.A, self.J = (None if dense else X1.A), getattr(X1, "J", None)                   # GraphSK slices: J = the bit-packed rows (SK.jl:32); GraphSKNormal: N x N Float64
         # fourK = round(2/β * log(coth(β Γ / M)), digits = MAXDIGITS): QT.jl:165
         self.fourK = round(2.0 / beta * math.log(1.0 / math.tanh(beta * Gamma / M)), 8)
 
@@ -765,6 +779,33 @@ def GraphCommReLULE(*args, fc=False, seed=DEFAULT_SEED):
     return _pattern_ensemble(GraphLocalEntropy, GraphCommReLU, "K1, K2, P", args, fc=fc, seed=seed)
 
 
+def _pattern_quant(G, sig, args, **kw):
+    """the reference's two signatures (src/QAliases.jl:85-159): (``sig``, M, Γ, β) draws the patterns with ``G(sig...; kw...)``, (X, M, Γ, β)
+    takes X's; ``GraphQuant`` rounds fourK to 8 digits (QT.jl:165)"""
+    return _pattern_ensemble(lambda Nk, M, Gamma, beta, X: GraphQuant(X, M, Gamma, beta), G, sig, args, **kw)
+
+
+def GraphQPercStepT(*args, seed=DEFAULT_SEED):
+    """``GraphQPercStepT(N, P, M, Γ, β)`` / ``GraphQPercStepT(X::GraphPercStep, M, Γ, β)`` (src/QAliases.jl:101-115): a ``GraphQuant`` whose M
+    Trotter slices are perceptrons on one pattern matrix — quantum annealing of a learning problem.  See ``Renergies``."""
+    return _pattern_quant(GraphPercStep, "N, P", args, seed=seed)
+
+
+def GraphQPercLinearT(*args, seed=DEFAULT_SEED):
+    """``GraphQPercLinearT(N, P, M, Γ, β)`` / ``GraphQPercLinearT(X::GraphPercLinear, M, Γ, β)`` (src/QAliases.jl:85-99)."""
+    return _pattern_quant(GraphPercLinear, "N, P", args, seed=seed)
+
+
+def GraphQCommStepT(*args, fc=False, seed=DEFAULT_SEED):
+    """``GraphQCommStepT(K1, K2, P, M, Γ, β; fc)`` / ``GraphQCommStepT(X::GraphCommStep, M, Γ, β)`` (src/QAliases.jl:117-137)."""
+    return _pattern_quant(GraphCommStep, "K1, K2, P", args, fc=fc, seed=seed)
+
+
+def GraphQCommReLUT(*args, fc=False, seed=DEFAULT_SEED):
+    """``GraphQCommReLUT(K1, K2, P, M, Γ, β; fc)`` / ``GraphQCommReLUT(X::GraphCommReLU, M, Γ, β)`` (src/QAliases.jl:139-159)."""
+    return _pattern_quant(GraphCommReLU, "K1, K2, P", args, fc=fc, seed=seed)
+
+
 def GraphPercStepRE(*args, seed=DEFAULT_SEED):
     """``GraphPercStepRE(N, P, M, γ, β)`` / ``GraphPercStepRE(X::GraphPercStep, M, γ, β)`` (src/REAliases.jl): a Robust Ensemble of M
     perceptrons that share one pattern matrix."""
@@ -939,6 +980,44 @@ def distances(X, C=None):
     """``distances(X)`` (LE.jl:309-318): the M x M matrix of Hamming distances between the replica configurations, centre excluded — shape
     (M, M) for one replica of the batch, (R, M, M) otherwise (int64); read as ``LEenergies`` reads."""
     return _le_observable(X, C, "distances", "distances")
+
+
+def Renergies(X, C=None):
+    """``Renergies(X)`` (QT.jl:201-211) of a ``GraphQuant`` over pattern machines: the energy of every Trotter slice under its own graph — the
+    training errors; their minimum is what a quantum-annealing run on a learning problem reports — shape (M,) for one replica of the batch,
+    (R, M) otherwise.  Read as ``LEenergies`` reads: the live configuration of the engine that runs ``X`` (inside a hook: the sample's), or
+    ``C``; recomputed from the configuration on the device, so a hook that calls it does not change the run."""
+    return _le_observable(X, C, "Renergies", "quant_renergies")
+
+
+def Qenergy(X, C=None):
+    """``Qenergy(X, C)`` (QT.jl:253-268) of a ``GraphQuant``: a float for one replica of the batch, shape (R,) otherwise; read as ``Renergies``."""
+    Q = _le_observable(X, C, "Qenergy", "quant_observables")[0]
+    return float(Q[0]) if Q.size == 1 else Q
+
+
+def transverse_mag(X, C=None, beta=None):
+    """``transverse_mag(X.X0, C, β)`` (QT.jl:113-122) of a ``GraphQuant`` (β defaults to the graph's): a float for one replica, else (R,)."""
+    tm = _le_observable(X, C, "transverse_mag", "quant_observables")[1] if beta is None else _quant_observables_at(X, C, beta)[1]
+    return float(tm[0]) if tm.size == 1 else tm
+
+
+def overlaps(X, C=None):
+    """``overlaps(X)`` (QT.jl:213-251) of a ``GraphQuant``: shape (M // 2,) for one replica of the batch, (R, M // 2) otherwise."""
+    ov = _le_observable(X, C, "overlaps", "quant_observables")[2]
+    return ov[0] if ov.shape[0] == 1 else ov
+
+
+def _quant_observables_at(X, C, beta):
+    from .engine import Engine
+    if C is not None:
+        with Engine(X, C.R) as eng:
+            eng.set_config(C)
+            return eng.quant_observables(beta=beta)
+    eng = getattr(X, "_engine", None)
+    if eng is None or not eng._ctx:
+        raise RuntimeError("transverse_mag(X): no engine is running this graph; pass a configuration")
+    return eng.quant_observables(beta=beta)
 
 
 def checkerboard_coloring(L, D):
