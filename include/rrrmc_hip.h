@@ -95,7 +95,13 @@ enum rrrmc_model {
     RRRMC_MODEL_QUANT_PERC_STEP = 29,   /* GraphQPercStepT */
     RRRMC_MODEL_QUANT_PERC_LINEAR = 30, /* GraphQPercLinearT */
     RRRMC_MODEL_QUANT_COMM_STEP = 31,   /* GraphQCommStepT */
-    RRRMC_MODEL_QUANT_COMM_RELU = 32    /* GraphQCommReLUT */
+    RRRMC_MODEL_QUANT_COMM_RELU = 32,   /* GraphQCommReLUT */
+    /* random K-SAT (src/graphs/SAT.jl): the model of a context made by rrrmc_ctx_create_sat (N variables; K and M ignored by
+       rrrmc_ctx_create_multi), and the two ensembles over SAT slices that share one clause set (src/REAliases.jl:77-92,
+       src/LEAliases.jl:77-92): made by rrrmc_ctx_create_re / _le with RRRMC_RE_SLICE_SAT; selectors of rrrmc_ctx_create_multi (N = Nk, M) */
+    RRRMC_MODEL_SAT = 33,      /* GraphSAT(N, K, alpha): energy = the number of violated clauses (reported as Float64) */
+    RRRMC_MODEL_RE_SAT = 34,   /* GraphSATRE */
+    RRRMC_MODEL_LE_SAT = 35    /* GraphSATLE */
 };
 
 /* slice families of rrrmc_ctx_create_re */
@@ -106,7 +112,9 @@ enum rrrmc_re_slice {
     RRRMC_RE_SLICE_PERC_STEP = 3,   /* GraphPercStep (src/graphs/PercStep.jl): patterns with rrrmc_set_patterns; Nk odd */
     RRRMC_RE_SLICE_PERC_LINEAR = 4, /* GraphPercLinear (src/graphs/PercLinear.jl): patterns with rrrmc_set_patterns; Nk odd */
     RRRMC_RE_SLICE_COMM_STEP = 5,   /* GraphCommStep (src/graphs/CommStep.jl): patterns with rrrmc_set_comm_patterns; Nk = K1*K2, K1, K2 odd */
-    RRRMC_RE_SLICE_COMM_RELU = 6    /* GraphCommReLU (src/graphs/CommReLU.jl): patterns and labels with rrrmc_set_comm_patterns; K1, K2 even */
+    RRRMC_RE_SLICE_COMM_RELU = 6,   /* GraphCommReLU (src/graphs/CommReLU.jl): patterns and labels with rrrmc_set_comm_patterns; K1, K2 even */
+    /* 7 is unassigned: rrrmc_ctx_create_re / _le refuse it with RRRMC_ERR_INVALID_ARG */
+    RRRMC_RE_SLICE_SAT = 8          /* GraphSAT (src/graphs/SAT.jl): clauses with rrrmc_set_clauses */
 };
 
 /* Library ABI version (major*10000 + minor*100 + patch). */
@@ -347,6 +355,36 @@ RRRMC_API int32_t rrrmc_set_comm_patterns(rrrmc_ctx *ctx, int64_t K2, const uint
  * rrrmc_gen_patterns(fc ? K1 : K1*K2, P, seed) draws its rows, with fc's K1 columns repeated K2 times; y_out[ceil(P / 64)] (may be NULL)
  * from the SKBITS stream of `seed` with third counter word 2.  Needs no device. */
 RRRMC_API int32_t rrrmc_gen_comm_patterns(int64_t K1, int64_t K2, int64_t P, int32_t fc, uint64_t seed, uint64_t *xi_out, uint64_t *y_out);
+
+/* ---- Random K-SAT (src/graphs/SAT.jl; RRRMC_MODEL_SAT, RRRMC_MODEL_RE_SAT, RRRMC_MODEL_LE_SAT, RRRMC_RE_SLICE_SAT) ------
+ * rrrmc_ctx_create_sat: R chains of GraphSAT with N variables, N <= 65535 (RRRMC_ERR_UNSUPPORTED beyond: 16-bit variable ids).  Spins: one
+ * bit per variable in 64-bit chunks, as every chunk-layout model.  Then rrrmc_set_clauses.  Sampler: rrrmc_standard_mc_async
+ * (src/RRRMC.jl:81-127) with rrrmc_fetch_results_f64 (the integer energies arrive as exact Float64s), rrrmc_set_resume,
+ * rrrmc_set_debug_checks, rrrmc_energy_f64.  delta_energy is recomputed from the spins: there is no cache to keep.  rrrMC / bklMC / wtmMC /
+ * extremal_opt answer RRRMC_ERR_UNSUPPORTED on the stand-alone graph (an integer DeltaECache of max_conn + 1 levels over variable-degree
+ * neighbourhoods is not wired); rrrMC runs on the two ensembles.
+ *
+ * rrrmc_set_clauses: Mc clauses as vars[Mc * Kmax] (0-based variables in ascending order, short clauses padded with -1 at the end) and
+ * lits[Mc * Kmax] (literal k of clause a is satisfied iff spin vars[a][k] == lits[a][k]; pads ignored).  RRRMC_ERR_INVALID_ARG: an empty
+ * clause, a variable out of range, a variable twice in one clause, variables not ascending, a literal bit above 1.  RRRMC_ERR_UNSUPPORTED:
+ * a clause of more than 8 literals, Mc > 2^20, a variable in more than 65535 clauses.  For a context made by rrrmc_ctx_create_sat, or by
+ * rrrmc_ctx_create_re / _le with RRRMC_RE_SLICE_SAT (N = Nk: all slices, and the centre of a GraphLocalEntropy, share the one clause
+ * set).  May be called again: it ends a resumed run.
+ *
+ * rrrmc_sat_build: the kernel build of the last standardMC call on a stand-alone GraphSAT: 0 none yet, 1 one thread per replica
+ * (R > 16384, or RRRMC_SAT_NO_WAVE=1), 2 one wavefront per replica (R <= 16384: the two cross between 16384 and 32768 replicas, profiles/r12/sat.md; or RRRMC_SAT_WAVE=1).
+ * Both give the same bits. */
+RRRMC_API int32_t rrrmc_ctx_create_sat(rrrmc_ctx **out, int64_t N, int64_t R, int32_t device, uint32_t replica0);
+RRRMC_API int32_t rrrmc_set_clauses(rrrmc_ctx *ctx, int64_t Mc, int64_t Kmax, const int32_t *vars, const int8_t *lits);
+RRRMC_API int32_t rrrmc_sat_build(rrrmc_ctx *ctx, int32_t *build_out);
+/* The checks of rrrmc_set_clauses on the host alone, for N variables: the same codes and messages (a context-free failure: the text is
+ * rrrmc_last_error(NULL)); max_conn_out (may be NULL) receives max |T[i]|.  Needs no device. */
+RRRMC_API int32_t rrrmc_check_clauses(int64_t N, int64_t Mc, int64_t Kmax, const int32_t *vars, const int8_t *lits, int64_t *max_conn_out);
+/* gen_randomKSAT / choose (SAT.jl:17-56; the reference's rand is unpinned): Mc = round(alpha * N) (ties to even) clauses of K distinct
+ * ascending variables, vars_out[Mc * K] and lits_out[Mc * K] in the layout of rrrmc_set_clauses.  Draw n = a*K + k: the variable is
+ * 1 + floor(u64(GRAPH, n) * (N - k) / 2^64) followed by choose's bump and sorted insert; the literal bit of sorted position k is the top
+ * bit of u64(COUPLING, n).  Both arrays NULL: only Mc_out is written.  Needs no device. */
+RRRMC_API int32_t rrrmc_gen_ksat(int64_t N, int64_t K, double alpha, uint64_t seed, int64_t *Mc_out, int32_t *vars_out, int8_t *lits_out);
 
 /* ---- GraphLocalEntropy (src/graphs/LE.jl; RRRMC_MODEL_LE_*) -------------------------------------------------------
  * The Local Entropy ensemble: M replicas of one graph, each coupled to an explicit reference ("centre") configuration by the inner graph

@@ -59,15 +59,25 @@ const LE_EMPTY, LE_SK, LE_SKN = 14, 15, 16            # GraphLocalEntropy over G
 const PERC_STEP, PERC_LINEAR = 17, 18                 # GraphPercStep, GraphPercLinear (rrrmc_ctx_create_perc; multi selectors)
 const COMM_STEP, COMM_RELU = 23, 24                   # GraphCommStep, GraphCommReLU (rrrmc_ctx_create_comm; multi selectors, N = K1 K2, K = K2)
 const QUANT_PAT_MODELS = (29, 30, 31, 32)              # by slice kind 3..6: GraphQPercStepT, GraphQPercLinearT, GraphQCommStepT, GraphQCommReLUT (multi selectors)
-const RE_MODELS = (RE_EMPTY, RE_SK, RE_SKN, 19, 20, 25, 26)   # by slice kind 0..6 (3, 4: GraphPercStep, GraphPercLinear; 5, 6: GraphCommStep, GraphCommReLU)
-const LE_MODELS = (LE_EMPTY, LE_SK, LE_SKN, 21, 22, 27, 28)
+const SAT, RE_SAT, LE_SAT = 33, 34, 35                 # GraphSAT (rrrmc_ctx_create_sat), GraphSATRE, GraphSATLE (multi selectors)
+const RE_MODELS = (RE_EMPTY, RE_SK, RE_SKN, 19, 20, 25, 26, 0, RE_SAT)   # by slice kind 0..8 (3, 4: GraphPercStep, GraphPercLinear; 5, 6: GraphCommStep, GraphCommReLU; 7 unassigned; 8: GraphSAT)
+const LE_MODELS = (LE_EMPTY, LE_SK, LE_SKN, 21, 22, 27, 28, 0, LE_SAT)
 const CommGraph = Union{RRRMC.CommStep.GraphCommStep,RRRMC.CommReLU.GraphCommReLU}
 const PercGraph = Union{RRRMC.PercStep.GraphPercStep,RRRMC.PercLinear.GraphPercLinear}
 # slice kind of an ensemble's graph type (rrrmc_re_slice)
 ens_kind(G, what) = G <: RRRMC.SK.GraphSK ? 1 : G <: RRRMC.SK.GraphSKNormal ? 2 : G <: RRRMC.Empty.GraphEmpty ? 0 :
                     G <: RRRMC.PercStep.GraphPercStep ? 3 : G <: RRRMC.PercLinear.GraphPercLinear ? 4 :
-                    G <: RRRMC.CommStep.GraphCommStep ? 5 : G <: RRRMC.CommReLU.GraphCommReLU ? 6 :
-                    throw(ArgumentError("the engine runs the $what over GraphEmpty, GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, GraphCommStep and GraphCommReLU slices, given: $G"))
+                    G <: RRRMC.CommStep.GraphCommStep ? 5 : G <: RRRMC.CommReLU.GraphCommReLU ? 6 : G <: RRRMC.SAT.GraphSAT ? 8 :
+                    throw(ArgumentError("the engine runs the $what over GraphEmpty, GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, GraphCommStep, GraphCommReLU and GraphSAT slices, given: $G"))
+# the clauses of a GraphSAT as Mc rows of K = max length 0-based variables (-1 pads) and literal bits (SAT.jl:75-115): rrrmc_set_clauses
+function set_patterns!(ctx, X1::RRRMC.SAT.GraphSAT)
+    vars = fill(Int32(-1), X1.K, X1.M); lits = zeros(Int8, X1.K, X1.M)
+    for a = 1:X1.M, k = 1:length(X1.A[a])
+        vars[k, a] = X1.A[a][k] - 1; lits[k, a] = X1.J[a][k]
+    end
+    GC.@preserve vars lits check(ccall((:rrrmc_set_clauses, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int32}, Ptr{Int8}), ctx.p, X1.M, X1.K, vars, lits), ctx.p)
+    return ctx
+end
 # the patterns of a perceptron as P rows of chunks (ξv, PercStep.jl:19-29): rrrmc_set_patterns
 function set_patterns!(ctx, X1::PercGraph)
     nch = (X1.N + 63) >> 6
@@ -277,6 +287,25 @@ function Ctx(X::PercGraph, R::Integer; device = 0, replica0 = 0, devices = nothi
         ref[] = create(lin ? PERC_LINEAR : PERC_STEP, X.N, 0, 0, R; replica0 = replica0, devices = devices)
     end
     return set_patterns!(Ctx(ref[], R, X.N, true), X)
+end
+
+# ---- GraphSAT (src/graphs/SAT.jl), stand-alone: standardMC only (rrrMC / bklMC / wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED) ----
+# The integer energies arrive as exact Float64s.  GraphSATRE / GraphSATLE (src/REAliases.jl:77-92, src/LEAliases.jl:77-92) go through the
+# GraphRobustEnsemble / GraphLocalEntropy methods with slice kind 8.
+function Ctx(X::RRRMC.SAT.GraphSAT, R::Integer; device = 0, replica0 = 0, devices = nothing)
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    if devices === nothing
+        check(ccall((:rrrmc_ctx_create_sat, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, UInt32), ref, X.N, R, device, replica0))
+    else
+        ref[] = create(SAT, X.N, 0, 0, R; replica0 = replica0, devices = devices)
+    end
+    return set_patterns!(Ctx(ref[], R, X.N, true), X)
+end
+# which kernel ran the last standardMC call on a stand-alone GraphSAT: 0 none yet, 1 one thread per replica, 2 one wavefront per replica
+function sat_build(ctx::Ctx)
+    b = Ref{Int32}(0)
+    check(ccall((:rrrmc_sat_build, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), ctx.p, b), ctx.p)
+    return Int(b[])
 end
 
 # ---- GraphCommStep / GraphCommReLU (src/graphs/CommStep.jl, CommReLU.jl), stand-alone: standardMC only -------------------------------

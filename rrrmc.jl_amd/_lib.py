@@ -39,7 +39,22 @@ SYMBOLS = [
     "rrrmc_ctx_create_perc", "rrrmc_set_patterns", "rrrmc_gen_patterns",
     "rrrmc_ctx_create_comm", "rrrmc_set_comm_patterns", "rrrmc_gen_comm_patterns",
     "rrrmc_ctx_create_quant_pattern", "rrrmc_quant_renergies", "rrrmc_quant_pattern_build",
+    "rrrmc_ctx_create_sat", "rrrmc_set_clauses", "rrrmc_sat_build", "rrrmc_gen_ksat", "rrrmc_check_clauses",
 ]
+
+
+class _I32OrNull:
+    """an int32 array argument that may be None (a NULL pointer)"""
+    @classmethod
+    def from_param(cls, obj):
+        return None if obj is None else i32p.from_param(obj)
+
+
+class _I8OrNull:
+    """an int8 array argument that may be None (a NULL pointer)"""
+    @classmethod
+    def from_param(cls, obj):
+        return None if obj is None else i8p.from_param(obj)
 
 
 class RRRMCError(RuntimeError):
@@ -245,6 +260,16 @@ def lib():
     L.rrrmc_quant_pattern_build.argtypes = [vp, C.POINTER(C.c_int32)]
     L.rrrmc_quant_renergies.restype = C.c_int32
     L.rrrmc_quant_renergies.argtypes = [vp, f64p]
+    L.rrrmc_ctx_create_sat.restype = C.c_int32
+    L.rrrmc_ctx_create_sat.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int32, C.c_uint32]
+    L.rrrmc_set_clauses.restype = C.c_int32
+    L.rrrmc_set_clauses.argtypes = [vp, C.c_int64, C.c_int64, i32p, i8p]
+    L.rrrmc_sat_build.restype = C.c_int32
+    L.rrrmc_sat_build.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.rrrmc_check_clauses.restype = C.c_int32
+    L.rrrmc_check_clauses.argtypes = [C.c_int64, C.c_int64, C.c_int64, i32p, i8p, C.POINTER(C.c_int64)]
+    L.rrrmc_gen_ksat.restype = C.c_int32
+    L.rrrmc_gen_ksat.argtypes = [C.c_int64, C.c_int64, C.c_double, C.c_uint64, C.POINTER(C.c_int64), _I32OrNull, _I8OrNull]
     L.rrrmc_le_distances.restype = C.c_int32
     L.rrrmc_le_distances.argtypes = [vp, i64p]
     L.rrrmc_le_tables.restype = C.c_int32

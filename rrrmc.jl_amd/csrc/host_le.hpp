@@ -3,10 +3,10 @@
 // Robust Ensemble's buffers (re_sp, re_mu, re_tab, re_Eslice and the q_* DeltaECache arrays) with M + 1 rows.
 inline bool is_le(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_LE_EMPTY || ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_LE_SKN ||
                                                 ctx->model == RRRMC_MODEL_LE_PERC_STEP || ctx->model == RRRMC_MODEL_LE_PERC_LINEAR ||
-                                                ctx->model == RRRMC_MODEL_LE_COMM_STEP || ctx->model == RRRMC_MODEL_LE_COMM_RELU; }
+                                                ctx->model == RRRMC_MODEL_LE_COMM_STEP || ctx->model == RRRMC_MODEL_LE_COMM_RELU || ctx->model == RRRMC_MODEL_LE_SAT; }
 inline int le_slice_of(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_LE_SK ? RE_SK : ctx->model == RRRMC_MODEL_LE_SKN ? RE_SKN :
                                                       ctx->model == RRRMC_MODEL_LE_PERC_STEP ? RE_PSTEP : ctx->model == RRRMC_MODEL_LE_PERC_LINEAR ? RE_PLIN :
-                                                      ctx->model == RRRMC_MODEL_LE_COMM_STEP ? RE_CSTEP : ctx->model == RRRMC_MODEL_LE_COMM_RELU ? RE_CRELU : RE_EMPTY; }
+                                                      ctx->model == RRRMC_MODEL_LE_COMM_STEP ? RE_CSTEP : ctx->model == RRRMC_MODEL_LE_COMM_RELU ? RE_CRELU : ctx->model == RRRMC_MODEL_LE_SAT ? RE_SAT : RE_EMPTY; }
 inline int le_levels(int64_t M) { return (int)(M % 2 == 0 ? M / 2 + 2 : (M + 1) / 2); }        // length of allΔE(GraphLE) (LE.jl:176-179)
 
 // allΔE(GraphLE{M,γT}) (LE.jl:176-179): M even (0, 2|γT|, 4|γT|, 8|γT|, ..., 2M|γT|), M odd (2|γT|, 6|γT|, ..., 2M|γT|); Julia's integer
@@ -67,6 +67,7 @@ LeParams le_params(rrrmc_ctx* ctx, double beta)
     if (ctx->model == RRRMC_MODEL_LE_SKN) { P.Jd = ctx->sk_J; P.slf = ctx->q_slf; P.smv = ctx->q_smv; P.scur = ctx->q_scur; }
     if (le_slice_of(ctx) == RE_PSTEP || le_slice_of(ctx) == RE_PLIN) P.pc = perc_params(ctx, M + 1);
     if (le_slice_of(ctx) == RE_CSTEP || le_slice_of(ctx) == RE_CRELU) P.cm = comm_params(ctx, M + 1);
+    if (le_slice_of(ctx) == RE_SAT) P.sat = sat_table(ctx);
     P.tab = ctx->re_tab; P.etab = nullptr; P.ft = ctx->re_tab + L; P.ctab = reinterpret_cast<const uint8_t*>(ctx->re_tab + 2 * L);
     P.abi = ctx->q_spins; P.sp = ctx->re_sp; P.mu = ctx->re_mu; P.cls = ctx->q_cls; P.sv = ctx->q_sv; P.spos = ctx->q_spos; P.st = ctx->q_st;
     P.T = ctx->q_T; P.zz = ctx->q_z; P.E_cur = ctx->sk_E; P.acc_rate = ctx->q_accrate; P.stats = ctx->q_stats; P.Es = ctx->sk_Es;
@@ -95,6 +96,7 @@ int32_t le_run_init(rrrmc_ctx* ctx, double beta, bool cache)
         case RE_PLIN: hipLaunchKernelGGL(le_init_kernel<RE_PLIN>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CSTEP: hipLaunchKernelGGL(le_init_kernel<RE_CSTEP>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CRELU: hipLaunchKernelGGL(le_init_kernel<RE_CRELU>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
+        case RE_SAT: hipLaunchKernelGGL(le_init_kernel<RE_SAT>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         default: hipLaunchKernelGGL(le_init_kernel<RE_EMPTY>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -118,6 +120,7 @@ le_kernel_fn le_rrr_fn(int slice, bool lds, int L)
         case RE_PLIN: return lds ? le_rrr_for_L<true, RE_PLIN>(L) : le_rrr_for_L<false, RE_PLIN>(L);
         case RE_CSTEP: return lds ? le_rrr_for_L<true, RE_CSTEP>(L) : le_rrr_for_L<false, RE_CSTEP>(L);
         case RE_CRELU: return lds ? le_rrr_for_L<true, RE_CRELU>(L) : le_rrr_for_L<false, RE_CRELU>(L);
+        case RE_SAT: return lds ? le_rrr_for_L<true, RE_SAT>(L) : le_rrr_for_L<false, RE_SAT>(L);
         default: return lds ? le_rrr_for_L<true, RE_EMPTY>(L) : le_rrr_for_L<false, RE_EMPTY>(L);
     }
 }
@@ -136,6 +139,7 @@ int32_t le_debug_check(rrrmc_ctx* ctx, const LeParams& P0, bool cache)
         case RE_PLIN: hipLaunchKernelGGL(le_check_kernel<RE_PLIN>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CSTEP: hipLaunchKernelGGL(le_check_kernel<RE_CSTEP>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CRELU: hipLaunchKernelGGL(le_check_kernel<RE_CRELU>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
+        case RE_SAT: hipLaunchKernelGGL(le_check_kernel<RE_SAT>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         default: hipLaunchKernelGGL(le_check_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -192,6 +196,7 @@ int32_t le_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, i
             case RE_PLIN: hipLaunchKernelGGL(le_standard_kernel<RE_PLIN>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             case RE_CSTEP: hipLaunchKernelGGL(le_standard_kernel<RE_CSTEP>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             case RE_CRELU: hipLaunchKernelGGL(le_standard_kernel<RE_CRELU>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
+            case RE_SAT: hipLaunchKernelGGL(le_standard_kernel<RE_SAT>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             default: hipLaunchKernelGGL(le_standard_kernel<RE_EMPTY>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
         }
     } else {
@@ -246,6 +251,7 @@ int32_t le_observables(rrrmc_ctx* ctx)
         case RE_PLIN: hipLaunchKernelGGL(le_obs_kernel<RE_PLIN>, grid, blk, 0, ctx->stream, P); break;
         case RE_CSTEP: hipLaunchKernelGGL(le_obs_kernel<RE_CSTEP>, grid, blk, 0, ctx->stream, P); break;
         case RE_CRELU: hipLaunchKernelGGL(le_obs_kernel<RE_CRELU>, grid, blk, 0, ctx->stream, P); break;
+        case RE_SAT: hipLaunchKernelGGL(le_obs_kernel<RE_SAT>, grid, blk, 0, ctx->stream, P); break;
         default: hipLaunchKernelGGL(le_obs_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P); break;
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -258,8 +264,8 @@ int32_t le_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind
     *out = nullptr;
     const bool perc = slice_kind == RRRMC_RE_SLICE_PERC_STEP || slice_kind == RRRMC_RE_SLICE_PERC_LINEAR;
     const bool comm = slice_kind == RRRMC_RE_SLICE_COMM_STEP || slice_kind == RRRMC_RE_SLICE_COMM_RELU;
-    if (slice_kind != RRRMC_RE_SLICE_EMPTY && slice_kind != RRRMC_RE_SLICE_SK && slice_kind != RRRMC_RE_SLICE_SKN && !perc && !comm)
-        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind must be RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP, _PERC_LINEAR, _COMM_STEP or _COMM_RELU, given: %d", slice_kind);
+    if (slice_kind != RRRMC_RE_SLICE_EMPTY && slice_kind != RRRMC_RE_SLICE_SK && slice_kind != RRRMC_RE_SLICE_SKN && slice_kind != RRRMC_RE_SLICE_SAT && !perc && !comm)
+        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind must be RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP, _PERC_LINEAR, _COMM_STEP, _COMM_RELU or _SAT, given: %d", slice_kind);
     if (Nk < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "Nk and R must be >= 1");
     if (perc) { const int32_t rcn = perc_check_n(Nk); if (rcn) return rcn; }
     if (comm) { const int32_t rcn = comm_check_nk(Nk, slice_kind == RRRMC_RE_SLICE_COMM_RELU); if (rcn) return rcn; }
@@ -276,7 +282,8 @@ int32_t le_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind
     if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
     ctx->model = slice_kind == RRRMC_RE_SLICE_SK ? RRRMC_MODEL_LE_SK : slice_kind == RRRMC_RE_SLICE_SKN ? RRRMC_MODEL_LE_SKN :
                  slice_kind == RRRMC_RE_SLICE_PERC_STEP ? RRRMC_MODEL_LE_PERC_STEP : slice_kind == RRRMC_RE_SLICE_PERC_LINEAR ? RRRMC_MODEL_LE_PERC_LINEAR :
-                 slice_kind == RRRMC_RE_SLICE_COMM_STEP ? RRRMC_MODEL_LE_COMM_STEP : slice_kind == RRRMC_RE_SLICE_COMM_RELU ? RRRMC_MODEL_LE_COMM_RELU : RRRMC_MODEL_LE_EMPTY;
+                 slice_kind == RRRMC_RE_SLICE_COMM_STEP ? RRRMC_MODEL_LE_COMM_STEP : slice_kind == RRRMC_RE_SLICE_COMM_RELU ? RRRMC_MODEL_LE_COMM_RELU :
+                 slice_kind == RRRMC_RE_SLICE_SAT ? RRRMC_MODEL_LE_SAT : RRRMC_MODEL_LE_EMPTY;
     const int64_t rows = M + 1, N = Nk * rows, L = le_levels(M);
     ctx->N = N; ctx->K = 0; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = Nk; ctx->qM = M; ctx->qW = 2 * ((N + 63) / 64); ctx->q_Wk = 2 * ((Nk + 63) / 64);

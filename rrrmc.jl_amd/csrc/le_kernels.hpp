@@ -105,6 +105,8 @@ __global__ __launch_bounds__(kReInitThreads) void le_init_kernel(LeParams P, int
         perc_init_rows<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, Nk, N, s_n);          // (row 0, the centre: built, never used)
     } else if constexpr (kCommSlice<SLICE>) {
         comm_init_rows<SLICE == RE_CRELU>(P.cm, comm_view(P.cm, r), sp, Nk, N, s_n);          // (likewise)
+    } else if constexpr (SLICE == RE_SAT) {
+        sat_init_rows(P.sat, sp, Nk, 1, rows, s_n);
     }
     __syncthreads();
     if (cache) {
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(kReInitThreads) void le_init_kernel(LeParams P, int
             if constexpr (SLICE == RE_SK) { long long n = s_n[k]; n /= 2; E += (double)n / P.sN; }
             else if constexpr (SLICE == RE_SKN) E += s_E[k];
             else if constexpr (kPercSlice<SLICE>) E += perc_energy_of<SLICE == RE_PLIN>(s_n[k], P.pc.sN);
-            else if constexpr (kCommSlice<SLICE>) E += (double)s_n[k];
+            else if constexpr (kCommSlice<SLICE> || SLICE == RE_SAT) E += (double)s_n[k];
             else E += 0.0;
         }
         P.E_cur[r] = E;

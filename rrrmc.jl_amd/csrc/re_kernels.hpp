@@ -18,15 +18,18 @@
 #include "rrr_kernels.hpp"   // RrrView, sbit / sflip, slice_delta, skn_update, kRrrThreads, TAG_RRR, det_exp
 #include "perc_kernels.hpp"  // the binary perceptron slices (PercParams, perc_residual, perc_update, perc_init_rows)
 #include "comm_kernels.hpp"  // the binary committee machine slices (CommParams, comm_residual, comm_update, comm_init_rows)
+#include "sat_kernels.hpp"   // the K-SAT slices (SatTable, sat_delta, sat_row_energy, sat_init_rows)
 
 namespace rrrmc {
 
 enum ReSlice { RE_EMPTY = 0, RE_SK = 1, RE_SKN = 2,          // GraphEmpty (Graph0RE), binary GraphSK (GraphSKRE), GraphSKNormal
                RE_PSTEP = 3, RE_PLIN = 4,                    // GraphPercStep (GraphPercStepRE), GraphPercLinear (GraphPercLinearRE)
-               RE_CSTEP = 5, RE_CRELU = 6 };                 // GraphCommStep (GraphCommStepRE), GraphCommReLU (GraphCommReLURE)
+               RE_CSTEP = 5, RE_CRELU = 6,                   // GraphCommStep (GraphCommStepRE), GraphCommReLU (GraphCommReLURE)
+               RE_SAT = 8 };                                 // GraphSAT (GraphSATRE); 7 is unassigned, as in the ABI
 template <int SLICE> constexpr bool kPercSlice = SLICE == RE_PSTEP || SLICE == RE_PLIN;
 template <int SLICE> constexpr bool kCommSlice = SLICE == RE_CSTEP || SLICE == RE_CRELU;
 // slices whose state is a pure function of the configuration, updated once per accepted move by the whole wavefront in the LDS builds
+// (a K-SAT slice is not one: like the binary SK slice it keeps no state, its residual is recomputed from the spins by the worker thread)
 template <int SLICE> constexpr bool kWaveSlice = kPercSlice<SLICE> || kCommSlice<SLICE>;
 constexpr int kReMmax = 32;                                 // replicas of the ensemble; levels L = ceil(M / 2) <= 16
 
@@ -36,6 +39,7 @@ struct ReParams {
     const double* Jd;                                       // GraphSKNormal: [Nk][Nk]
     PercParams pc;                                          // perceptron slices: the shared patterns, every slice's Stabilities
     CommParams cm;                                          // committee machine slices: the same for GraphCommStep / GraphCommReLU
+    SatTable sat;                                           // K-SAT slices: the shared occurrence program (no per-slice state)
     double* slf;                                            // [R][2][M][Nk]  every slice's lfields / lfields_last (SK.jl:212-276)
     int32_t* smv;                                           // [R][M]         move_last of every slice (-1 = none)
     uint8_t* scur;                                          // [R][M]         which of the two arrays is `lfields`
@@ -120,11 +124,24 @@ __device__ __forceinline__ void re_slice_update(const RrrView& v, const CommView
     static_assert(kCommSlice<SLICE>, "a CommView goes with a committee machine slice");
     comm_update<SLICE == RE_CRELU, WAVE>(cv, k, i, sbit(v.sp, x));
 }
+// ... and with the K-SAT slices (sat_kernels.hpp): delta_energy from the row's spins, no update_cache!
+template <int SLICE>
+__device__ __forceinline__ double re_residual(const RrrView& v, const SatTable& sv, int x, int /*k*/, int i)
+{
+    static_assert(SLICE == RE_SAT, "a SatTable goes with a K-SAT slice");
+    return (double)sat_delta(sv, v.sp, x - i, i);
+}
+template <int SLICE, bool WAVE>
+__device__ __forceinline__ void re_slice_update(const RrrView&, const SatTable&, int, int, int)
+{
+    static_assert(SLICE == RE_SAT, "a SatTable goes with a K-SAT slice");
+}
 // the view of one chain's slice state that the kernels pass to the two above
 template <int SLICE, class PP>
 __device__ __forceinline__ auto re_slice_view(const PP& P, int r)
 {
-    if constexpr (kCommSlice<SLICE>) return comm_view(P.cm, r);
+    if constexpr (SLICE == RE_SAT) return P.sat;
+    else if constexpr (kCommSlice<SLICE>) return comm_view(P.cm, r);
     else return perc_view(P.pc, r);
 }
 // class of ABI site j with spin bit s, for the group's μ = mub + σ: a + L up (DeltaE.jl:80-86 with lfields[j] = σ_j fk(mū), RE.jl:101)
@@ -163,6 +180,8 @@ __device__ inline double re_slice_energy(const ReParams& P, const RrrView& v, in
         return perc_row_energy<SLICE == RE_PLIN>(P.pc, v.sp, k * Nk, Nk, P.N);
     } else if constexpr (kCommSlice<SLICE>) {
         return comm_row_energy<SLICE == RE_CRELU>(P.cm, v.sp, k * Nk, P.N);
+    } else if constexpr (SLICE == RE_SAT) {
+        return (double)sat_row_energy(P.sat, v.sp, k * Nk);
     } else {
         return 0.0;
     }
@@ -249,6 +268,8 @@ __global__ __launch_bounds__(kReInitThreads) void re_init_kernel(ReParams P, int
         perc_init_rows<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, Nk, N, s_n);
     } else if constexpr (kCommSlice<SLICE>) {
         comm_init_rows<SLICE == RE_CRELU>(P.cm, comm_view(P.cm, r), sp, Nk, N, s_n);
+    } else if constexpr (SLICE == RE_SAT) {
+        sat_init_rows(P.sat, sp, Nk, 0, M, s_n);
     }
     __syncthreads();
     if (cache) {
@@ -286,7 +307,7 @@ __global__ __launch_bounds__(kReInitThreads) void re_init_kernel(ReParams P, int
             if constexpr (SLICE == RE_SK) { long long n = s_n[k]; n /= 2; E += (double)n / P.sN; }
             else if constexpr (SLICE == RE_SKN) E += s_E[k];
             else if constexpr (kPercSlice<SLICE>) E += perc_energy_of<SLICE == RE_PLIN>(s_n[k], P.pc.sN);
-            else if constexpr (kCommSlice<SLICE>) E += (double)s_n[k];
+            else if constexpr (kCommSlice<SLICE> || SLICE == RE_SAT) E += (double)s_n[k];
             else E += 0.0;
         }
         P.E_cur[r] = E;

@@ -37,6 +37,7 @@
 #include "perc_kernels.hpp"
 #include "comm_kernels.hpp"
 #include "quant_pat_kernels.hpp"
+#include "sat_kernels.hpp"
 #include "re_kernels.hpp"
 #include "le_kernels.hpp"
 
@@ -296,6 +297,13 @@ struct rrrmc_ctx {
     int16_t* cm_ds = nullptr;      // [R][rows][K2 + 1][64 PW] Δ1 of every unit, Δ2
     uint64_t* cm_mk = nullptr;     // [R][rows][2 K2 + 2][PW] the sets p1, m1 of every unit, p2, m2
     int64_t cm_P = 0, cm_K2 = 0;
+    // ---- random K-SAT (RRRMC_MODEL_SAT, and the slices of RRRMC_MODEL_RE_SAT / _LE_SAT; host_sat.hpp): spins in q_spins, E in sk_E, counts
+    //      in q_stats; no per-chain cache ----
+    uint32_t* sat_off = nullptr;   // [Nk + 1] the occurrence program's CSR (sat_core.hpp)
+    SatEntry* sat_ent = nullptr;   // [sat_off[Nk]] one 16-byte entry per occurrence
+    uint32_t* sat_spT = nullptr;   // [qW][R] the thread build's transposed spins (allocated on first use)
+    int64_t sat_Mc = 0, sat_maxconn = 0;
+    int sat_build = 0;             // the build of the last standardMC call: 1 thread per replica, 2 wavefront per replica
 
     // ---- fast standardMC on RRRMC_MODEL_SPARSE_F64 (spf_fast_kernels.hpp; allocated on first use) ----
     std::vector<double> h_Jf;           // host copy of the couplings (threshold tables per beta)
@@ -457,7 +465,8 @@ hipError_t raise_lds_attr(const void* fn, size_t bytes)
 inline bool chunk_layout(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_QUANT_RRG || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_SPARSE_LEVELS ||
                                                        ctx->model == RRRMC_MODEL_RE_EMPTY || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_RE_SKN ||
                                                        ctx->model == RRRMC_MODEL_LE_EMPTY || ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_LE_SKN ||
-                                                       (ctx->model >= RRRMC_MODEL_PERC_STEP && ctx->model <= RRRMC_MODEL_LE_COMM_RELU); }
+                                                       (ctx->model >= RRRMC_MODEL_PERC_STEP && ctx->model <= RRRMC_MODEL_LE_COMM_RELU) ||
+                                                       ctx->model == RRRMC_MODEL_SAT || ctx->model == RRRMC_MODEL_RE_SAT || ctx->model == RRRMC_MODEL_LE_SAT; }
 inline bool sparse_int_model(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_SPARSE_PM1 || ctx->model == RRRMC_MODEL_SPARSE_LEVELS; }
 inline double lv_to_f64(const rrrmc_ctx* ctx, long long units) { return (double)(units * ctx->lv_mul) / ctx->lv_div; }
 
@@ -601,6 +610,7 @@ inline void smp_commit(rrrmc_ctx* ctx, int kind, int64_t n) { ctx->smp_kind = ki
 #include "host_perc.hpp"
 #include "host_comm.hpp"
 #include "host_quant_pat.hpp"
+#include "host_sat.hpp"
 #include "host_re.hpp"
 #include "host_le.hpp"
 int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact);
@@ -914,6 +924,7 @@ void rrrmc_ctx_destroy(rrrmc_ctx* ctx)
     free_dev(ctx->cs_spins); free_dev(ctx->cs_buf); free_dev(ctx->cs_u16);
     free_dev(ctx->snap); free_dev(ctx->d_pairs); free_dev(ctx->d_ovl); free_dev(ctx->d_qobs);
     free_dev(ctx->re_sp); free_dev(ctx->re_mu); free_dev(ctx->re_tab); free_dev(ctx->re_Eslice); free_dev(ctx->le_dist);
+    free_dev(ctx->sat_off); free_dev(ctx->sat_ent); free_dev(ctx->sat_spT);
     free_dev(ctx->pc_col); free_dev(ctx->pc_row); free_dev(ctx->pc_ds); free_dev(ctx->pc_pm); free_dev(ctx->pc_mm);
     free_dev(ctx->cm_col); free_dev(ctx->cm_row); free_dev(ctx->cm_lab); free_dev(ctx->cm_ds); free_dev(ctx->cm_mk);
     for (int i = 0; i < 2; ++i) { free_dev(ctx->d_slots[i]); free_dev(ctx->d_vecs[i]); free_dev(ctx->d_nbrs[i]); free_dev(ctx->d_masks[i]); }
@@ -1237,6 +1248,7 @@ int32_t rrrmc_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int6
     if (ctx->model == RRRMC_MODEL_SPARSE_LEVELS) return lev_standard_mc_async(ctx, beta, iters, step, false);
     if (is_perc(ctx)) return perc_mc_async(ctx, beta, iters, step);
     if (is_comm(ctx)) return comm_mc_async(ctx, beta, iters, step);
+    if (is_sat(ctx)) return sat_mc_async(ctx, beta, iters, step);
     if (is_re(ctx)) return re_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (is_le(ctx)) return le_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (ctx->model == RRRMC_MODEL_QUANT_RRG) {
@@ -1271,8 +1283,8 @@ int32_t rrrmc_set_debug_checks(rrrmc_ctx* ctx, int32_t on)
 {
     RRRMC_MULTI(ctx, false, rrrmc_set_debug_checks(c, on));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_perc(ctx) && !is_comm(ctx) && !quant_pat(ctx))
-        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy, the perceptron and the committee machine graphs, and GraphQuant over the latter two");
+    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_perc(ctx) && !is_comm(ctx) && !quant_pat(ctx) && !is_sat(ctx))
+        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy, the perceptron, the committee machine and the K-SAT graphs, and GraphQuant over perceptrons and committee machines");
     ctx->debug_checks = on != 0;
     return RRRMC_OK;
 }
@@ -1666,6 +1678,7 @@ int32_t rrrmc_re_energies(rrrmc_ctx* ctx, double* out)
         case RE_PLIN: hipLaunchKernelGGL(re_energies_kernel<RE_PLIN>, grid, blk, 0, ctx->stream, P); break;
         case RE_CSTEP: hipLaunchKernelGGL(re_energies_kernel<RE_CSTEP>, grid, blk, 0, ctx->stream, P); break;
         case RE_CRELU: hipLaunchKernelGGL(re_energies_kernel<RE_CRELU>, grid, blk, 0, ctx->stream, P); break;
+        case RE_SAT: hipLaunchKernelGGL(re_energies_kernel<RE_SAT>, grid, blk, 0, ctx->stream, P); break;
         default: hipLaunchKernelGGL(re_energies_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P); break;
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -1704,6 +1717,79 @@ int32_t rrrmc_set_comm_patterns(rrrmc_ctx* ctx, int64_t K2, const uint64_t* xi, 
     if (!is_comm(ctx) && !comm_slices(ctx) && !quant_pat_comm(ctx))
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_comm_patterns is for contexts made by rrrmc_ctx_create_comm, or by rrrmc_ctx_create_re / _le / _quant_pattern with a committee machine slice kind");
     return comm_set_patterns(ctx, K2, xi, y, P, is_comm(ctx) ? 1 : is_le(ctx) ? ctx->qM + 1 : ctx->qM);
+}
+
+// ---- random K-SAT: exported entry points (host_sat.hpp) ----
+int32_t rrrmc_ctx_create_sat(rrrmc_ctx** out, int64_t N, int64_t R, int32_t device, uint32_t replica0)
+{
+    return sat_ctx_create(out, N, R, device, replica0);
+}
+
+int32_t rrrmc_set_clauses(rrrmc_ctx* ctx, int64_t Mc, int64_t Kmax, const int32_t* vars, const int8_t* lits)
+{
+    RRRMC_MULTI(ctx, false, rrrmc_set_clauses(c, Mc, Kmax, vars, lits));
+    smp_drop(ctx);
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!is_sat(ctx) && !sat_slices(ctx))
+        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_clauses is for contexts made by rrrmc_ctx_create_sat, or by rrrmc_ctx_create_re / _le with RRRMC_RE_SLICE_SAT");
+    return sat_set_clauses(ctx, Mc, Kmax, vars, lits);
+}
+
+int32_t rrrmc_check_clauses(int64_t N, int64_t Mc, int64_t Kmax, const int32_t* vars, const int8_t* lits, int64_t* max_conn_out)
+{
+    if (!vars || !lits) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "vars or lits is NULL");
+    std::vector<uint32_t> off;
+    std::vector<SatEntry> ent;
+    int64_t mc = 0;
+    char msg[256];
+    const int rcb = sat_build_program(N, Mc, Kmax, vars, lits, off, ent, &mc, msg, sizeof msg);
+    if (rcb) return fail(nullptr, rcb == 3 ? RRRMC_ERR_UNSUPPORTED : RRRMC_ERR_INVALID_ARG, "%s", msg);
+    if (max_conn_out) *max_conn_out = mc;
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_sat_build(rrrmc_ctx* ctx, int32_t* build_out)
+{
+    if (!ctx || !build_out) return RRRMC_ERR_INVALID_ARG;
+    if (is_multi(ctx)) return rrrmc_sat_build(ctx->kids[0], build_out);
+    if (!is_sat(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_sat_build is for contexts made by rrrmc_ctx_create_sat");
+    *build_out = ctx->sat_build;
+    return RRRMC_OK;
+}
+
+// gen_randomKSAT / choose (SAT.jl:17-56) on the addressed streams: draw n = a K + k; the variable from GRAPH, the literal bit of sorted
+// position k from COUPLING
+int32_t rrrmc_gen_ksat(int64_t N, int64_t K, double alpha, uint64_t seed, int64_t* Mc_out, int32_t* vars_out, int8_t* lits_out)
+{
+    if (!Mc_out) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "Mc_out is NULL");
+    if (N <= 0) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "N must be positive: %lld", (long long)N);                   // SAT.jl:43-46
+    if (K <= 0) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "K must be positive: %lld", (long long)K);
+    if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "alpha must be non-negative: %g", alpha);
+    if (N < K) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "N must not be less than K: %lld < %lld", (long long)N, (long long)K);
+    const double m = std::nearbyint(alpha * (double)N);          // round(Int, α N): ties to even (the default rounding mode)
+    if (!(m < 9.0e15)) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "alpha * N = %g is not a clause count", alpha * (double)N);
+    const int64_t Mc = (int64_t)m;
+    *Mc_out = Mc;
+    if (!vars_out && !lits_out) return RRRMC_OK;
+    if (!vars_out || !lits_out) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "vars_out and lits_out go together");
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    std::vector<int64_t> out((size_t)K);
+    for (int64_t a = 0; a < Mc; ++a) {
+        for (int64_t k = 0; k < K; ++k) {                        // choose, 1-based values
+            const uint64_t n = (uint64_t)(a * K + k);
+            int64_t x = 1 + (int64_t)mulhi64(stream_u64(k0, k1, TAG_GRAPH, n), (uint64_t)(N - k));
+            for (int64_t l = 0; l < k; ++l) if (out[(size_t)l] <= x) x += 1;
+            int64_t l = 0;
+            while (l < k && out[(size_t)l] <= x) ++l;
+            for (int64_t j = k; j > l; --j) out[(size_t)j] = out[(size_t)(j - 1)];
+            out[(size_t)l] = x;
+        }
+        for (int64_t k = 0; k < K; ++k) {
+            vars_out[a * K + k] = (int32_t)(out[(size_t)k] - 1);
+            lits_out[a * K + k] = (int8_t)(stream_u64(k0, k1, TAG_COUPLING, (uint64_t)(a * K + k)) >> 63);
+        }
+    }
+    return RRRMC_OK;
 }
 
 // ---- GraphLocalEntropy: exported entry points (host_le.hpp) ----------------------------------------------------------------------
@@ -1813,9 +1899,10 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                          : model == RRRMC_MODEL_QUANT_COMM_STEP ? RRRMC_RE_SLICE_COMM_STEP : model == RRRMC_MODEL_QUANT_COMM_RELU ? RRRMC_RE_SLICE_COMM_RELU : 0;
     const bool quant = model == RRRMC_MODEL_QUANT_RRG || model == RRRMC_MODEL_QUANT_SK || model == RRRMC_MODEL_QUANT_SKN || model == RRRMC_MODEL_QUANT_F64 || qpat;
     const bool re = model == RRRMC_MODEL_RE_EMPTY || model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_RE_SKN || model == RRRMC_MODEL_RE_PERC_STEP || model == RRRMC_MODEL_RE_PERC_LINEAR ||
-                    model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_RE_COMM_RELU;
+                    model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_RE_COMM_RELU || model == RRRMC_MODEL_RE_SAT;
     const bool le = model == RRRMC_MODEL_LE_EMPTY || model == RRRMC_MODEL_LE_SK || model == RRRMC_MODEL_LE_SKN || model == RRRMC_MODEL_LE_PERC_STEP || model == RRRMC_MODEL_LE_PERC_LINEAR ||
-                    model == RRRMC_MODEL_LE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_RELU;
+                    model == RRRMC_MODEL_LE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_RELU || model == RRRMC_MODEL_LE_SAT;
+    const bool sat = model == RRRMC_MODEL_SAT;
     const bool pc = model == RRRMC_MODEL_PERC_STEP || model == RRRMC_MODEL_PERC_LINEAR;
     const bool cm = model == RRRMC_MODEL_COMM_STEP || model == RRRMC_MODEL_COMM_RELU;
     if (cm && (K < 1 || N % K != 0)) {
@@ -1828,11 +1915,12 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                               : model == RRRMC_MODEL_RE_PERC_LINEAR || model == RRRMC_MODEL_LE_PERC_LINEAR ? RRRMC_RE_SLICE_PERC_LINEAR
                               : model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_STEP ? RRRMC_RE_SLICE_COMM_STEP
                               : model == RRRMC_MODEL_RE_COMM_RELU || model == RRRMC_MODEL_LE_COMM_RELU ? RRRMC_RE_SLICE_COMM_RELU
+                              : model == RRRMC_MODEL_RE_SAT || model == RRRMC_MODEL_LE_SAT ? RRRMC_RE_SLICE_SAT
                                                                                                        : RRRMC_RE_SLICE_EMPTY;
     ctx->model = quant ? RRRMC_MODEL_QUANT_RRG : model; ctx->K = K; ctx->R = R; ctx->replica0 = replica0; ctx->device = device_ids[0];
     ctx->N = quant || re ? N * M : le ? N * (M + 1) : N;
     if (re || le) { ctx->qNk = N; ctx->qM = M; }
-    if (pc) { ctx->qNk = N; ctx->qM = 1; }
+    if (pc || sat) { ctx->qNk = N; ctx->qM = 1; }
     if (cm) { ctx->qNk = N; ctx->qM = 1; ctx->cm_K2 = K; ctx->K = 0; }
     if (quant) { ctx->qNk = N; ctx->qM = M; ctx->q_sk = model == RRRMC_MODEL_QUANT_SK; ctx->q_skn = model == RRRMC_MODEL_QUANT_SKN; ctx->q_spf = model == RRRMC_MODEL_QUANT_F64; ctx->q_pat = qpat; }
     if (qpat >= RRRMC_RE_SLICE_COMM_STEP) { ctx->cm_K2 = K; ctx->K = 0; }
@@ -1849,6 +1937,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : re ? rrrmc_ctx_create_re(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : le ? rrrmc_ctx_create_le(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : pc ? rrrmc_ctx_create_perc(&c, N, model == RRRMC_MODEL_PERC_LINEAR, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : sat ? rrrmc_ctx_create_sat(&c, N, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : cm ? rrrmc_ctx_create_comm(&c, N / K, K, model == RRRMC_MODEL_COMM_RELU, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                                                             : rrrmc_ctx_create(&c, model, N, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0);
         if (rc) {
@@ -2071,6 +2160,7 @@ int32_t rrrmc_rrr_mc_async(rrrmc_ctx* ctx, double beta, double fourK, int64_t it
     if (ctx->model == RRRMC_MODEL_SPARSE_F64) return spf_cont_async(ctx, 0, beta, iters, step, 1.0, staged_thr, staged_thr_fact);
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone perceptron graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone committee machine graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
+    if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone GraphSAT (a DeltaECache of max_conn + 1 levels over variable-degree neighbourhoods): standardMC is, and rrrMC on GraphSATRE / GraphSATLE");
     if (is_re(ctx)) return re_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (is_le(ctx)) return le_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model != RRRMC_MODEL_QUANT_RRG) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not available for model kind %d", ctx->model);
@@ -2086,6 +2176,7 @@ int32_t rrrmc_bkl_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t s
     if (rc) return rc;
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone committee machine graphs (standardMC is)");
+    if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone GraphSAT (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for a GraphQuant over pattern machines (DeltaECacheCont over AllButOne neighbourhoods): rrrMC and standardMC are");
@@ -2128,6 +2219,7 @@ int32_t rrrmc_wtm_mc_async(rrrmc_ctx* ctx, double beta, int64_t samples, double 
     if (rc) return rc;
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone committee machine graphs (standardMC is)");
+    if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone GraphSAT (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for a GraphQuant over pattern machines (rrrMC and standardMC are)");
@@ -2158,6 +2250,7 @@ int32_t rrrmc_extremal_opt_async(rrrmc_ctx* ctx, const double* ftau, int64_t ite
     if (rc) return rc;
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone committee machine graphs (standardMC is)");
+    if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone GraphSAT (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for a GraphQuant over pattern machines (rrrMC and standardMC are)");
@@ -2322,6 +2415,9 @@ int32_t rrrmc_energy_f64(rrrmc_ctx* ctx, double* E_out)
     } else if (is_comm(ctx)) {
         ctx->std_cache_live = false;
         rc = comm_run_init(ctx);
+    } else if (is_sat(ctx)) {
+        ctx->std_cache_live = false;
+        rc = sat_run_init(ctx);
     } else if (is_re(ctx)) {
         if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphRobustEnsemble needs (gamma, beta): call rrrmc_re_set_params first");
         ctx->std_cache_live = false;

@@ -311,6 +311,13 @@ class Engine:
         check(lib().rrrmc_quant_pattern_build(self._ctx, C.byref(b)), self._ctx)
         return b.value
 
+    def sat_build(self):
+        """The kernel build the last standardMC call on a stand-alone GraphSAT ran: 0 = none yet, 1 = one thread per replica, 2 = one
+        wavefront per replica."""
+        b = C.c_int32(-1)
+        check(lib().rrrmc_sat_build(self._ctx, C.byref(b)), self._ctx)
+        return b.value
+
     def spf_team_build(self):
         """(waves, width, slots) of the spf_team_kernel build the default standardMC of a GraphRRGNormal / GraphEANormal launches here;
         zeros when the one-wavefront kernel runs instead."""

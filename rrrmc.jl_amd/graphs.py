@@ -2,6 +2,7 @@
 
 Indices are 0-based here; the Julia glue converts from the reference's 1-based tuples.
 """
+import ctypes as C
 import math
 
 import numpy as np
@@ -734,16 +735,98 @@ class GraphCommReLU(_GraphComm):
     __doc__ += _GraphComm.__doc__
 
 
+class GraphSAT(_DeviceGraph):
+    """``GraphSAT(N, K, α)`` (src/graphs/SAT.jl:117-127): random K-SAT with ``N`` variables and ``M = round(α N)`` clauses of ``K`` distinct
+    variables each; the energy is the number of violated clauses.  ``ET = Int``.  ``A[a]`` holds the variables of clause ``a`` (0-based,
+    ascending) and ``J[a]`` its literal bits: literal k is satisfied iff ``s[A[a][k]] == J[a][k]``.  ``T[i]`` lists the clauses containing
+    ``i`` in clause order, ``neighb[i]`` the other variables of those clauses in order of first appearance, ``max_conn = max |T[i]|``
+    (SAT.jl:86-114).  The reference draws the clauses with an unpinned ``rand``: here ``seed`` names them (``rrrmc_gen_ksat``, host only),
+    and ``from_clauses(N, A, J)`` takes explicit, possibly ragged clauses (1 to 8 literals), as ``GraphSAT(N, A, J)`` does."""
+    model_kind = 33         # RRRMC_MODEL_SAT
+    energy_dtype = np.int64
+    _staged_thr = 0.5
+
+    def _create(self, ctx, R, device, replica0):
+        check(lib().rrrmc_ctx_create_sat(ctx, self.N, R, device, replica0))
+
+    def _upload_couplings(self, ctx):
+        check(lib().rrrmc_set_clauses(ctx, self.M, self.K, self._vars.reshape(-1), self._lits.reshape(-1)), ctx)
+
+    def __init__(self, N, K, alpha, seed=DEFAULT_SEED):
+        N, K = int(N), int(K)
+        Mc = C.c_int64(0)
+        check(lib().rrrmc_gen_ksat(N, K, float(alpha), seed, C.byref(Mc), None, None))
+        vars_ = np.zeros((Mc.value, K), np.int32)
+        lits = np.zeros((Mc.value, K), np.int8)
+        if Mc.value:
+            check(lib().rrrmc_gen_ksat(N, K, float(alpha), seed, C.byref(Mc), vars_.reshape(-1), lits.reshape(-1)))
+        self._init_clauses(N, [r.tolist() for r in vars_], [r.tolist() for r in lits])
+
+    @classmethod
+    def from_clauses(cls, N, A, J):
+        """the graph of explicit clauses: ``A[a]`` the 0-based variables of clause ``a`` in ascending order, ``J[a]`` its 0/1 literal bits"""
+        X = cls.__new__(cls)
+        X._init_clauses(int(N), [[int(i) for i in a] for a in A], [[int(j) for j in ja] for ja in J])
+        return X
+
+    def _init_clauses(self, N, A, J):
+        if len(A) != len(J):
+            raise ValueError("Incompatible lengths of A and J: %d vs %d" % (len(A), len(J)))      # SAT.jl:88
+        if len(A) == 0:
+            raise ValueError("a GraphSAT needs at least one clause")                              # (maximum over an empty collection, SAT.jl:90)
+        for a, (Aa, Ja) in enumerate(zip(A, J)):
+            if len(Aa) != len(Ja):
+                raise ValueError("clause %d: %d variables, %d literal bits" % (a, len(Aa), len(Ja)))
+            if len(Aa) == 0:
+                raise ValueError("clause %d is empty" % a)
+            if any(i < 0 or i >= N for i in Aa):
+                raise ValueError("clause %d: a variable is out of range (N = %d)" % (a, N))
+            if any(x >= y for x, y in zip(Aa, Aa[1:])):
+                raise ValueError("clause %d: the variables must be distinct and in ascending order" % a)
+            if any(j not in (0, 1) for j in Ja):
+                raise ValueError("clause %d: literal bits must be 0 or 1" % a)
+        self.N, self.M, self.K = N, len(A), max(len(a) for a in A)                                # SAT.jl:87-90
+        self.A, self.J = A, J
+        self.T = [[] for _ in range(N)]
+        for a, Aa in enumerate(A):                                                                # SAT.jl:92-97
+            for i in Aa:
+                self.T[i].append(a)
+        self.neighb = [[] for _ in range(N)]
+        for i in range(N):                                                                        # SAT.jl:99-107
+            seen = set()
+            for a in self.T[i]:
+                for j in A[a]:
+                    if j != i and j not in seen:
+                        seen.add(j)
+                        self.neighb[i].append(j)
+        self.max_conn = max(len(t) for t in self.T)
+        self._vars = np.full((self.M, self.K), -1, np.int32)
+        self._lits = np.zeros((self.M, self.K), np.int8)
+        for a, (Aa, Ja) in enumerate(zip(A, J)):
+            self._vars[a, :len(Aa)] = Aa
+            self._lits[a, :len(Ja)] = Ja
+
+    def export_cnf(self, path):
+        """``export_cnf(X, filename)`` (SAT.jl:129-140): DIMACS CNF, variables 1-based, a positive literal where J = 1"""
+        with open(path, "w") as f:
+            f.write("p cnf %d %d\n" % (self.N, self.M))
+            for Aa, Ja in zip(self.A, self.J):
+                f.write("".join("%d " % ((2 * j - 1) * (i + 1)) for j, i in zip(Ja, Aa)) + "0\n")
+
+
 def _ensemble_slice_kind(slice_graph):
+    if isinstance(slice_graph, GraphSAT):
+        return 8            # RRRMC_RE_SLICE_SAT (7 is unassigned)
     return (0 if slice_graph is None else 1 if isinstance(slice_graph, GraphSK) else 2 if isinstance(slice_graph, GraphSKNormal)
             else 3 if isinstance(slice_graph, GraphPercStep) else 4 if isinstance(slice_graph, GraphPercLinear)
             else 5 if isinstance(slice_graph, GraphCommStep) else 6)
 
 
-def _pattern_ensemble(ens, G, sig, args, **kw):
+def _pattern_ensemble(ens, G, sig, args, family=None, **kw):
     """the reference's two signatures (src/REAliases.jl:126-166, src/LEAliases.jl:126-189): (``sig``, M, γ, β) draws the patterns with
-    ``G(sig...; kw...)``, (X, M, γ, β) takes X's"""
-    if isinstance(args[0], G.__base__):
+    ``G(sig...; kw...)``, (X, M, γ, β) takes X's.  ``family``: the class whose instances select the second signature (default: G's base, so
+    that a GraphPercLinear handed to GraphPercStepRE is named in the error instead of being taken for an N)"""
+    if isinstance(args[0], family or G.__base__):
         if len(args) != 4:
             raise TypeError("expected (X, M, γ, β)")
         X, M, gamma, beta = args
@@ -806,6 +889,18 @@ def GraphQCommReLUT(*args, fc=False, seed=DEFAULT_SEED):
     return _pattern_quant(GraphCommReLU, "K1, K2, P", args, fc=fc, seed=seed)
 
 
+def GraphSATRE(*args, seed=DEFAULT_SEED):
+    """``GraphSATRE(N, K, α, M, γ, β)`` / ``GraphSATRE(X::GraphSAT, M, γ, β)`` (src/REAliases.jl:77-92): a Robust Ensemble of M replicas of
+    one K-SAT instance — a replicated constraint-satisfaction problem."""
+    return _pattern_ensemble(GraphRobustEnsemble, GraphSAT, "N, K, α", args, family=GraphSAT, seed=seed)
+
+
+def GraphSATLE(*args, seed=DEFAULT_SEED):
+    """``GraphSATLE(N, K, α, M, γ, β)`` / ``GraphSATLE(X::GraphSAT, M, γ, β)`` (src/LEAliases.jl:77-92): a Local Entropy ensemble of M
+    replicas of one K-SAT instance and a centre."""
+    return _pattern_ensemble(GraphLocalEntropy, GraphSAT, "N, K, α", args, family=GraphSAT, seed=seed)
+
+
 def GraphPercStepRE(*args, seed=DEFAULT_SEED):
     """``GraphPercStepRE(N, P, M, γ, β)`` / ``GraphPercStepRE(X::GraphPercStep, M, γ, β)`` (src/REAliases.jl): a Robust Ensemble of M
     perceptrons that share one pattern matrix."""
@@ -852,16 +947,16 @@ class GraphRobustEnsemble(_DeviceGraph):
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
             raise ValueError("M must be greater than 2, given: %d" % M)                  # RE.jl:37
-        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm)):
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT)):
             raise TypeError("the slices of a GraphRobustEnsemble are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, "
-                            "GraphCommStep or GraphCommReLU")
+                            "GraphCommStep, GraphCommReLU or GraphSAT")
         if slice_graph is not None and slice_graph.N != int(Nk):
             raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
         self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
         self.N = self.Nk * self.M
         self.X1 = slice_graph
         self.slice_kind = _ensemble_slice_kind(slice_graph)
-        self.model_kind = (11, 12, 13, 19, 20, 25, 26)[self.slice_kind]  # RRRMC_MODEL_RE_EMPTY / _SK / _SKN / _PERC_* / _COMM_*
+        self.model_kind = (11, 12, 13, 19, 20, 25, 26, None, 34)[self.slice_kind]  # RRRMC_MODEL_RE_EMPTY / _SK / _SKN / _PERC_* / _COMM_* / _SAT
         self.J = getattr(slice_graph, "J", None)
         self._engine = None                             # the Engine running this graph: REenergies reads the live configuration there
 
@@ -917,9 +1012,9 @@ class GraphLocalEntropy(_DeviceGraph):
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
             raise ValueError("M must be greater than 2, given: %d" % M)                  # LE.jl:24
-        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm)):
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT)):
             raise TypeError("the slices of a GraphLocalEntropy are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, "
-                            "GraphCommStep or GraphCommReLU")
+                            "GraphCommStep, GraphCommReLU or GraphSAT")
         if slice_graph is not None and slice_graph.N != int(Nk):
             raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
         self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
@@ -927,7 +1022,7 @@ class GraphLocalEntropy(_DeviceGraph):
         self.N = self.Nk * (self.M + 1)
         self.X1 = slice_graph
         self.slice_kind = _ensemble_slice_kind(slice_graph)
-        self.model_kind = (14, 15, 16, 21, 22, 27, 28)[self.slice_kind]  # RRRMC_MODEL_LE_EMPTY / _SK / _SKN / _PERC_* / _COMM_*
+        self.model_kind = (14, 15, 16, 21, 22, 27, 28, None, 35)[self.slice_kind]  # RRRMC_MODEL_LE_EMPTY / _SK / _SKN / _PERC_* / _COMM_* / _SAT
         self.J = getattr(slice_graph, "J", None)
         self._engine = None                             # the Engine running this graph: the observables read the live configuration there
 
@@ -1038,6 +1133,8 @@ def getN(X):
 
 def neighbors(X, i):
     """src/Interface.jl:158; RRG.jl:261 (uA = neighbours with non-zero coupling), EA.jl:292 (de-duplicated)."""
+    if isinstance(X, GraphSAT):
+        return np.asarray(X.neighb[i], np.int64)                                                  # SAT.jl:322
     if getattr(X, "model_kind", 0) == 7 and not X.ea_form:
         return X.A[i][X.J[i] != 0]
     return np.unique(X.A[i])
@@ -1045,6 +1142,8 @@ def neighbors(X, i):
 
 def all_delta_e(X):
     """allΔE (src/Interface.jl:200-201): RRG.jl:262-281, EA.jl:293-309 — sorted values of |dE|."""
+    if isinstance(X, GraphSAT):
+        return tuple(range(X.max_conn + 1))                                                       # SAT.jl:325
     K = X.K
     if getattr(X, "model_kind", 0) == 7:
         es = {0}

@@ -6,6 +6,8 @@
   python tools/bench_models.py perc [R ...] GraphPercStepRE / GraphPercStepLE(1001, 400, 5) and GraphPercStep(1001, 400): the same three legs
   python tools/bench_models.py comm [R ...] GraphCommStepRE / LE(201, 5, 400, 5), GraphCommReLURE / LE(168, 6, 400, 5) and the two
                                             stand-alone graphs: the same legs
+  python tools/bench_models.py sat [R ...]  GraphSAT(1000, 3, 4.2), β = 2: standardMC through the wave and the thread build
+  python tools/bench_models.py satre [R ...] GraphSATRE(1001, 3, 4.2, 5) beside GraphPercStepRE(1001, 400, 5): rrrMC, both builds
 """
 import json
 import os
@@ -339,6 +341,66 @@ def bench_comm(P=400, M=5, gamma=2.0, beta=0.4, iters=1 << 14, step=1 << 12, see
             print(json.dumps(out), flush=True)
 
 
+def _timed_legs(pkg, X, R, legs, envs, beta, it, step, seed, reps):
+    """one warm-up call and `reps` timed calls per leg (name, env, sampler), each continuing from the configuration the last one left: the
+    median and the (min, max) of the sampler kernel's rate (HIP events around the kernel), the acceptance of the last call"""
+    out = {}
+    for name, env, rrr in legs:
+        for k in envs:
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        eng = pkg.Engine(X, R)
+        eng.seed(seed)
+        eng.init_spins_random()
+        rates, call_rates = [], []
+        for rep in range(reps + 1):
+            res = eng.rrr_mc(beta, it, step) if rrr else eng.standard_mc(beta, it, step)
+            total_ms, sweep_ms, _ = eng.last_timing()
+            if rep:
+                rates.append(float(R) * it / (sweep_ms * 1e-3))
+                call_rates.append(float(R) * it / (total_ms * 1e-3))
+        # call_iterations_per_s: the events around the WHOLE call on the device — the energy / cache set-up of a fresh call and the layout
+        # copies around the sampler kernel (the ensembles' slice-major copies, the SAT thread build's two transposes) included
+        out[name] = {"kernel_iterations_per_s": float(np.median(rates)), "min": min(rates), "max": max(rates),
+                     "call_iterations_per_s": float(np.median(call_rates)),
+                     "acceptance": float(res[1].mean()) / it, "energy_per_spin": float(res[0][:, -1].mean()) / X.N}
+        if not rrr and hasattr(X, "max_conn"):
+            out[name]["build"] = eng.sat_build()
+        eng.close()
+    for k in envs:
+        os.environ.pop(k, None)
+    return out
+
+
+def bench_sat(N=1000, K=3, alpha=4.2, beta=2.0, iters=1 << 16, step=1 << 12, seed=0x5EED, reps=3):
+    """GraphSAT(1000, 3, 4.2) under standardMC at β = 2 through both builds (one wavefront per replica, one thread per replica), kernel
+    iterations/s per replica count: python tools/bench_models.py sat 8 256 2048 8192"""
+    pkg = entry.load_package()
+    X = pkg.GraphSAT(N, K, alpha, seed=seed)
+    envs = ("RRRMC_SAT_NO_WAVE", "RRRMC_SAT_WAVE")
+    for R in ([int(a) for a in sys.argv[2:]] or [8, 256, 2048, 8192]):
+        it = max(step, iters * 2048 // max(R, 2048))
+        out = {"model": "GraphSAT", "N": N, "K": K, "alpha": alpha, "clauses": X.M, "max_conn": X.max_conn, "beta": beta, "replicas": R, "iters": it}
+        out.update(_timed_legs(pkg, X, R, (("wave", {"RRRMC_SAT_WAVE": "1"}, False), ("thread", {"RRRMC_SAT_NO_WAVE": "1"}, False)), envs,
+                               beta, it, step, seed, reps))
+        print(json.dumps(out), flush=True)
+
+
+def bench_satre(Nk=1001, K=3, alpha=4.2, P=400, M=5, gamma=2.0, beta=0.4, iters=1 << 14, step=1 << 12, seed=0x5EED, reps=3):
+    """GraphSATRE(1001, 3, 4.2, 5) beside GraphPercStepRE(1001, 400, 5) (γ = 2, β = 0.4: bench_perc's point) under rrrMC through the thread and
+    the LDS build, kernel iterations/s per chain count: python tools/bench_models.py satre 8 4096"""
+    pkg = entry.load_package()
+    envs = ("RRRMC_RE_NO_LDS", "RRRMC_RE_LDS")
+    legs = (("rrr_thread", {"RRRMC_RE_NO_LDS": "1"}, True), ("rrr_lds", {"RRRMC_RE_LDS": "1"}, True), ("rrr_default", {}, True))
+    for R in ([int(a) for a in sys.argv[2:]] or [8, 4096]):
+        it = max(step, iters * 1024 // max(R, 1024))
+        for model, X in (("GraphSATRE", pkg.GraphSATRE(Nk, K, alpha, M, gamma, beta, seed=seed)),
+                         ("GraphPercStepRE", pkg.GraphPercStepRE(Nk, P, M, gamma, beta, seed=seed))):
+            out = {"model": model, "Nk": Nk, "M": M, "gamma": gamma, "beta": beta, "replicas": R, "iters": it}
+            out.update(_timed_legs(pkg, X, R, legs, envs, beta, it, step, seed, reps))
+            print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "sk"
-    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm}[which]()
+    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm, "sat": bench_sat, "satre": bench_satre}[which]()
