@@ -205,6 +205,12 @@ RRRMC_API int32_t rrrmc_standard_mc_async(rrrmc_ctx *ctx, double beta, int64_t i
 RRRMC_API int32_t rrrmc_sync(rrrmc_ctx *ctx);
 /* Results of the last (a)sync sampling call: Es_out[R * nsamples] replica-major, accepted_out[R]. */
 RRRMC_API int32_t rrrmc_fetch_results(rrrmc_ctx *ctx, int64_t *Es_out, int64_t *accepted_out);
+/* The build of the LDS-resident sweep kernel the last standardMC call on a sparse +-J context launched: -1 = none yet (or the call took
+ * another kernel: graphs beyond LDS), 0 = the generic kernel, else the zero-block pattern the build is specialised for, two bits per
+ * class of dE > 0, class 0 lowest: the number of leading four-plane blocks of that class's acceptance threshold the build takes as
+ * zero (beta = 1 at K = 3: 2 = two blocks of class 0, none of class 1).  RRRMC_SWEEP_GENERIC=1 in the environment of a call selects the
+ * generic kernel.  Multi-device contexts report their first shard. */
+RRRMC_API int32_t rrrmc_sweep_build(rrrmc_ctx *ctx, int32_t *build_out);
 
 /* ---- colour-parallel ("checkerboard") sweeps: build-defined extension for large sparse graphs ---------------------
  * The reference's standardMC is random-site (src/RRRMC.jl:113) and its kernel here keeps a replica group's spins in

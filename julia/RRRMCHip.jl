@@ -301,6 +301,12 @@ function Ctx(X::RRRMC.SAT.GraphSAT, R::Integer; device = 0, replica0 = 0, device
     end
     return set_patterns!(Ctx(ref[], R, X.N, true), X)
 end
+# which build of the sweep kernel the last standardMC call on a sparse +-J graph launched: -1 none, 0 generic, else its zero-block pattern
+function sweep_build(ctx::Ctx)
+    b = Ref{Int32}(0)
+    check(ccall((:rrrmc_sweep_build, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), ctx.p, b), ctx.p)
+    return Int(b[])
+end
 # which kernel ran the last standardMC call on a stand-alone GraphSAT: 0 none yet, 1 one thread per replica, 2 one wavefront per replica
 function sat_build(ctx::Ctx)
     b = Ref{Int32}(0)

@@ -2,10 +2,12 @@
 // with g++ -fsanitize=address,undefined, into tests/host_sanitize.cpp (sanitizers on the CPU build only).
 //   ChunkDesc / plan_chunk_list   how the iterations of a standardMC call are cut into chunks and batches
 //   threshold64                   ceil(p 2^64): the acceptance thresholds of the bit-plane comparison
+//   zero_blocks / zero_pattern    leading all-zero blocks of the +-J thresholds: which specialised sweep kernel a launch may take
 //   shard_bounds                  the replica shards of a multi-device context
 #pragma once
 #include <stdint.h>
 
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -92,6 +94,42 @@ inline uint64_t threshold64(double p, bool* always)
     const int s = -sh;
     if (s >= 64) return 1;
     return (man + ((1ull << s) - 1)) >> s;
+}
+
+// Leading zero blocks of the +-J thresholds.  Class n (unsatisfied bonds) of a K-regular +-J model has dE = 2 (K - 2n) and the threshold
+// T_n = threshold64(exp(-beta dE)); the producers compare four bit planes (one Philox block) at a time, most significant first.
+// zb[n], n < (K + 1) / 2 = number of LEADING blocks, 0 .. nblocks, whose four planes of T_n are all zero: there the comparison needs no
+// threshold at all (sparse_kernels.hpp: refine_block_zb).  A class that is always accepted counts as 0 (generic): its eq mask is 0 anyway.
+inline int zero_blocks_of(uint64_t T, bool always, int nblocks)
+{
+    int b = 0;
+    while (!always && b < nblocks && b < 16 && ((T >> (60 - 4 * b)) & 0xfull) == 0) ++b;
+    return b;
+}
+inline void zero_blocks(double beta, int K, int nblocks, int* zb)
+{
+    for (int n = 0; n < (K + 1) / 2; ++n) {
+        bool always;
+        const uint64_t T = threshold64(std::exp(-beta * (2.0 * (double)(K - 2 * n))), &always);
+        zb[n] = zero_blocks_of(T, always, nblocks);
+    }
+}
+// ... packed two bits per class, as the ZB parameter of sweep_kernel takes it: a field holds 0 .. 3 and the word four classes, so
+// nblocks <= kZeroPatternMaxBlocks and K <= kZeroPatternMaxK (the callers' static_asserts); beyond either the pattern is 0 = generic
+constexpr int kZeroPatternMaxBlocks = 3, kZeroPatternMaxK = 8;
+inline uint32_t zero_pattern(double beta, int K, int nblocks)
+{
+    if (K < 1 || K > kZeroPatternMaxK || nblocks > kZeroPatternMaxBlocks) return 0u;
+    int zb[4] = {0, 0, 0, 0};
+    zero_blocks(beta, K, nblocks, zb);
+    return (uint32_t)zb[0] | ((uint32_t)zb[1] << 2) | ((uint32_t)zb[2] << 4) | ((uint32_t)zb[3] << 6);
+}
+// a kernel built for pattern `have` is right for a launch of pattern `want` iff it assumes no more zero blocks than there are, class by class
+inline bool zero_pattern_covers(uint32_t want, uint32_t have)
+{
+    for (int n = 0; n < 4; ++n)
+        if (((have >> (2 * n)) & 3u) > ((want >> (2 * n)) & 3u)) return false;
+    return true;
 }
 
 // shard d of ndev over R replicas: whole 32-replica groups in global-id order (the last shard takes the ragged tail); b1 <= b0 = empty

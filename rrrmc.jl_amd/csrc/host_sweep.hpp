@@ -158,6 +158,13 @@ int32_t pm1_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_
     P.gbase = ctx->it_done;
     P.N = (int)N; P.C = C; P.TS = ctx->TS; P.Rpad = (int)ctx->Rpad;
     sweep_fn fn = ctx->lds_mode ? sweep_for_K((int)K, ctx->sweep_mode) : nullptr;
+    ctx->sweep_build = -1;
+    if (ctx->lds_mode) {
+        // thresholds with leading zero blocks: a build that skips them (the pattern comes from the same exp / threshold64 as the planes above)
+        uint32_t zb_have = 0u;
+        if (sweep_fn fz = sweep_zb_for((int)K, ctx->sweep_mode, zero_pattern(beta, (int)K, kSwBlocks), &zb_have)) fn = fz;
+        ctx->sweep_build = (int)zb_have;
+    }
     BigSweepParams PB{};
     BigMaskParams PM{};
     if (ctx->big_masks) {

@@ -142,6 +142,7 @@ struct rrrmc_ctx {
     bool wide = false;                  // the neighbour table stays in HBM/L2 (longer chunks; needed for 8192 < N)
     bool big_bufs_ready = false;        // ensure_big_buffers has run
     bool big_mode = false;              // N does not fit LDS: random-site standardMC through plan_big_kernel / big_sweep_kernel (spins in HBM/L2)
+    int sweep_build = -1;               // rrrmc_sweep_build: zero-block pattern of the sweep kernel the last standardMC call launched (0 generic, -1 none)
     int sweep_mode = 0;                 // sweep_kernel<K, MODE>: 0 LDS table / byte offsets, 1 HBM table / byte offsets, 2 HBM table / word indices
     int ncolors = 0;
     std::vector<int32_t> color_count;   // sites per colour
@@ -411,6 +412,39 @@ sweep_fn sweep_for_K(int K, int mode)
         case 29: return sweep_kernel<5, 3>; case 30: return sweep_kernel<6, 3>; case 31: return sweep_kernel<7, 3>;
         default: return nullptr;
     }
+}
+
+// Builds of sweep_kernel specialised for thresholds whose leading blocks are zero (host_plan.hpp: zero_pattern; two bits per class, class
+// 0 lowest).  K = 3 only — GraphRRG at K = 3 is the headline, and the only shape the gain has been measured at — in the two modes its
+// contexts take up to N = 8192, at every pattern K = 3 has: (1, 0) from beta = 0.47, (2, 0) from 0.93 (the headline's beta = 1), (3, 1) from
+// 1.39, (3, 2) from 2.78, (3, 3) from 4.16.  A launch takes the build that assumes the most zero blocks without assuming one the launch does
+// not have (a block compared the generic way is right whatever its planes hold); a launch no build fits — (0, 0), every other K, MODE 2
+// and 3 — runs the generic kernel.
+struct SweepZbBuild { int K, mode; uint32_t zb; sweep_fn fn; };
+#define RRRMC_ZB(c0, c1) ((uint32_t)(c0) | ((uint32_t)(c1) << 2))
+#define RRRMC_ZB_K3(mode, c0, c1) {3, mode, RRRMC_ZB(c0, c1), sweep_kernel<3, mode, RRRMC_ZB(c0, c1)>}
+const SweepZbBuild kSweepZbBuilds[] = {
+    RRRMC_ZB_K3(1, 1, 0), RRRMC_ZB_K3(1, 2, 0), RRRMC_ZB_K3(1, 3, 1), RRRMC_ZB_K3(1, 3, 2), RRRMC_ZB_K3(1, 3, 3),
+    RRRMC_ZB_K3(0, 1, 0), RRRMC_ZB_K3(0, 2, 0), RRRMC_ZB_K3(0, 3, 1), RRRMC_ZB_K3(0, 3, 2), RRRMC_ZB_K3(0, 3, 3),
+};
+#undef RRRMC_ZB_K3
+#undef RRRMC_ZB
+// the build for a launch of pattern `want` (nullptr: none — the generic kernel); RRRMC_SWEEP_GENERIC=1 (tests, timing experiments) takes the
+// generic kernel whatever the pattern.  The environment is read at every call: a test switches between two calls of one context.
+sweep_fn sweep_zb_for(int K, int mode, uint32_t want, uint32_t* zb_out)
+{
+    *zb_out = 0u;
+    if (const char* e = std::getenv("RRRMC_SWEEP_GENERIC"); e && e[0] == '1') return nullptr;
+    const SweepZbBuild* best = nullptr;
+    int best_n = 0;
+    for (const SweepZbBuild& b : kSweepZbBuilds) {
+        if (b.K != K || b.mode != mode || !zero_pattern_covers(want, b.zb)) continue;
+        int n = 0;
+        for (int c = 0; c < 4; ++c) n += (int)((b.zb >> (2 * c)) & 3u);
+        if (n > best_n) { best = &b; best_n = n; }
+    }
+    if (best) *zb_out = best->zb;
+    return best ? best->fn : nullptr;
 }
 
 // wide = the neighbour table is not staged in LDS (8192 < N: offsets are word indices, see SweepParams::table)
@@ -883,6 +917,8 @@ int32_t rrrmc_ctx_create(rrrmc_ctx** out, int32_t model, int64_t N, int64_t K, i
     if (ctx->lds_mode) {
         sweep_fn fn = sweep_for_K((int)K, ctx->sweep_mode);
         CREATE_TRY(raise_lds_attr(reinterpret_cast<const void*>(fn), ctx->lds_bytes));
+        for (const SweepZbBuild& zb : kSweepZbBuilds)
+            if (zb.K == (int)K && zb.mode == ctx->sweep_mode) CREATE_TRY(raise_lds_attr(reinterpret_cast<const void*>(zb.fn), ctx->lds_bytes));
         CREATE_TRY(raise_lds_attr(reinterpret_cast<const void*>(plan_for_K((int)K)), ctx->plan_lds_bytes));
     }
     if (ctx->big_mode)
@@ -1745,6 +1781,15 @@ int32_t rrrmc_check_clauses(int64_t N, int64_t Mc, int64_t Kmax, const int32_t* 
     const int rcb = sat_build_program(N, Mc, Kmax, vars, lits, off, ent, &mc, msg, sizeof msg);
     if (rcb) return fail(nullptr, rcb == 3 ? RRRMC_ERR_UNSUPPORTED : RRRMC_ERR_INVALID_ARG, "%s", msg);
     if (max_conn_out) *max_conn_out = mc;
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_sweep_build(rrrmc_ctx* ctx, int32_t* build_out)
+{
+    if (!ctx || !build_out) return RRRMC_ERR_INVALID_ARG;
+    if (is_multi(ctx)) return rrrmc_sweep_build(ctx->kids[0], build_out);
+    if (ctx->model != RRRMC_MODEL_SPARSE_PM1) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_sweep_build is for sparse +-J contexts");
+    *build_out = ctx->sweep_build;
     return RRRMC_OK;
 }
 

@@ -315,8 +315,50 @@ __device__ __forceinline__ void refine_block(uint32_t (&lt)[NT], uint32_t (&eq)[
     }
 }
 
+// Zero-block form of refine_block.  At low temperature the leading planes of a threshold are zero for the whole launch (T_n =
+// exp(-beta dE) 2^64 is small): on a block whose four planes of T_n are all zero, x is identically 0 and eq only keeps the replicas
+// whose four u bits are zero as well — eq &= ~(w0 | w1 | w2 | w3), two instructions (the OR of the first three words is shared by the
+// classes) where the generic form spends eight and its share of the ORs into lt.  ZB packs, two bits per class, the number of LEADING
+// blocks of the class that are zero (host: zero_blocks / zero_pattern in host_plan.hpp); block pb of class n takes this form when
+// pb < ((ZB >> 2n) & 3), a compile-time choice — run-time tests per threshold bit cost far more than they save.
+// ZB = 0 is refine_block itself.
+static_assert(kSwBlocks <= kZeroPatternMaxBlocks && kMaxK <= kZeroPatternMaxK, "ZB packs two bits per class and four classes (host_plan.hpp: zero_pattern)");
+template <int NT, uint32_t ZB, uint32_t PB>
+__device__ __forceinline__ void refine_block_zb(uint32_t (&lt)[NT], uint32_t (&eq)[NT], const Philox4& o, const uint32_t* __restrict__ taum)
+{
+    static_assert(NT <= 4 && (ZB >> (2 * NT)) == 0u, "one two-bit field per class");
+    if constexpr (ZB == 0u) refine_block<NT>(lt, eq, o, PB, taum);
+    else {
+        const uint32_t w012 = bitop3<0xfe>(o.w[0], o.w[1], o.w[2]);
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            if (PB < ((ZB >> (2 * n)) & 3u)) eq[n] = bitop3<0x10>(eq[n], w012, o.w[3]);      // eq & ~(w0 | w1 | w2) & ~w3; lt untouched
+            else {
+                uint32_t x[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t tm = taum[(PB * 4 + j) * 4 + n];
+                    x[j] = bitop3<0x20>(eq[n], o.w[j], tm);
+                    eq[n] = bitop3<0x90>(eq[n], o.w[j], tm);
+                }
+                lt[n] = (lt[n] | x[0] | x[1]) | (x[2] | x[3]);      // (as v_bitop3_b32 0xfe these ORs measured the same: profiles/r07/producer_diet.md)
+            }
+        }
+    }
+}
+
+template <int NT, uint32_t ZB, int B0, int B1>
+__device__ __forceinline__ void refine_eager(uint32_t (&lt)[NT], uint32_t (&eq)[NT], uint32_t k0, uint32_t k1, uint64_t g, uint32_t group,
+                                             const uint32_t* __restrict__ taum)
+{
+    if constexpr (B0 < B1) {
+        refine_block_zb<NT, ZB, (uint32_t)B0>(lt, eq, accept_planes(k0, k1, g, group, (uint32_t)B0), taum);
+        refine_eager<NT, ZB, B0 + 1, B1>(lt, eq, k0, k1, g, group, taum);
+    }
+}
+
 // ---- producers -------------------------------------------------------------------------------------
-template <int K, int MODE>
+template <int K, int MODE, uint32_t ZB = 0u>
 __device__ __forceinline__ void produce_chunk(const SweepParams& P, const ChunkDesc& cd, uint4* __restrict__ desc,
                                               const uint16_t* __restrict__ tbl, const LeftList& left, int pw, int lane, uint32_t group,
                                               const uint32_t (&slots)[kProducerTasksMax])
@@ -370,8 +412,12 @@ __device__ __forceinline__ void produce_chunk(const SweepParams& P, const ChunkD
         // does not depend on its unluckiest lane.
         // fully unrolled: the block index is a compile-time constant, so the threshold words are loop-invariant scalars
         uint32_t pb = 0;
+        if constexpr (ZB == 0u) {
 #pragma unroll
-        for (int b = 0; b < kSwBlocks; ++b) refine_block<NT>(lt, eq, accept_planes(P.k0, P.k1, g, group, (uint32_t)b), (uint32_t)b, P.taum);
+            for (int b = 0; b < kSwBlocks; ++b) refine_block<NT>(lt, eq, accept_planes(P.k0, P.k1, g, group, (uint32_t)b), (uint32_t)b, P.taum);
+        } else {
+            refine_eager<NT, ZB, 0, kSwBlocks>(lt, eq, P.k0, P.k1, g, group, P.taum);      // (the list-full loop below and the fix tasks stay generic)
+        }
         pb = (uint32_t)kSwBlocks;
         bool need = any_set<NT>(eq);
         const unsigned long long bal = __ballot(need);
@@ -894,7 +940,8 @@ __device__ __forceinline__ void tally_chunk(TallyState<NS>& t, const ChunkDesc& 
     if (base < count) tally_group<NS, K, true>(t, tal, base, count, lane);
 }
 
-template <int K, int MODE = 0>
+// ZB: zero-block pattern of the thresholds this build is specialised for (refine_block_zb); 0 = the generic kernel, right for any launch
+template <int K, int MODE = 0, uint32_t ZB = 0u>
 __global__ __launch_bounds__(kSweepThreads) void sweep_kernel(SweepParams P)
 {
     constexpr int NQ = SweepCfg<K>::NQ, NS = SweepCfg<K>::NS;
@@ -1057,7 +1104,7 @@ __global__ __launch_bounds__(kSweepThreads) void sweep_kernel(SweepParams P)
 #ifndef RRRMC_ABLATE_PRODUCE
             if constexpr (kSwLeftMax > 2 * kWave)
                 if (c >= 1 && c - 1 < P.nchunks) fix_tasks<K>(P, cdp, desc + ((c - 1) % 3) * NQ * C, left_list(c - 1), lane, group, 1 + pw);
-            if (c < P.nchunks) produce_chunk<K, MODE>(P, cd0, desc + (c % 3) * NQ * C, tbl, left_list(c), pw, lane, group, sl0);
+            if (c < P.nchunks) produce_chunk<K, MODE, ZB>(P, cd0, desc + (c % 3) * NQ * C, tbl, left_list(c), pw, lane, group, sl0);
 #endif
             RRRMC_T1
             __syncthreads();

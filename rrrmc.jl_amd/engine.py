@@ -311,6 +311,13 @@ class Engine:
         check(lib().rrrmc_quant_pattern_build(self._ctx, C.byref(b)), self._ctx)
         return b.value
 
+    def sweep_build(self):
+        """The build of the LDS-resident sweep kernel the last standardMC call on a sparse +-J graph launched: -1 = none, 0 = the generic
+        kernel, else the zero-block pattern it is specialised for (two bits per class: leading all-zero blocks of the threshold)."""
+        b = C.c_int32(-2)
+        check(lib().rrrmc_sweep_build(self._ctx, C.byref(b)), self._ctx)
+        return b.value
+
     def sat_build(self):
         """The kernel build the last standardMC call on a stand-alone GraphSAT ran: 0 = none yet, 1 = one thread per replica, 2 = one
         wavefront per replica."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cycle-weighted VALU utilisation model of sweep_kernel<3, 1> (the roofline that binds: the replica state never leaves LDS).
+"""Cycle-weighted VALU utilisation model of sweep_kernel<3, 1, 2u> — the headline's build: MODE 1, zero-block pattern (2, 0) of beta = 1 — (the roofline that binds: the replica state never leaves LDS).
 
   python tools/valu_model.py         (in the build container: hipcc cross-compiles; reads the committed rocprofv3 / ubench outputs)
 
@@ -41,11 +41,11 @@ def kernel_isa():
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "sw.hip")
         open(src, "w").write('#include "%s/rrrmc.jl_amd/csrc/sparse_kernels.hpp"\n'
-                             'template __global__ void rrrmc::sweep_kernel<3, 1>(rrrmc::SweepParams);\n' % ROOT)
+                             'template __global__ void rrrmc::sweep_kernel<3, 1, 2u>(rrrmc::SweepParams);\n' % ROOT)
         out = os.path.join(d, "sw.s")
         subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-w", "-o", out, src])
         lines = open(out).read().splitlines()
-    start = next(i for i, l in enumerate(lines) if l.startswith("_ZN5rrrmc12sweep_kernelILi3ELi1EEEvNS_11SweepParamsE:"))
+    start = next(i for i, l in enumerate(lines) if l.startswith("_ZN5rrrmc12sweep_kernelILi3ELi1ELj2EEEvNS_11SweepParamsE:"))
     end = next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])
     return [l.strip() for l in lines[start:end + 1]]
 
@@ -88,9 +88,12 @@ def cost_ns(op, ns):
 
 def pmc():
     txt = open(prof_file(SUMMARY)).read()
-    blk = lambda tag: txt[txt.index("[%s] void rrrmc::sweep_kernel<3, 1>" % tag):]
+    if "sweep_kernel<3, 1, 2u>" not in txt:
+        sys.exit("valu_model.py: %s has no counters of sweep_kernel<3, 1, 2u> (the headline's build): it was taken on another build of the "
+                 "kernel — run tools/profile_gpu.sh on this tree first" % prof_file(SUMMARY))
+    blk = lambda tag: txt[txt.index("[%s] void rrrmc::sweep_kernel<3, 1, 2u>" % tag):]
     val = lambda tag, name: float(re.search(r"%s\s+avg=([\d.e+]+)" % name, blk(tag)).group(1))
-    ns = float(re.search(r"sweep_kernel<3, 1>\(rrrmc::SweepParams\)\s+n=\d+ avg_ns=(\d+)", txt).group(1))
+    ns = float(re.search(r"sweep_kernel<3, 1, 2u>\(rrrmc::SweepParams\)\s+n=\d+ avg_ns=(\d+)", txt).group(1))
     return {"SQ_INSTS_VALU": val("pmc_sq", "SQ_INSTS_VALU"), "SQ_INSTS_SALU": val("pmc_sq", "SQ_INSTS_SALU"), "SQ_INSTS_LDS": val("pmc_sq", "SQ_INSTS_LDS"),
             "GRBM_GUI_ACTIVE": val("pmc_lds", "GRBM_GUI_ACTIVE"), "FETCH_SIZE_KB": val("pmc_fetch", "FETCH_SIZE"), "WRITE_SIZE_KB": val("pmc_write", "WRITE_SIZE"),
             "rocprof_avg_ns": ns}
@@ -117,7 +120,7 @@ def main():
     P = pmc()
     clock_hz = P["GRBM_GUI_ACTIVE"] / 8.0 / (P["rocprof_avg_ns"] * 1e-9)          # GRBM_GUI_ACTIVE sums the 8 XCDs
     mean_ns = task_ns / n_valu
-    model = {"kernel": "sweep_kernel<3, 1>", "simds": SIMDS, "valu_insts_per_launch": P["SQ_INSTS_VALU"], "clock_hz": clock_hz,
+    model = {"kernel": "sweep_kernel<3, 1, 2u>", "simds": SIMDS, "valu_insts_per_launch": P["SQ_INSTS_VALU"], "clock_hz": clock_hz,
              "mean_issue_ns": mean_ns, "mean_issue_cycles": mean_ns * 1e-9 * clock_hz,
              "producer_task": {"valu_wave_insts": n_valu, "issue_ns_per_simd": task_ns, "mix": dict(tvalu.most_common())},
              "pmc": P,
@@ -149,7 +152,7 @@ def main():
     traffic.update(provenance())
     json.dump(traffic, open(os.path.join(PROF, "traffic.json"), "w"), indent=1)
     with open(os.path.join(PROF, "sweep31_isa_hist.txt"), "w") as f:
-        f.write("# opcode histogram of sweep_kernel<3, 1> (hipcc -O3 --offload-arch=gfx950 -S), static counts\n")
+        f.write("# opcode histogram of sweep_kernel<3, 1, 2u> (hipcc -O3 --offload-arch=gfx950 -S), static counts\n")
         f.write("# whole kernel: %d instructions\n" % len(insts))
         for o, c in whole.most_common():
             f.write("%6d %s\n" % (c, o))
