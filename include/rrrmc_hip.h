@@ -101,7 +101,13 @@ enum rrrmc_model {
        src/LEAliases.jl:77-92): made by rrrmc_ctx_create_re / _le with RRRMC_RE_SLICE_SAT; selectors of rrrmc_ctx_create_multi (N = Nk, M) */
     RRRMC_MODEL_SAT = 33,      /* GraphSAT(N, K, alpha): energy = the number of violated clauses (reported as Float64) */
     RRRMC_MODEL_RE_SAT = 34,   /* GraphSATRE */
-    RRRMC_MODEL_LE_SAT = 35    /* GraphSATLE */
+    RRRMC_MODEL_LE_SAT = 35,   /* GraphSATLE */
+    /* the third committee machine (src/graphs/CommQu.jl): GraphCommQu by rrrmc_ctx_create_comm_qu, its ensembles by rrrmc_ctx_create_re / _le
+       with RRRMC_RE_SLICE_COMM_QU, its GraphQuant by rrrmc_ctx_create_quant_pattern; selectors of rrrmc_ctx_create_multi as their siblings */
+    RRRMC_MODEL_COMM_QU = 36,        /* GraphCommQu(K1, K2, P): energy = the number of misclassified patterns (reported as Float64) */
+    RRRMC_MODEL_RE_COMM_QU = 37,     /* GraphCommQuRE */
+    RRRMC_MODEL_LE_COMM_QU = 38,     /* GraphCommQuLE */
+    RRRMC_MODEL_QUANT_COMM_QU = 39   /* GraphQCommQuT (the contexts report RRRMC_MODEL_QUANT_RRG) */
 };
 
 /* slice families of rrrmc_ctx_create_re */
@@ -114,7 +120,8 @@ enum rrrmc_re_slice {
     RRRMC_RE_SLICE_COMM_STEP = 5,   /* GraphCommStep (src/graphs/CommStep.jl): patterns with rrrmc_set_comm_patterns; Nk = K1*K2, K1, K2 odd */
     RRRMC_RE_SLICE_COMM_RELU = 6,   /* GraphCommReLU (src/graphs/CommReLU.jl): patterns and labels with rrrmc_set_comm_patterns; K1, K2 even */
     /* 7 is unassigned: rrrmc_ctx_create_re / _le refuse it with RRRMC_ERR_INVALID_ARG */
-    RRRMC_RE_SLICE_SAT = 8          /* GraphSAT (src/graphs/SAT.jl): clauses with rrrmc_set_clauses */
+    RRRMC_RE_SLICE_SAT = 8,         /* GraphSAT (src/graphs/SAT.jl): clauses with rrrmc_set_clauses */
+    RRRMC_RE_SLICE_COMM_QU = 9      /* GraphCommQu (src/graphs/CommQu.jl): patterns and labels with rrrmc_set_comm_patterns; K1, K2 even */
 };
 
 /* Library ABI version (major*10000 + minor*100 + patch). */
@@ -159,7 +166,7 @@ RRRMC_API int32_t rrrmc_ctx_create(rrrmc_ctx **out, int32_t model, int64_t N, in
  *          (N = Nk, M) as rrrmc_ctx_create_quant_sk / _skn do (K ignored), RRRMC_MODEL_QUANT_F64 takes (N = Nk, K, M) as rrrmc_ctx_create_quant_f64,
  *          RRRMC_MODEL_RE_EMPTY / _SK / _SKN take (N = Nk, M) as rrrmc_ctx_create_re does (K ignored), RRRMC_MODEL_LE_EMPTY / _SK / _SKN
  *          take (N = Nk, M) as rrrmc_ctx_create_le does (K ignored), and so do RRRMC_MODEL_RE_PERC_* / RRRMC_MODEL_LE_PERC_* and
- *          RRRMC_MODEL_RE_COMM_* / RRRMC_MODEL_LE_COMM_*; RRRMC_MODEL_COMM_STEP / _RELU take (N = K1*K2, K = K2) as rrrmc_ctx_create_comm does;
+ *          RRRMC_MODEL_RE_COMM_* / RRRMC_MODEL_LE_COMM_*; RRRMC_MODEL_COMM_STEP / _RELU / _QU take (N = K1*K2, K = K2) as rrrmc_ctx_create_comm / _comm_qu do;
  *          RRRMC_MODEL_PERC_STEP / _LINEAR take N as rrrmc_ctx_create_perc does; M is ignored otherwise.
  */
 RRRMC_API int32_t rrrmc_ctx_create_multi(rrrmc_ctx **out, int32_t model, int64_t N, int64_t K, int64_t M, int64_t R,
@@ -279,10 +286,10 @@ RRRMC_API int32_t rrrmc_ctx_create_quant_skn(rrrmc_ctx **out, int64_t Nk, int64_
  * the generic caches over all Nk * M spins — rrrmc_bkl_mc_async, rrrmc_wtm_mc_async, rrrmc_extremal_opt_async (neighbors = the two Trotter
  * neighbours, then the slice graph's, QT.jl:288-321); one thread per replica.  rrrmc_quant_observables is not wired for these slices. */
 RRRMC_API int32_t rrrmc_ctx_create_quant_f64(rrrmc_ctx **out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0);
-/* GraphQuant over M pattern machines that share one pattern matrix — GraphQPercStepT, GraphQPercLinearT, GraphQCommStepT, GraphQCommReLUT
- * (src/QAliases.jl:85-159).  slice_kind is RRRMC_RE_SLICE_PERC_STEP / _PERC_LINEAR / _COMM_STEP / _COMM_RELU; Nk synapses per slice, for the
- * committee machines Nk = K1*K2 (K2 is ignored for the perceptrons).  RRRMC_ERR_INVALID_ARG: Nk even (perceptrons); K1, K2 even (step) or odd
- * (ReLU), Nk not a multiple of K2; M <= 2 (QT.jl:47).  RRRMC_ERR_UNSUPPORTED: Nk > 32767, N = Nk*M > 65535.  Then rrrmc_set_patterns
+/* GraphQuant over M pattern machines that share one pattern matrix — GraphQPercStepT, GraphQPercLinearT, GraphQCommStepT, GraphQCommReLUT,
+ * GraphQCommQuT (src/QAliases.jl:85-181).  slice_kind is RRRMC_RE_SLICE_PERC_STEP / _PERC_LINEAR / _COMM_STEP / _COMM_RELU / _COMM_QU; Nk synapses
+ * per slice, for the committee machines Nk = K1*K2 (K2 is ignored for the perceptrons).  RRRMC_ERR_INVALID_ARG: Nk even (perceptrons); K1, K2 even
+ * (step) or odd (ReLU, Qu), Nk not a multiple of K2; M <= 2 (QT.jl:47).  RRRMC_ERR_UNSUPPORTED: Nk > 32767, N = Nk*M > 65535.  Then rrrmc_set_patterns
  * (perceptrons) or rrrmc_set_comm_patterns (committee machines; 1 <= P <= 4096) and rrrmc_quant_set_field, without which every sampler,
  * energy and observable call answers RRRMC_ERR_STATE.  Sites are GraphQuant's, x = k*Nk + i.  energy = energy(GraphQT) + sum_k
  * energy(X1[k]) / M (QT.jl:185-199); delta_energy_residual = delta_energy(X1[k], C1[k], i) / M (QT.jl:270-281).  Served by rrrmc_rrr_mc_async
@@ -351,11 +358,16 @@ RRRMC_API int32_t rrrmc_gen_patterns(int64_t N, int64_t P, uint64_t seed, uint64
  * rrrmc_set_resume, rrrmc_set_debug_checks, rrrmc_energy_f64.  rrrMC / bklMC / wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED.
  *
  * rrrmc_set_comm_patterns: the P patterns xi[P * ceil(N / 64)] in rrrmc_set_patterns' layout (bits beyond N must be 0), and for
- * GraphCommReLU the labels y[ceil(P / 64)] (bit a = y_a; bits beyond P must be 0); y must be NULL for GraphCommStep.  1 <= P <= 4096
+ * GraphCommReLU and GraphCommQu the labels y[ceil(P / 64)] (bit a = y_a; bits beyond P must be 0); y must be NULL for GraphCommStep.  1 <= P <= 4096
  * (RRRMC_ERR_UNSUPPORTED beyond).  N % K2 != 0, a wrong parity of K1 = N / K2 or K2, a missing or extra y: RRRMC_ERR_INVALID_ARG.  For a
  * context made by rrrmc_ctx_create_comm (K2 must be the context's), or by rrrmc_ctx_create_re / _le with a committee slice kind (N = Nk:
  * this call fixes K2; all slices, and the centre of a GraphLocalEntropy, share the one matrix).  May be called again: it ends a resumed run. */
 RRRMC_API int32_t rrrmc_ctx_create_comm(rrrmc_ctx **out, int64_t K1, int64_t K2, int32_t relu, int64_t R, int32_t device, uint32_t replica0);
+/* GraphCommQu (src/graphs/CommQu.jl; RRRMC_MODEL_COMM_QU, RRRMC_RE_SLICE_COMM_QU): the committee machine whose hidden units answer with the
+ * square of their stability, Delta2[a] = o_a sum_u c_u Delta1[u][a]^2, energy = #{Delta2 <= 0}.  K1 and K2 even, labels required: everything
+ * said of GraphCommReLU above holds (rrrmc_set_comm_patterns with y, rrrmc_gen_comm_patterns, the samplers served and refused, N <= 32767);
+ * the reference's per-pattern heaps are not kept, Delta2 is 32-bit. */
+RRRMC_API int32_t rrrmc_ctx_create_comm_qu(rrrmc_ctx **out, int64_t K1, int64_t K2, int64_t R, int32_t device, uint32_t replica0);
 RRRMC_API int32_t rrrmc_set_comm_patterns(rrrmc_ctx *ctx, int64_t K2, const uint64_t *xi, const uint64_t *y, int64_t P);
 /* gen_xi (CommStep.jl:16-26, CommReLU.jl:16-27, fc: CommStep.jl:85-93), drawn on the host: xi_out[P * ceil(K1*K2 / 64)] as
  * rrrmc_gen_patterns(fc ? K1 : K1*K2, P, seed) draws its rows, with fc's K1 columns repeated K2 times; y_out[ceil(P / 64)] (may be NULL)

@@ -58,17 +58,19 @@ const RE_EMPTY, RE_SK, RE_SKN = 11, 12, 13            # GraphRobustEnsemble over
 const LE_EMPTY, LE_SK, LE_SKN = 14, 15, 16            # GraphLocalEntropy over GraphEmpty / GraphSK / GraphSKNormal (rrrmc_ctx_create_le; multi selectors)
 const PERC_STEP, PERC_LINEAR = 17, 18                 # GraphPercStep, GraphPercLinear (rrrmc_ctx_create_perc; multi selectors)
 const COMM_STEP, COMM_RELU = 23, 24                   # GraphCommStep, GraphCommReLU (rrrmc_ctx_create_comm; multi selectors, N = K1 K2, K = K2)
+const COMM_QU, QUANT_COMM_QU = 36, 39                 # GraphCommQu (rrrmc_ctx_create_comm_qu), GraphQCommQuT (slice kind 9); multi selectors as their siblings
 const QUANT_PAT_MODELS = (29, 30, 31, 32)              # by slice kind 3..6: GraphQPercStepT, GraphQPercLinearT, GraphQCommStepT, GraphQCommReLUT (multi selectors)
 const SAT, RE_SAT, LE_SAT = 33, 34, 35                 # GraphSAT (rrrmc_ctx_create_sat), GraphSATRE, GraphSATLE (multi selectors)
-const RE_MODELS = (RE_EMPTY, RE_SK, RE_SKN, 19, 20, 25, 26, 0, RE_SAT)   # by slice kind 0..8 (3, 4: GraphPercStep, GraphPercLinear; 5, 6: GraphCommStep, GraphCommReLU; 7 unassigned; 8: GraphSAT)
-const LE_MODELS = (LE_EMPTY, LE_SK, LE_SKN, 21, 22, 27, 28, 0, LE_SAT)
-const CommGraph = Union{RRRMC.CommStep.GraphCommStep,RRRMC.CommReLU.GraphCommReLU}
+const RE_MODELS = (RE_EMPTY, RE_SK, RE_SKN, 19, 20, 25, 26, 0, RE_SAT, 37)   # by slice kind 0..9 (3, 4: GraphPercStep, GraphPercLinear; 5, 6: GraphCommStep, GraphCommReLU; 7 unassigned; 8: GraphSAT; 9: GraphCommQu)
+const LE_MODELS = (LE_EMPTY, LE_SK, LE_SKN, 21, 22, 27, 28, 0, LE_SAT, 38)
+const CommGraph = Union{RRRMC.CommStep.GraphCommStep,RRRMC.CommReLU.GraphCommReLU,RRRMC.CommQu.GraphCommQu}
 const PercGraph = Union{RRRMC.PercStep.GraphPercStep,RRRMC.PercLinear.GraphPercLinear}
 # slice kind of an ensemble's graph type (rrrmc_re_slice)
 ens_kind(G, what) = G <: RRRMC.SK.GraphSK ? 1 : G <: RRRMC.SK.GraphSKNormal ? 2 : G <: RRRMC.Empty.GraphEmpty ? 0 :
                     G <: RRRMC.PercStep.GraphPercStep ? 3 : G <: RRRMC.PercLinear.GraphPercLinear ? 4 :
                     G <: RRRMC.CommStep.GraphCommStep ? 5 : G <: RRRMC.CommReLU.GraphCommReLU ? 6 : G <: RRRMC.SAT.GraphSAT ? 8 :
-                    throw(ArgumentError("the engine runs the $what over GraphEmpty, GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, GraphCommStep, GraphCommReLU and GraphSAT slices, given: $G"))
+                    G <: RRRMC.CommQu.GraphCommQu ? 9 :
+                    throw(ArgumentError("the engine runs the $what over GraphEmpty, GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, GraphCommStep, GraphCommReLU, GraphCommQu and GraphSAT slices, given: $G"))
 # the clauses of a GraphSAT as Mc rows of K = max length 0-based variables (-1 pads) and literal bits (SAT.jl:75-115): rrrmc_set_clauses
 function set_patterns!(ctx, X1::RRRMC.SAT.GraphSAT)
     vars = fill(Int32(-1), X1.K, X1.M); lits = zeros(Int8, X1.K, X1.M)
@@ -85,11 +87,11 @@ function set_patterns!(ctx, X1::PercGraph)
     GC.@preserve xi check(ccall((:rrrmc_set_patterns, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt64}, Int64), ctx.p, xi, X1.P), ctx.p)
     return ctx
 end
-# the patterns of a committee machine as P rows of chunks, and GraphCommReLU's labels as P bits: rrrmc_set_comm_patterns (fixes K2)
+# the patterns of a committee machine as P rows of chunks, and GraphCommReLU's / GraphCommQu's labels as P bits: rrrmc_set_comm_patterns (fixes K2)
 function set_patterns!(ctx, X1::CommGraph)
     nch = (X1.N + 63) >> 6
     xi = Matrix{UInt64}(undef, nch, X1.P); for a = 1:X1.P; xi[:, a] = X1.ξv[a].chunks; end
-    if X1 isa RRRMC.CommReLU.GraphCommReLU
+    if !(X1 isa RRRMC.CommStep.GraphCommStep)
         y = copy(X1.y.chunks)
         GC.@preserve xi y check(ccall((:rrrmc_set_comm_patterns, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{UInt64}, Ptr{UInt64}, Int64), ctx.p, X1.K2, xi, y, X1.P), ctx.p)
     else
@@ -219,14 +221,15 @@ function Ctx(X::RRRMC.QT.GraphQuant{fourK,G}, R::Integer, β::Real; device = 0, 
         Jm = Matrix{Float64}(undef, Nk, Nk); for i = 1:Nk; Jm[:, i] = X1.J[i]; end
         GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
     elseif G <: Union{PercGraph,CommGraph}
-        # GraphQPercStepT / GraphQPercLinearT / GraphQCommStepT / GraphQCommReLUT (src/QAliases.jl:85-159): pattern machines on one pattern matrix
+        # GraphQPercStepT / GraphQPercLinearT / GraphQCommStepT / GraphQCommReLUT / GraphQCommQuT (src/QAliases.jl:85-181): pattern machines on one
+        # pattern matrix
         kind = ens_kind(G, "GraphQuant")
         K2 = G <: CommGraph ? X1.K2 : 0
         if devices === nothing
             check(ccall((:rrrmc_ctx_create_quant_pattern, LIB), Int32, (Ref{Ptr{Cvoid}}, Int32, Int64, Int64, Int64, Int64, Int32, UInt32),
                         ref, kind, Nk, K2, M, R, device, replica0))
         else
-            ref[] = create(QUANT_PAT_MODELS[kind - 2], Nk, K2, M, R; replica0 = replica0, devices = devices)
+            ref[] = create(kind == 9 ? QUANT_COMM_QU : QUANT_PAT_MODELS[kind - 2], Nk, K2, M, R; replica0 = replica0, devices = devices)
         end
         ctx = set_patterns!(Ctx(ref[], R, Nk * M, true), X1)
     elseif G <: F64Graph
@@ -314,15 +317,19 @@ function sat_build(ctx::Ctx)
     return Int(b[])
 end
 
-# ---- GraphCommStep / GraphCommReLU (src/graphs/CommStep.jl, CommReLU.jl), stand-alone: standardMC only -------------------------------
+# ---- GraphCommStep / GraphCommReLU / GraphCommQu (src/graphs/CommStep.jl, CommReLU.jl, CommQu.jl), stand-alone: standardMC only --------
+# (the GraphCommQu methods — this one, and the RE / LE / GraphQuant ones through ens_kind = 9 — are checked statically only, as the rest of this file)
 # (rrrMC / bklMC / wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED).  The integer energies arrive as exact Float64s.
 function Ctx(X::CommGraph, R::Integer; device = 0, replica0 = 0, devices = nothing)
     relu = X isa RRRMC.CommReLU.GraphCommReLU
+    qu = X isa RRRMC.CommQu.GraphCommQu
     ref = Ref{Ptr{Cvoid}}(C_NULL)
-    if devices === nothing
+    if devices === nothing && qu
+        check(ccall((:rrrmc_ctx_create_comm_qu, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Int32, UInt32), ref, X.K1, X.K2, R, device, replica0))
+    elseif devices === nothing
         check(ccall((:rrrmc_ctx_create_comm, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, Int64, Int32, UInt32), ref, X.K1, X.K2, relu ? 1 : 0, R, device, replica0))
     else
-        ref[] = create(relu ? COMM_RELU : COMM_STEP, X.N, X.K2, 0, R; replica0 = replica0, devices = devices)
+        ref[] = create(qu ? COMM_QU : relu ? COMM_RELU : COMM_STEP, X.N, X.K2, 0, R; replica0 = replica0, devices = devices)
     end
     return set_patterns!(Ctx(ref[], R, X.N, true), X)
 end

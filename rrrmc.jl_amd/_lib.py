@@ -37,7 +37,7 @@ SYMBOLS = [
     "rrrmc_ctx_create_re", "rrrmc_re_set_params", "rrrmc_re_energies", "rrrmc_re_tables",
     "rrrmc_ctx_create_le", "rrrmc_le_set_params", "rrrmc_le_energies", "rrrmc_le_cenergy", "rrrmc_le_distances", "rrrmc_le_tables",
     "rrrmc_ctx_create_perc", "rrrmc_set_patterns", "rrrmc_gen_patterns",
-    "rrrmc_ctx_create_comm", "rrrmc_set_comm_patterns", "rrrmc_gen_comm_patterns",
+    "rrrmc_ctx_create_comm", "rrrmc_ctx_create_comm_qu", "rrrmc_set_comm_patterns", "rrrmc_gen_comm_patterns",
     "rrrmc_ctx_create_quant_pattern", "rrrmc_quant_renergies", "rrrmc_quant_pattern_build",
     "rrrmc_ctx_create_sat", "rrrmc_set_clauses", "rrrmc_sat_build", "rrrmc_sweep_build", "rrrmc_gen_ksat", "rrrmc_check_clauses",
 ]
@@ -250,6 +250,8 @@ def lib():
     L.rrrmc_gen_patterns.argtypes = [C.c_int64, C.c_int64, C.c_uint64, u64p]
     L.rrrmc_ctx_create_comm.restype = C.c_int32
     L.rrrmc_ctx_create_comm.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_uint32]
+    L.rrrmc_ctx_create_comm_qu.restype = C.c_int32
+    L.rrrmc_ctx_create_comm_qu.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_uint32]
     L.rrrmc_set_comm_patterns.restype = C.c_int32
     L.rrrmc_set_comm_patterns.argtypes = [vp, C.c_int64, u64p, _U64OrNull, C.c_int64]
     L.rrrmc_gen_comm_patterns.restype = C.c_int32

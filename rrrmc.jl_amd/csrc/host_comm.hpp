@@ -1,19 +1,29 @@
-// Host side of the binary committee machines (comm_kernels.hpp): the stand-alone GraphCommStep / GraphCommReLU contexts under standardMC,
+// Host side of the binary committee machines (comm_kernels.hpp): the stand-alone GraphCommStep / GraphCommReLU / GraphCommQu contexts under
+// standardMC,
 // and the pattern matrix, labels and Stabilities that the Robust Ensemble and Local Entropy contexts with committee slices share with them.
 // Included by rrrmc_hip.hip inside its anonymous namespace, before host_re.hpp; not a stand-alone translation unit.
-inline bool is_comm(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_COMM_STEP || ctx->model == RRRMC_MODEL_COMM_RELU; }
+inline bool is_comm(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_COMM_STEP || ctx->model == RRRMC_MODEL_COMM_RELU || ctx->model == RRRMC_MODEL_COMM_QU; }
 inline bool comm_slices(const rrrmc_ctx* ctx)
 {
     return ctx->model == RRRMC_MODEL_RE_COMM_STEP || ctx->model == RRRMC_MODEL_RE_COMM_RELU || ctx->model == RRRMC_MODEL_LE_COMM_STEP ||
-           ctx->model == RRRMC_MODEL_LE_COMM_RELU;
+           ctx->model == RRRMC_MODEL_LE_COMM_RELU || ctx->model == RRRMC_MODEL_RE_COMM_QU || ctx->model == RRRMC_MODEL_LE_COMM_QU;
 }
 inline bool comm_relu(const rrrmc_ctx* ctx)
 {
     return ctx->model == RRRMC_MODEL_COMM_RELU || ctx->model == RRRMC_MODEL_RE_COMM_RELU || ctx->model == RRRMC_MODEL_LE_COMM_RELU ||
            (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_pat == RRRMC_RE_SLICE_COMM_RELU);
 }
+inline bool comm_qu(const rrrmc_ctx* ctx)
+{
+    return ctx->model == RRRMC_MODEL_COMM_QU || ctx->model == RRRMC_MODEL_RE_COMM_QU || ctx->model == RRRMC_MODEL_LE_COMM_QU ||
+           (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_pat == RRRMC_RE_SLICE_COMM_QU);
+}
+// GraphCommReLU and GraphCommQu: K1, K2 even, labelled patterns
+inline bool comm_labelled(const rrrmc_ctx* ctx) { return comm_relu(ctx) || comm_qu(ctx); }
+inline int comm_kind(const rrrmc_ctx* ctx) { return comm_qu(ctx) ? CK_QU : comm_relu(ctx) ? CK_RELU : CK_STEP; }
 
-// GraphCommStep(K2, ξ, ξv): isodd(K1), isodd(K2) (CommStep.jl:65-66); GraphCommReLU: iseven (CommReLU.jl:68-69)
+// GraphCommStep(K2, ξ, ξv): isodd(K1), isodd(K2) (CommStep.jl:65-66); GraphCommReLU, GraphCommQu (relu = true): iseven (CommReLU.jl:68-69,
+// CommQu.jl:72-73)
 int32_t comm_check_k(rrrmc_ctx* ctx, int64_t K1, int64_t K2, bool relu)
 {
     if (K1 < 1 || K2 < 1) return fail(ctx, RRRMC_ERR_INVALID_ARG, "K1 and K2 must be >= 1, given: %lld, %lld", (long long)K1, (long long)K2);
@@ -24,7 +34,8 @@ int32_t comm_check_k(rrrmc_ctx* ctx, int64_t K1, int64_t K2, bool relu)
         return fail(ctx, RRRMC_ERR_UNSUPPORTED, "N = K1*K2 = %lld: the committee machine kernels cover N <= %d (16-bit stabilities)", (long long)(K1 * K2), kCommNmax);
     return RRRMC_OK;
 }
-// what an ensemble context can check before K2 is known: N = K1 K2 is odd (step) or a multiple of 4 (ReLU), and the kernels' bound
+// what an ensemble context can check before K2 is known: N = K1 K2 is odd (step) or a multiple of 4 (relu = true: ReLU, Qu), and the
+// kernels' bound
 int32_t comm_check_nk(int64_t N, bool relu)
 {
     if (!relu && N % 2 == 0) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "N = K1*K2 with K1, K2 odd must be odd, given: %lld", (long long)N);
@@ -45,10 +56,10 @@ CommParams comm_params(const rrrmc_ctx* ctx, int64_t rows)
 // rrrmc_set_comm_patterns on one device: rows = chains' rows that carry Stabilities (1, M, or M + 1)
 int32_t comm_set_patterns(rrrmc_ctx* ctx, int64_t K2, const uint64_t* xi, const uint64_t* y, int64_t P, int64_t rows)
 {
-    const bool relu = comm_relu(ctx);
+    const bool relu = comm_labelled(ctx), qu = comm_qu(ctx);
     const int64_t N = ctx->qNk;
     if (!xi) return fail(ctx, RRRMC_ERR_INVALID_ARG, "xi is NULL");
-    if (relu && !y) return fail(ctx, RRRMC_ERR_INVALID_ARG, "a GraphCommReLU needs the labels y");
+    if (relu && !y) return fail(ctx, RRRMC_ERR_INVALID_ARG, "a %s needs the labels y", qu ? "GraphCommQu" : "GraphCommReLU");
     if (!relu && y) return fail(ctx, RRRMC_ERR_INVALID_ARG, "a GraphCommStep has no labels: y must be NULL");
     if (K2 < 1 || N % K2 != 0) return fail(ctx, RRRMC_ERR_INVALID_ARG, "N = %lld is not a multiple of K2 = %lld", (long long)N, (long long)K2);
     if ((is_comm(ctx) || ctx->model == RRRMC_MODEL_QUANT_RRG) && K2 != ctx->cm_K2)
@@ -80,8 +91,8 @@ int32_t comm_set_patterns(rrrmc_ctx* ctx, int64_t K2, const uint64_t* xi, const 
         HIP_TRY(ctx, hipMalloc(&ctx->cm_col, sizeof(uint64_t) * (size_t)(N * PW)));
         HIP_TRY(ctx, hipMalloc(&ctx->cm_row, sizeof(uint64_t) * (size_t)(P * nch)));
         HIP_TRY(ctx, hipMalloc(&ctx->cm_lab, sizeof(uint64_t) * (size_t)(2 * PW)));
-        HIP_TRY(ctx, hipMalloc(&ctx->cm_ds, sizeof(int16_t) * (size_t)ctx->R * (size_t)rows * comm_ds_row((int)K2, (int)PW)));
-        HIP_TRY(ctx, hipMalloc(&ctx->cm_mk, sizeof(uint64_t) * (size_t)ctx->R * (size_t)rows * comm_mk_row((int)K2, (int)PW)));
+        HIP_TRY(ctx, hipMalloc(&ctx->cm_ds, sizeof(int16_t) * (size_t)ctx->R * (size_t)rows * comm_ds_row((int)K2, (int)PW, qu)));
+        HIP_TRY(ctx, hipMalloc(&ctx->cm_mk, sizeof(uint64_t) * (size_t)ctx->R * (size_t)rows * comm_mk_row((int)K2, (int)PW, qu)));
         ctx->cm_P = P; ctx->cm_K2 = K2;
     }
     HIP_TRY(ctx, hipMemcpy(ctx->cm_col, col.data(), sizeof(uint64_t) * col.size(), hipMemcpyHostToDevice));
@@ -108,8 +119,11 @@ CommMcParams comm_mc_params(rrrmc_ctx* ctx, double beta)
 int32_t comm_run_init(rrrmc_ctx* ctx)
 {
     const CommMcParams P = comm_mc_params(ctx, 1.0);
-    if (comm_relu(ctx)) hipLaunchKernelGGL(comm_init_kernel<true>, dim3((unsigned)ctx->R), dim3(kCommInitThreads), 0, ctx->stream, P);
-    else hipLaunchKernelGGL(comm_init_kernel<false>, dim3((unsigned)ctx->R), dim3(kCommInitThreads), 0, ctx->stream, P);
+    switch (comm_kind(ctx)) {
+        case CK_QU: hipLaunchKernelGGL(comm_init_kernel<CK_QU>, dim3((unsigned)ctx->R), dim3(kCommInitThreads), 0, ctx->stream, P); break;
+        case CK_RELU: hipLaunchKernelGGL(comm_init_kernel<CK_RELU>, dim3((unsigned)ctx->R), dim3(kCommInitThreads), 0, ctx->stream, P); break;
+        default: hipLaunchKernelGGL(comm_init_kernel<CK_STEP>, dim3((unsigned)ctx->R), dim3(kCommInitThreads), 0, ctx->stream, P); break;
+    }
     HIP_TRY(ctx, hipGetLastError());
     return RRRMC_OK;
 }
@@ -143,18 +157,24 @@ int32_t comm_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step)
     if (!(ctx->resume && ctx->std_cache_live)) { const int32_t rc = comm_run_init(ctx); if (rc) return rc; }
     CommMcParams P = comm_mc_params(ctx, beta);
     P.g0 = ctx->it_done; P.iters = iters; P.step = step; P.samp0 = step;
-    const bool relu = comm_relu(ctx);
+    const int kind = comm_kind(ctx);
     HIP_TRY(ctx, hipEventRecord(ctx->ev_sweep[0], st));
-    if (relu) hipLaunchKernelGGL(comm_standard_kernel<true>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P);
-    else hipLaunchKernelGGL(comm_standard_kernel<false>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P);
+    switch (kind) {
+        case CK_QU: hipLaunchKernelGGL(comm_standard_kernel<CK_QU>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
+        case CK_RELU: hipLaunchKernelGGL(comm_standard_kernel<CK_RELU>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
+        default: hipLaunchKernelGGL(comm_standard_kernel<CK_STEP>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
+    }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_sweep[1], st));
     if (ctx->debug_checks) {
         if (!ctx->dbg_flag) { HIP_TRY(ctx, hipMalloc(&ctx->dbg_flag, sizeof(int32_t) * 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, st)); }
         P.flag = ctx->dbg_flag;
         const dim3 grid((unsigned)((ctx->R + 63) / 64)), blk(64);
-        if (relu) hipLaunchKernelGGL(comm_check_kernel<true>, grid, blk, 0, st, P);
-        else hipLaunchKernelGGL(comm_check_kernel<false>, grid, blk, 0, st, P);
+        switch (kind) {
+            case CK_QU: hipLaunchKernelGGL(comm_check_kernel<CK_QU>, grid, blk, 0, st, P); break;
+            case CK_RELU: hipLaunchKernelGGL(comm_check_kernel<CK_RELU>, grid, blk, 0, st, P); break;
+            default: hipLaunchKernelGGL(comm_check_kernel<CK_STEP>, grid, blk, 0, st, P); break;
+        }
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_end, st));
@@ -168,12 +188,13 @@ int32_t comm_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step)
     return RRRMC_OK;
 }
 
-int32_t comm_ctx_create(rrrmc_ctx** out, int64_t K1, int64_t K2, int32_t relu, int64_t R, int32_t device, uint32_t replica0)
+// kind: CK_STEP, CK_RELU or CK_QU
+int32_t comm_ctx_create(rrrmc_ctx** out, int64_t K1, int64_t K2, int kind, int64_t R, int32_t device, uint32_t replica0)
 {
     if (!out) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "R must be >= 1");
-    { const int32_t rck = comm_check_k(nullptr, K1, K2, relu != 0); if (rck) return rck; }
+    { const int32_t rck = comm_check_k(nullptr, K1, K2, kind != CK_STEP); if (rck) return rck; }
     if (replica0 % 32) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "replica0 must be a multiple of 32 (given %u)", replica0);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -182,7 +203,7 @@ int32_t comm_ctx_create(rrrmc_ctx** out, int64_t K1, int64_t K2, int32_t relu, i
     rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
     if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
     const int64_t N = K1 * K2;
-    ctx->model = relu ? RRRMC_MODEL_COMM_RELU : RRRMC_MODEL_COMM_STEP;
+    ctx->model = kind == CK_QU ? RRRMC_MODEL_COMM_QU : kind == CK_RELU ? RRRMC_MODEL_COMM_RELU : RRRMC_MODEL_COMM_STEP;
     ctx->N = N; ctx->K = 0; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = N; ctx->qM = 1; ctx->qW = 2 * ((N + 63) / 64);
     ctx->cm_K2 = K2;

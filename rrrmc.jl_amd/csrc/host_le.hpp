@@ -3,10 +3,12 @@
 // Robust Ensemble's buffers (re_sp, re_mu, re_tab, re_Eslice and the q_* DeltaECache arrays) with M + 1 rows.
 inline bool is_le(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_LE_EMPTY || ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_LE_SKN ||
                                                 ctx->model == RRRMC_MODEL_LE_PERC_STEP || ctx->model == RRRMC_MODEL_LE_PERC_LINEAR ||
-                                                ctx->model == RRRMC_MODEL_LE_COMM_STEP || ctx->model == RRRMC_MODEL_LE_COMM_RELU || ctx->model == RRRMC_MODEL_LE_SAT; }
+                                                ctx->model == RRRMC_MODEL_LE_COMM_STEP || ctx->model == RRRMC_MODEL_LE_COMM_RELU || ctx->model == RRRMC_MODEL_LE_SAT ||
+                                                ctx->model == RRRMC_MODEL_LE_COMM_QU; }
 inline int le_slice_of(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_LE_SK ? RE_SK : ctx->model == RRRMC_MODEL_LE_SKN ? RE_SKN :
                                                       ctx->model == RRRMC_MODEL_LE_PERC_STEP ? RE_PSTEP : ctx->model == RRRMC_MODEL_LE_PERC_LINEAR ? RE_PLIN :
-                                                      ctx->model == RRRMC_MODEL_LE_COMM_STEP ? RE_CSTEP : ctx->model == RRRMC_MODEL_LE_COMM_RELU ? RE_CRELU : ctx->model == RRRMC_MODEL_LE_SAT ? RE_SAT : RE_EMPTY; }
+                                                      ctx->model == RRRMC_MODEL_LE_COMM_STEP ? RE_CSTEP : ctx->model == RRRMC_MODEL_LE_COMM_RELU ? RE_CRELU : ctx->model == RRRMC_MODEL_LE_SAT ? RE_SAT :
+                                                      ctx->model == RRRMC_MODEL_LE_COMM_QU ? RE_CQU : RE_EMPTY; }
 inline int le_levels(int64_t M) { return (int)(M % 2 == 0 ? M / 2 + 2 : (M + 1) / 2); }        // length of allΔE(GraphLE) (LE.jl:176-179)
 
 // allΔE(GraphLE{M,γT}) (LE.jl:176-179): M even (0, 2|γT|, 4|γT|, 8|γT|, ..., 2M|γT|), M odd (2|γT|, 6|γT|, ..., 2M|γT|); Julia's integer
@@ -66,7 +68,7 @@ LeParams le_params(rrrmc_ctx* ctx, double beta)
     if (ctx->model == RRRMC_MODEL_LE_SK) { P.Jb = ctx->q_Jb; P.Wk = (int)ctx->q_Wk; P.sN = std::sqrt((double)ctx->qNk); }
     if (ctx->model == RRRMC_MODEL_LE_SKN) { P.Jd = ctx->sk_J; P.slf = ctx->q_slf; P.smv = ctx->q_smv; P.scur = ctx->q_scur; }
     if (le_slice_of(ctx) == RE_PSTEP || le_slice_of(ctx) == RE_PLIN) P.pc = perc_params(ctx, M + 1);
-    if (le_slice_of(ctx) == RE_CSTEP || le_slice_of(ctx) == RE_CRELU) P.cm = comm_params(ctx, M + 1);
+    if (le_slice_of(ctx) == RE_CSTEP || le_slice_of(ctx) == RE_CRELU || le_slice_of(ctx) == RE_CQU) P.cm = comm_params(ctx, M + 1);
     if (le_slice_of(ctx) == RE_SAT) P.sat = sat_table(ctx);
     P.tab = ctx->re_tab; P.etab = nullptr; P.ft = ctx->re_tab + L; P.ctab = reinterpret_cast<const uint8_t*>(ctx->re_tab + 2 * L);
     P.abi = ctx->q_spins; P.sp = ctx->re_sp; P.mu = ctx->re_mu; P.cls = ctx->q_cls; P.sv = ctx->q_sv; P.spos = ctx->q_spos; P.st = ctx->q_st;
@@ -96,6 +98,7 @@ int32_t le_run_init(rrrmc_ctx* ctx, double beta, bool cache)
         case RE_PLIN: hipLaunchKernelGGL(le_init_kernel<RE_PLIN>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CSTEP: hipLaunchKernelGGL(le_init_kernel<RE_CSTEP>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CRELU: hipLaunchKernelGGL(le_init_kernel<RE_CRELU>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
+        case RE_CQU: hipLaunchKernelGGL(le_init_kernel<RE_CQU>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_SAT: hipLaunchKernelGGL(le_init_kernel<RE_SAT>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         default: hipLaunchKernelGGL(le_init_kernel<RE_EMPTY>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
     }
@@ -120,6 +123,7 @@ le_kernel_fn le_rrr_fn(int slice, bool lds, int L)
         case RE_PLIN: return lds ? le_rrr_for_L<true, RE_PLIN>(L) : le_rrr_for_L<false, RE_PLIN>(L);
         case RE_CSTEP: return lds ? le_rrr_for_L<true, RE_CSTEP>(L) : le_rrr_for_L<false, RE_CSTEP>(L);
         case RE_CRELU: return lds ? le_rrr_for_L<true, RE_CRELU>(L) : le_rrr_for_L<false, RE_CRELU>(L);
+        case RE_CQU: return lds ? le_rrr_for_L<true, RE_CQU>(L) : le_rrr_for_L<false, RE_CQU>(L);
         case RE_SAT: return lds ? le_rrr_for_L<true, RE_SAT>(L) : le_rrr_for_L<false, RE_SAT>(L);
         default: return lds ? le_rrr_for_L<true, RE_EMPTY>(L) : le_rrr_for_L<false, RE_EMPTY>(L);
     }
@@ -139,6 +143,7 @@ int32_t le_debug_check(rrrmc_ctx* ctx, const LeParams& P0, bool cache)
         case RE_PLIN: hipLaunchKernelGGL(le_check_kernel<RE_PLIN>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CSTEP: hipLaunchKernelGGL(le_check_kernel<RE_CSTEP>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CRELU: hipLaunchKernelGGL(le_check_kernel<RE_CRELU>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
+        case RE_CQU: hipLaunchKernelGGL(le_check_kernel<RE_CQU>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_SAT: hipLaunchKernelGGL(le_check_kernel<RE_SAT>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         default: hipLaunchKernelGGL(le_check_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
     }
@@ -196,6 +201,7 @@ int32_t le_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, i
             case RE_PLIN: hipLaunchKernelGGL(le_standard_kernel<RE_PLIN>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             case RE_CSTEP: hipLaunchKernelGGL(le_standard_kernel<RE_CSTEP>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             case RE_CRELU: hipLaunchKernelGGL(le_standard_kernel<RE_CRELU>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
+            case RE_CQU: hipLaunchKernelGGL(le_standard_kernel<RE_CQU>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             case RE_SAT: hipLaunchKernelGGL(le_standard_kernel<RE_SAT>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             default: hipLaunchKernelGGL(le_standard_kernel<RE_EMPTY>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
         }
@@ -204,7 +210,7 @@ int32_t le_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, i
         // RRRMC_LE_NO_LDS=1 forces the thread build, RRRMC_LE_LDS=1 the LDS build (timing experiments, the builds' parity test)
         size_t lds = le_rrr_lds_bytes(ctx->N, ctx->qW, ctx->qNk);
         if (P.pc.ds) lds = ((lds + 7) & ~(size_t)7) + perc_lds_bytes(P.pc.rows, P.pc.PW);
-        if (P.cm.ds) lds = ((lds + 7) & ~(size_t)7) + comm_lds_bytes(P.cm.rows, P.cm.K2, P.cm.PW);          // the rows' Stabilities
+        if (P.cm.ds) lds = ((lds + 7) & ~(size_t)7) + comm_lds_bytes(P.cm.rows, P.cm.K2, P.cm.PW, slice == RE_CQU);          // the rows' Stabilities
         const char* no_lds = std::getenv("RRRMC_LE_NO_LDS");
         const char* want_lds = std::getenv("RRRMC_LE_LDS");
         // (perceptron slices: the LDS build at every replica count, as in re_mc_async)
@@ -251,6 +257,7 @@ int32_t le_observables(rrrmc_ctx* ctx)
         case RE_PLIN: hipLaunchKernelGGL(le_obs_kernel<RE_PLIN>, grid, blk, 0, ctx->stream, P); break;
         case RE_CSTEP: hipLaunchKernelGGL(le_obs_kernel<RE_CSTEP>, grid, blk, 0, ctx->stream, P); break;
         case RE_CRELU: hipLaunchKernelGGL(le_obs_kernel<RE_CRELU>, grid, blk, 0, ctx->stream, P); break;
+        case RE_CQU: hipLaunchKernelGGL(le_obs_kernel<RE_CQU>, grid, blk, 0, ctx->stream, P); break;
         case RE_SAT: hipLaunchKernelGGL(le_obs_kernel<RE_SAT>, grid, blk, 0, ctx->stream, P); break;
         default: hipLaunchKernelGGL(le_obs_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P); break;
     }
@@ -263,12 +270,12 @@ int32_t le_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind
     if (!out) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     const bool perc = slice_kind == RRRMC_RE_SLICE_PERC_STEP || slice_kind == RRRMC_RE_SLICE_PERC_LINEAR;
-    const bool comm = slice_kind == RRRMC_RE_SLICE_COMM_STEP || slice_kind == RRRMC_RE_SLICE_COMM_RELU;
+    const bool comm = slice_kind == RRRMC_RE_SLICE_COMM_STEP || slice_kind == RRRMC_RE_SLICE_COMM_RELU || slice_kind == RRRMC_RE_SLICE_COMM_QU;
     if (slice_kind != RRRMC_RE_SLICE_EMPTY && slice_kind != RRRMC_RE_SLICE_SK && slice_kind != RRRMC_RE_SLICE_SKN && slice_kind != RRRMC_RE_SLICE_SAT && !perc && !comm)
-        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind must be RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP, _PERC_LINEAR, _COMM_STEP, _COMM_RELU or _SAT, given: %d", slice_kind);
+        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind must be RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP, _PERC_LINEAR, _COMM_STEP, _COMM_RELU, _SAT or _COMM_QU, given: %d", slice_kind);
     if (Nk < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "Nk and R must be >= 1");
     if (perc) { const int32_t rcn = perc_check_n(Nk); if (rcn) return rcn; }
-    if (comm) { const int32_t rcn = comm_check_nk(Nk, slice_kind == RRRMC_RE_SLICE_COMM_RELU); if (rcn) return rcn; }
+    if (comm) { const int32_t rcn = comm_check_nk(Nk, slice_kind != RRRMC_RE_SLICE_COMM_STEP); if (rcn) return rcn; }
     if (M <= 2) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "M must be greater than 2, given: %lld", (long long)M);      // LE.jl:24
     if (M > kLeMmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "M = %lld: the Local Entropy kernels cover M <= %d", (long long)M, kLeMmax);
     if (Nk * (M + 1) > 65535)
@@ -283,7 +290,7 @@ int32_t le_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind
     ctx->model = slice_kind == RRRMC_RE_SLICE_SK ? RRRMC_MODEL_LE_SK : slice_kind == RRRMC_RE_SLICE_SKN ? RRRMC_MODEL_LE_SKN :
                  slice_kind == RRRMC_RE_SLICE_PERC_STEP ? RRRMC_MODEL_LE_PERC_STEP : slice_kind == RRRMC_RE_SLICE_PERC_LINEAR ? RRRMC_MODEL_LE_PERC_LINEAR :
                  slice_kind == RRRMC_RE_SLICE_COMM_STEP ? RRRMC_MODEL_LE_COMM_STEP : slice_kind == RRRMC_RE_SLICE_COMM_RELU ? RRRMC_MODEL_LE_COMM_RELU :
-                 slice_kind == RRRMC_RE_SLICE_SAT ? RRRMC_MODEL_LE_SAT : RRRMC_MODEL_LE_EMPTY;
+                 slice_kind == RRRMC_RE_SLICE_SAT ? RRRMC_MODEL_LE_SAT : slice_kind == RRRMC_RE_SLICE_COMM_QU ? RRRMC_MODEL_LE_COMM_QU : RRRMC_MODEL_LE_EMPTY;
     const int64_t rows = M + 1, N = Nk * rows, L = le_levels(M);
     ctx->N = N; ctx->K = 0; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = Nk; ctx->qM = M; ctx->qW = 2 * ((N + 63) / 64); ctx->q_Wk = 2 * ((Nk + 63) / 64);

@@ -3,10 +3,12 @@
 // (fail, HIP_TRY, free_dev, ensure_state, smp_begin); not a stand-alone translation unit.
 inline bool is_re(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_RE_EMPTY || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_RE_SKN ||
                                                 ctx->model == RRRMC_MODEL_RE_PERC_STEP || ctx->model == RRRMC_MODEL_RE_PERC_LINEAR ||
-                                                ctx->model == RRRMC_MODEL_RE_COMM_STEP || ctx->model == RRRMC_MODEL_RE_COMM_RELU || ctx->model == RRRMC_MODEL_RE_SAT; }
+                                                ctx->model == RRRMC_MODEL_RE_COMM_STEP || ctx->model == RRRMC_MODEL_RE_COMM_RELU || ctx->model == RRRMC_MODEL_RE_SAT ||
+                                                ctx->model == RRRMC_MODEL_RE_COMM_QU; }
 inline int re_slice_of(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_RE_SK ? RE_SK : ctx->model == RRRMC_MODEL_RE_SKN ? RE_SKN :
                                                       ctx->model == RRRMC_MODEL_RE_PERC_STEP ? RE_PSTEP : ctx->model == RRRMC_MODEL_RE_PERC_LINEAR ? RE_PLIN :
-                                                      ctx->model == RRRMC_MODEL_RE_COMM_STEP ? RE_CSTEP : ctx->model == RRRMC_MODEL_RE_COMM_RELU ? RE_CRELU : ctx->model == RRRMC_MODEL_RE_SAT ? RE_SAT : RE_EMPTY; }
+                                                      ctx->model == RRRMC_MODEL_RE_COMM_STEP ? RE_CSTEP : ctx->model == RRRMC_MODEL_RE_COMM_RELU ? RE_CRELU : ctx->model == RRRMC_MODEL_RE_SAT ? RE_SAT :
+                                                      ctx->model == RRRMC_MODEL_RE_COMM_QU ? RE_CQU : RE_EMPTY; }
 inline int re_levels(int64_t M) { return (int)((M + 1) / 2); }          // allΔE(GraphRE): ceil(M / 2) values (RE.jl:208-213)
 
 // logcoshratio and fk (RE.jl:18-26), ΔElist (RE.jl:53-56) and the μ-energy table log(2 cosh(γ μ)) / β (RE.jl:90-93), host libm
@@ -34,7 +36,7 @@ ReParams re_params(rrrmc_ctx* ctx, double beta)
     if (ctx->model == RRRMC_MODEL_RE_SK) { P.Jb = ctx->q_Jb; P.Wk = (int)ctx->q_Wk; P.sN = std::sqrt((double)ctx->qNk); }
     if (ctx->model == RRRMC_MODEL_RE_SKN) { P.Jd = ctx->sk_J; P.slf = ctx->q_slf; P.smv = ctx->q_smv; P.scur = ctx->q_scur; }
     if (re_slice_of(ctx) == RE_PSTEP || re_slice_of(ctx) == RE_PLIN) P.pc = perc_params(ctx, M);
-    if (re_slice_of(ctx) == RE_CSTEP || re_slice_of(ctx) == RE_CRELU) P.cm = comm_params(ctx, M);
+    if (re_slice_of(ctx) == RE_CSTEP || re_slice_of(ctx) == RE_CRELU || re_slice_of(ctx) == RE_CQU) P.cm = comm_params(ctx, M);
     if (re_slice_of(ctx) == RE_SAT) P.sat = sat_table(ctx);
     P.tab = ctx->re_tab; P.etab = ctx->re_tab + M; P.ft = ctx->re_tab + 2 * M + 1;
     P.abi = ctx->q_spins; P.sp = ctx->re_sp; P.mu = ctx->re_mu; P.cls = ctx->q_cls; P.sv = ctx->q_sv; P.spos = ctx->q_spos; P.st = ctx->q_st;
@@ -70,6 +72,7 @@ int32_t re_run_init(rrrmc_ctx* ctx, double beta, bool cache)
         case RE_PLIN: hipLaunchKernelGGL(re_init_kernel<RE_PLIN>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CSTEP: hipLaunchKernelGGL(re_init_kernel<RE_CSTEP>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CRELU: hipLaunchKernelGGL(re_init_kernel<RE_CRELU>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
+        case RE_CQU: hipLaunchKernelGGL(re_init_kernel<RE_CQU>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_SAT: hipLaunchKernelGGL(re_init_kernel<RE_SAT>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
         default: hipLaunchKernelGGL(re_init_kernel<RE_EMPTY>, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, ctx->stream, P, cache ? 1 : 0); break;
     }
@@ -94,6 +97,7 @@ re_kernel_fn re_rrr_fn(int slice, bool lds, int L)
         case RE_PLIN: return lds ? re_rrr_for_L<true, RE_PLIN>(L) : re_rrr_for_L<false, RE_PLIN>(L);
         case RE_CSTEP: return lds ? re_rrr_for_L<true, RE_CSTEP>(L) : re_rrr_for_L<false, RE_CSTEP>(L);
         case RE_CRELU: return lds ? re_rrr_for_L<true, RE_CRELU>(L) : re_rrr_for_L<false, RE_CRELU>(L);
+        case RE_CQU: return lds ? re_rrr_for_L<true, RE_CQU>(L) : re_rrr_for_L<false, RE_CQU>(L);
         case RE_SAT: return lds ? re_rrr_for_L<true, RE_SAT>(L) : re_rrr_for_L<false, RE_SAT>(L);
         default: return lds ? re_rrr_for_L<true, RE_EMPTY>(L) : re_rrr_for_L<false, RE_EMPTY>(L);
     }
@@ -113,6 +117,7 @@ int32_t re_debug_check(rrrmc_ctx* ctx, const ReParams& P0, bool cache)
         case RE_PLIN: hipLaunchKernelGGL(re_check_kernel<RE_PLIN>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CSTEP: hipLaunchKernelGGL(re_check_kernel<RE_CSTEP>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_CRELU: hipLaunchKernelGGL(re_check_kernel<RE_CRELU>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
+        case RE_CQU: hipLaunchKernelGGL(re_check_kernel<RE_CQU>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         case RE_SAT: hipLaunchKernelGGL(re_check_kernel<RE_SAT>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
         default: hipLaunchKernelGGL(re_check_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); break;
     }
@@ -170,6 +175,7 @@ int32_t re_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, i
             case RE_PLIN: hipLaunchKernelGGL(re_standard_kernel<RE_PLIN>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             case RE_CSTEP: hipLaunchKernelGGL(re_standard_kernel<RE_CSTEP>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             case RE_CRELU: hipLaunchKernelGGL(re_standard_kernel<RE_CRELU>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
+            case RE_CQU: hipLaunchKernelGGL(re_standard_kernel<RE_CQU>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             case RE_SAT: hipLaunchKernelGGL(re_standard_kernel<RE_SAT>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
             default: hipLaunchKernelGGL(re_standard_kernel<RE_EMPTY>, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P); break;
         }
@@ -179,7 +185,7 @@ int32_t re_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, i
         // forces the thread build, RRRMC_RE_LDS=1 the LDS build (timing experiments, the builds' parity test)
         size_t lds = re_rrr_lds_bytes(ctx->N, ctx->qW, ctx->qNk);
         if (P.pc.ds) lds = ((lds + 7) & ~(size_t)7) + perc_lds_bytes(P.pc.rows, P.pc.PW);
-        if (P.cm.ds) lds = ((lds + 7) & ~(size_t)7) + comm_lds_bytes(P.cm.rows, P.cm.K2, P.cm.PW);          // the slices' Stabilities
+        if (P.cm.ds) lds = ((lds + 7) & ~(size_t)7) + comm_lds_bytes(P.cm.rows, P.cm.K2, P.cm.PW, slice == RE_CQU);          // the slices' Stabilities
         const char* no_lds = std::getenv("RRRMC_RE_NO_LDS");
         const char* want_lds = std::getenv("RRRMC_RE_LDS");
         // perceptron slices: the LDS build at every replica count (its update_cache! is spread over the wavefront; the thread build's is a
@@ -216,12 +222,12 @@ int32_t re_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind
     if (!out) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     const bool perc = slice_kind == RRRMC_RE_SLICE_PERC_STEP || slice_kind == RRRMC_RE_SLICE_PERC_LINEAR;
-    const bool comm = slice_kind == RRRMC_RE_SLICE_COMM_STEP || slice_kind == RRRMC_RE_SLICE_COMM_RELU;
+    const bool comm = slice_kind == RRRMC_RE_SLICE_COMM_STEP || slice_kind == RRRMC_RE_SLICE_COMM_RELU || slice_kind == RRRMC_RE_SLICE_COMM_QU;
     if (slice_kind != RRRMC_RE_SLICE_EMPTY && slice_kind != RRRMC_RE_SLICE_SK && slice_kind != RRRMC_RE_SLICE_SKN && slice_kind != RRRMC_RE_SLICE_SAT && !perc && !comm)
-        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind must be RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP, _PERC_LINEAR, _COMM_STEP, _COMM_RELU or _SAT, given: %d", slice_kind);
+        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind must be RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP, _PERC_LINEAR, _COMM_STEP, _COMM_RELU, _SAT or _COMM_QU, given: %d", slice_kind);
     if (Nk < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "Nk and R must be >= 1");
     if (perc) { const int32_t rcn = perc_check_n(Nk); if (rcn) return rcn; }
-    if (comm) { const int32_t rcn = comm_check_nk(Nk, slice_kind == RRRMC_RE_SLICE_COMM_RELU); if (rcn) return rcn; }
+    if (comm) { const int32_t rcn = comm_check_nk(Nk, slice_kind != RRRMC_RE_SLICE_COMM_STEP); if (rcn) return rcn; }
     if (M <= 2) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "M must be greater than 2, given: %lld", (long long)M);      // RE.jl:37
     if (M > kReMmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "M = %lld: the Robust Ensemble kernels cover M <= %d", (long long)M, kReMmax);
     if (Nk * M > 65535) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N = Nk*M = %lld is beyond the Robust Ensemble kernels (16-bit set members: N <= 65535)", (long long)(Nk * M));
@@ -235,7 +241,7 @@ int32_t re_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind
     ctx->model = slice_kind == RRRMC_RE_SLICE_SK ? RRRMC_MODEL_RE_SK : slice_kind == RRRMC_RE_SLICE_SKN ? RRRMC_MODEL_RE_SKN :
                  slice_kind == RRRMC_RE_SLICE_PERC_STEP ? RRRMC_MODEL_RE_PERC_STEP : slice_kind == RRRMC_RE_SLICE_PERC_LINEAR ? RRRMC_MODEL_RE_PERC_LINEAR :
                  slice_kind == RRRMC_RE_SLICE_COMM_STEP ? RRRMC_MODEL_RE_COMM_STEP : slice_kind == RRRMC_RE_SLICE_COMM_RELU ? RRRMC_MODEL_RE_COMM_RELU :
-                 slice_kind == RRRMC_RE_SLICE_SAT ? RRRMC_MODEL_RE_SAT : RRRMC_MODEL_RE_EMPTY;
+                 slice_kind == RRRMC_RE_SLICE_SAT ? RRRMC_MODEL_RE_SAT : slice_kind == RRRMC_RE_SLICE_COMM_QU ? RRRMC_MODEL_RE_COMM_QU : RRRMC_MODEL_RE_EMPTY;
     ctx->N = Nk * M; ctx->K = 0; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = Nk; ctx->qM = M; ctx->qW = 2 * ((Nk * M + 63) / 64); ctx->q_Wk = 2 * ((Nk + 63) / 64);
     ctx->device = device; ctx->replica0 = replica0;

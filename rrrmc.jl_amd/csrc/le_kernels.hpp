@@ -104,7 +104,7 @@ __global__ __launch_bounds__(kReInitThreads) void le_init_kernel(LeParams P, int
     } else if constexpr (kPercSlice<SLICE>) {
         perc_init_rows<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, Nk, N, s_n);          // (row 0, the centre: built, never used)
     } else if constexpr (kCommSlice<SLICE>) {
-        comm_init_rows<SLICE == RE_CRELU>(P.cm, comm_view(P.cm, r), sp, Nk, N, s_n);          // (likewise)
+        comm_init_rows<comm_kind_of_slice(SLICE)>(P.cm, comm_view<comm_kind_of_slice(SLICE)>(P.cm, r), sp, Nk, N, s_n);          // (likewise)
     } else if constexpr (SLICE == RE_SAT) {
         sat_init_rows(P.sat, sp, Nk, 1, rows, s_n);
     }
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
         __syncthreads();
     }
     if constexpr (LDS && kCommSlice<SLICE>) {
-        const int nm = rows * (int)comm_mk_row(P.cm.K2, P.cm.PW), nd = rows * (int)comm_ds_row(P.cm.K2, P.cm.PW);  // mask words, stabilities
+        const int nm = rows * (int)comm_mk_row(P.cm.K2, P.cm.PW, comm_kind_of_slice(SLICE) == CK_QU), nd = rows * (int)comm_ds_row(P.cm.K2, P.cm.PW, comm_kind_of_slice(SLICE) == CK_QU);  // mask words, stabilities
         pv.mk = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(le_lds) + ((le_rrr_lds_bytes(N, P.W, Nk) + 7) & ~(size_t)7));
         pv.ds = reinterpret_cast<int16_t*>(pv.mk + nm);
         for (int i = (int)threadIdx.x; i < nm; i += (int)blockDim.x) pv.mk[i] = g_pv.mk[i];
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
         const int move = sv[(size_t)kc * N + (size_t)mulhi64(uu, (uint64_t)t[kc])];
         const int i = move / rows, km = move - i * rows, xm = km * Nk + i;
         // delta_energy_residual (LE.jl:276-290): 0.0 for the centre, the replica slice's delta_energy (not divided by M)
-        const double dE1 = km == 0 ? 0.0 : re_residual<SLICE>(v, pv, xm, km, i);
+        const double dE1 = km == 0 ? 0.0 : re_residual<SLICE, LDS>(v, pv, xm, km, i);
 
         bool acc = false;
         if (acc_rate < P.staged_thr) {
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
     }
     if constexpr (LDS && kCommSlice<SLICE>) {
         __syncthreads();
-        const int nm = rows * (int)comm_mk_row(P.cm.K2, P.cm.PW), nd = rows * (int)comm_ds_row(P.cm.K2, P.cm.PW);
+        const int nm = rows * (int)comm_mk_row(P.cm.K2, P.cm.PW, comm_kind_of_slice(SLICE) == CK_QU), nd = rows * (int)comm_ds_row(P.cm.K2, P.cm.PW, comm_kind_of_slice(SLICE) == CK_QU);
         for (int i = (int)threadIdx.x; i < nm; i += (int)blockDim.x) g_pv.mk[i] = pv.mk[i];
         for (int i = (int)threadIdx.x; i < nd; i += (int)blockDim.x) g_pv.ds[i] = pv.ds[i];
     }
@@ -546,7 +546,7 @@ __global__ __launch_bounds__(64) void le_check_kernel(LeParams P, int cache)
             }
     }
     if constexpr (kPercSlice<SLICE>) bad = bad || perc_state_bad<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, 1, Nk, N);
-    if constexpr (kCommSlice<SLICE>) bad = bad || comm_state_bad<SLICE == RE_CRELU>(P.cm, comm_view(P.cm, r), sp, 1, Nk, N);
+    if constexpr (kCommSlice<SLICE>) bad = bad || comm_state_bad<comm_kind_of_slice(SLICE)>(P.cm, comm_view<comm_kind_of_slice(SLICE)>(P.cm, r), sp, 1, Nk, N);
     if (cache) {
         int cnt[2 * kLeLmax];
         for (int k = 0; k < 2 * L; ++k) cnt[k] = 0;

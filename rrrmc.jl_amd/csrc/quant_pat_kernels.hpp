@@ -1,5 +1,5 @@
-// gfx950 kernels for GraphQuant over pattern-machine slices — GraphQPercStepT, GraphQPercLinearT, GraphQCommStepT, GraphQCommReLUT
-// (src/QAliases.jl:85-159): M Suzuki-Trotter slices of one binary perceptron or committee machine, all on one pattern matrix, coupled along
+// gfx950 kernels for GraphQuant over pattern-machine slices — GraphQPercStepT, GraphQPercLinearT, GraphQCommStepT, GraphQCommReLUT,
+// GraphQCommQuT (src/QAliases.jl:85-181): M Suzuki-Trotter slices of one binary perceptron or committee machine, all on one pattern matrix, coupled along
 // the Trotter axis by GraphQT{fourK} (src/graphs/QT.jl:42-122).
 //
 // Semantics (QT.jl).  Sites are GraphQuant's, x = k Nk + i (slice-major already: no working copy).  energy = energy(GraphQT) + Σ_k
@@ -24,7 +24,7 @@
 
 namespace rrrmc {
 
-enum QuantPat { QP_PSTEP = 3, QP_PLIN = 4, QP_CSTEP = 5, QP_CRELU = 6 };       // the slice kinds of the C ABI (RRRMC_RE_SLICE_*)
+enum QuantPat { QP_PSTEP = 3, QP_PLIN = 4, QP_CSTEP = 5, QP_CRELU = 6, QP_CQU = 9 };       // the slice kinds of the C ABI (RRRMC_RE_SLICE_*)
 template <int KIND> constexpr bool qp_perc = KIND == QP_PSTEP || KIND == QP_PLIN;
 
 struct QuantPatParams {
@@ -52,19 +52,19 @@ struct PatSlices {
     __device__ __forceinline__ PatSlices(const Params& Q, int r)
     {
         if constexpr (qp_perc<KIND>) { w = perc_view(Q.pc, r); rows = Q.pc.rows; }
-        else { w = comm_view(Q.cm, r); rows = Q.cm.rows; }
+        else { w = comm_view<comm_kind_of_slice(KIND)>(Q.cm, r); rows = Q.cm.rows; }
         g = w;
     }
     // 64-bit words of masks and 16-bit stabilities of the replica's `rows` slices
     __device__ __forceinline__ int n_mask() const
     {
         if constexpr (qp_perc<KIND>) return 2 * rows * w.PW;
-        else return rows * (int)comm_mk_row(w.K2, w.PW);
+        else return rows * (int)comm_mk_row(w.K2, w.PW, KIND == QP_CQU);
     }
     __device__ __forceinline__ int n_ds() const
     {
         if constexpr (qp_perc<KIND>) return rows * 64 * w.PW;
-        else return rows * (int)comm_ds_row(w.K2, w.PW);
+        else return rows * (int)comm_ds_row(w.K2, w.PW, KIND == QP_CQU);
     }
     __device__ __forceinline__ void attach(uint32_t* lds)
     {
@@ -103,23 +103,23 @@ struct PatSlices {
         const int k = slice_of(move, v.Nk, v.nk_magic, v.wide), i = move - k * v.Nk, s = sbit(v.sp, move);
         if constexpr (KIND == QP_PSTEP) return perc_residual<false>(w, k, i, s) / (double)v.M;
         else if constexpr (KIND == QP_PLIN) return perc_residual<true>(w, k, i, s) / (double)v.M;
-        else return comm_residual<KIND == QP_CRELU>(w, k, i, s) / (double)v.M;
+        else return comm_residual<comm_kind_of_slice(KIND), WAVE>(w, k, i, s) / (double)v.M;
     }
     __device__ __forceinline__ void update(const RrrView& v, int move) const          // after the bit flip
     {
         const int k = slice_of(move, v.Nk, v.nk_magic, v.wide), i = move - k * v.Nk, s = sbit(v.sp, move);
         if constexpr (qp_perc<KIND>) perc_update<KIND == QP_PLIN, WAVE>(w, k, i, s);
-        else comm_update<KIND == QP_CRELU, WAVE>(w, k, i, s);
+        else comm_update<comm_kind_of_slice(KIND), WAVE>(w, k, i, s);
     }
 };
 // bytes of LDS attach() uses with STAGE (8 for the alignment of the mask words)
-inline size_t quant_pat_stage_bytes(bool perc, int64_t M, int64_t K2, int64_t PW) { return 8 + (perc ? perc_lds_bytes(M, PW) : comm_lds_bytes(M, K2, PW)); }
+inline size_t quant_pat_stage_bytes(bool perc, int64_t M, int64_t K2, int64_t PW, bool qu) { return 8 + (perc ? perc_lds_bytes(M, PW) : comm_lds_bytes(M, K2, PW, qu)); }
 // energy(X1[k], C1[k]) of the slice that starts at bit `off`, recomputed from the configuration
 template <int KIND>
 __device__ __forceinline__ double pat_row_energy(const QuantPatParams& Q, const uint32_t* sp, int off, int Nk, int Nbits)
 {
     if constexpr (qp_perc<KIND>) return perc_row_energy<KIND == QP_PLIN>(Q.pc, sp, off, Nk, Nbits);
-    else return comm_row_energy<KIND == QP_CRELU>(Q.cm, sp, off, Nbits);
+    else return comm_row_energy<comm_kind_of_slice(KIND)>(Q.cm, sp, off, Nbits);
 }
 
 // the two samplers over these slices, one thread per replica ...
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(kInitThreads) void quant_pat_init_kernel(RrrParams 
         atomicAdd(reinterpret_cast<unsigned long long*>(&s_n0), (unsigned long long)n0);
     }
     if constexpr (qp_perc<KIND>) perc_init_rows<KIND == QP_PLIN>(Q.pc, perc_view(Q.pc, r), v.sp, Nk, 32 * P.W, s_slice);
-    else comm_init_rows<KIND == QP_CRELU>(Q.cm, comm_view(Q.cm, r), v.sp, Nk, 32 * P.W, s_slice);
+    else comm_init_rows<comm_kind_of_slice(KIND)>(Q.cm, comm_view<comm_kind_of_slice(KIND)>(Q.cm, r), v.sp, Nk, 32 * P.W, s_slice);
     // classes of this thread's block of spins, then the exclusive scan and the fills (as rrr_init_coop_kernel)
     const int per = (N + kInitThreads - 1) / kInitThreads, x0 = tid * per, x1 = x0 + per < N ? x0 + per : N;
     int cnt[4] = {0, 0, 0, 0};
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(64) void quant_pat_check_kernel(RrrParams P, QuantP
     const int Nk = P.Nk, M = P.M, Nbits = 32 * P.W;
     bool bad;
     if constexpr (qp_perc<KIND>) bad = perc_state_bad<KIND == QP_PLIN>(Q.pc, perc_view(Q.pc, r), sp, 0, Nk, Nbits);
-    else bad = comm_state_bad<KIND == QP_CRELU>(Q.cm, comm_view(Q.cm, r), sp, 0, Nk, Nbits);
+    else bad = comm_state_bad<comm_kind_of_slice(KIND)>(Q.cm, comm_view<comm_kind_of_slice(KIND)>(Q.cm, r), sp, 0, Nk, Nbits);
     long long n0 = 0;
     for (int i = 0; i < Nk; ++i) {
         int sj = sbit(sp, i + (M - 1) * Nk);

@@ -25,9 +25,10 @@ namespace rrrmc {
 enum ReSlice { RE_EMPTY = 0, RE_SK = 1, RE_SKN = 2,          // GraphEmpty (Graph0RE), binary GraphSK (GraphSKRE), GraphSKNormal
                RE_PSTEP = 3, RE_PLIN = 4,                    // GraphPercStep (GraphPercStepRE), GraphPercLinear (GraphPercLinearRE)
                RE_CSTEP = 5, RE_CRELU = 6,                   // GraphCommStep (GraphCommStepRE), GraphCommReLU (GraphCommReLURE)
-               RE_SAT = 8 };                                 // GraphSAT (GraphSATRE); 7 is unassigned, as in the ABI
+               RE_SAT = 8,                                   // GraphSAT (GraphSATRE); 7 is unassigned, as in the ABI
+               RE_CQU = 9 };                                 // GraphCommQu (GraphCommQuRE)
 template <int SLICE> constexpr bool kPercSlice = SLICE == RE_PSTEP || SLICE == RE_PLIN;
-template <int SLICE> constexpr bool kCommSlice = SLICE == RE_CSTEP || SLICE == RE_CRELU;
+template <int SLICE> constexpr bool kCommSlice = SLICE == RE_CSTEP || SLICE == RE_CRELU || SLICE == RE_CQU;
 // slices whose state is a pure function of the configuration, updated once per accepted move by the whole wavefront in the LDS builds
 // (a K-SAT slice is not one: like the binary SK slice it keeps no state, its residual is recomputed from the spins by the worker thread)
 template <int SLICE> constexpr bool kWaveSlice = kPercSlice<SLICE> || kCommSlice<SLICE>;
@@ -38,7 +39,7 @@ struct ReParams {
     const uint32_t* Jb; int Wk; double sN;                  // binary GraphSK: rows of J as 32-bit words, sqrt(Nk)
     const double* Jd;                                       // GraphSKNormal: [Nk][Nk]
     PercParams pc;                                          // perceptron slices: the shared patterns, every slice's Stabilities
-    CommParams cm;                                          // committee machine slices: the same for GraphCommStep / GraphCommReLU
+    CommParams cm;                                          // committee machine slices: the same for GraphCommStep / GraphCommReLU / GraphCommQu
     SatTable sat;                                           // K-SAT slices: the shared occurrence program (no per-slice state)
     double* slf;                                            // [R][2][M][Nk]  every slice's lfields / lfields_last (SK.jl:212-276)
     int32_t* smv;                                           // [R][M]         move_last of every slice (-1 = none)
@@ -99,7 +100,7 @@ __device__ __forceinline__ void re_slice_update(const RrrView& v, int x)
     if constexpr (SLICE == RE_SKN) skn_update(v, x);
 }
 // the same two with the perceptron slices (perc_kernels.hpp), whose state is not part of the RrrView; WAVE: the wavefront-wide update
-template <int SLICE>
+template <int SLICE, bool WAVE = false>
 __device__ __forceinline__ double re_residual(const RrrView& v, const PercView& pv, int x, int k, int i)
 {
     if constexpr (kPercSlice<SLICE>) return perc_residual<SLICE == RE_PLIN>(pv, k, i, sbit(v.sp, x));
@@ -111,21 +112,22 @@ __device__ __forceinline__ void re_slice_update(const RrrView& v, const PercView
     if constexpr (kPercSlice<SLICE>) perc_update<SLICE == RE_PLIN, WAVE>(pv, k, i, sbit(v.sp, x));
     else re_slice_update<SLICE>(v, x);
 }
-// ... and with the committee machine slices (comm_kernels.hpp)
-template <int SLICE>
+// ... and with the committee machine slices (comm_kernels.hpp); WAVE: all 64 lanes call it with identical values (GraphCommQu shares
+// the patterns among them)
+template <int SLICE, bool WAVE = false>
 __device__ __forceinline__ double re_residual(const RrrView& v, const CommView& cv, int x, int k, int i)
 {
     static_assert(kCommSlice<SLICE>, "a CommView goes with a committee machine slice");
-    return comm_residual<SLICE == RE_CRELU>(cv, k, i, sbit(v.sp, x));
+    return comm_residual<comm_kind_of_slice(SLICE), WAVE>(cv, k, i, sbit(v.sp, x));
 }
 template <int SLICE, bool WAVE>
 __device__ __forceinline__ void re_slice_update(const RrrView& v, const CommView& cv, int x, int k, int i)
 {
     static_assert(kCommSlice<SLICE>, "a CommView goes with a committee machine slice");
-    comm_update<SLICE == RE_CRELU, WAVE>(cv, k, i, sbit(v.sp, x));
+    comm_update<comm_kind_of_slice(SLICE), WAVE>(cv, k, i, sbit(v.sp, x));
 }
 // ... and with the K-SAT slices (sat_kernels.hpp): delta_energy from the row's spins, no update_cache!
-template <int SLICE>
+template <int SLICE, bool WAVE = false>
 __device__ __forceinline__ double re_residual(const RrrView& v, const SatTable& sv, int x, int /*k*/, int i)
 {
     static_assert(SLICE == RE_SAT, "a SatTable goes with a K-SAT slice");
@@ -141,7 +143,7 @@ template <int SLICE, class PP>
 __device__ __forceinline__ auto re_slice_view(const PP& P, int r)
 {
     if constexpr (SLICE == RE_SAT) return P.sat;
-    else if constexpr (kCommSlice<SLICE>) return comm_view(P.cm, r);
+    else if constexpr (kCommSlice<SLICE>) return comm_view<comm_kind_of_slice(SLICE)>(P.cm, r);
     else return perc_view(P.pc, r);
 }
 // class of ABI site j with spin bit s, for the group's μ = mub + σ: a + L up (DeltaE.jl:80-86 with lfields[j] = σ_j fk(mū), RE.jl:101)
@@ -179,7 +181,7 @@ __device__ inline double re_slice_energy(const ReParams& P, const RrrView& v, in
     } else if constexpr (kPercSlice<SLICE>) {
         return perc_row_energy<SLICE == RE_PLIN>(P.pc, v.sp, k * Nk, Nk, P.N);
     } else if constexpr (kCommSlice<SLICE>) {
-        return comm_row_energy<SLICE == RE_CRELU>(P.cm, v.sp, k * Nk, P.N);
+        return comm_row_energy<comm_kind_of_slice(SLICE)>(P.cm, v.sp, k * Nk, P.N);
     } else if constexpr (SLICE == RE_SAT) {
         return (double)sat_row_energy(P.sat, v.sp, k * Nk);
     } else {
@@ -267,7 +269,7 @@ __global__ __launch_bounds__(kReInitThreads) void re_init_kernel(ReParams P, int
     } else if constexpr (kPercSlice<SLICE>) {
         perc_init_rows<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, Nk, N, s_n);
     } else if constexpr (kCommSlice<SLICE>) {
-        comm_init_rows<SLICE == RE_CRELU>(P.cm, comm_view(P.cm, r), sp, Nk, N, s_n);
+        comm_init_rows<comm_kind_of_slice(SLICE)>(P.cm, comm_view<comm_kind_of_slice(SLICE)>(P.cm, r), sp, Nk, N, s_n);
     } else if constexpr (SLICE == RE_SAT) {
         sat_init_rows(P.sat, sp, Nk, 0, M, s_n);
     }
@@ -391,7 +393,7 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
         __syncthreads();
     }
     if constexpr (LDS && kCommSlice<SLICE>) {
-        const int nm = M * (int)comm_mk_row(P.cm.K2, P.cm.PW), nd = M * (int)comm_ds_row(P.cm.K2, P.cm.PW);     // mask words, stabilities
+        const int nm = M * (int)comm_mk_row(P.cm.K2, P.cm.PW, comm_kind_of_slice(SLICE) == CK_QU), nd = M * (int)comm_ds_row(P.cm.K2, P.cm.PW, comm_kind_of_slice(SLICE) == CK_QU);     // mask words, stabilities
         pv.mk = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(re_lds) + ((re_rrr_lds_bytes(N, P.W, Nk) + 7) & ~(size_t)7));
         pv.ds = reinterpret_cast<int16_t*>(pv.mk + nm);
         for (int i = (int)threadIdx.x; i < nm; i += (int)blockDim.x) pv.mk[i] = g_pv.mk[i];
@@ -528,7 +530,7 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
                 zp += f1 - f0;
             }
             const double c = z / zp;
-            const double dE1 = re_residual<SLICE>(v, pv, xm, km, i);      // delta_energy_residual, RE.jl:303-310
+            const double dE1 = re_residual<SLICE, LDS>(v, pv, xm, km, i);      // delta_energy_residual, RE.jl:303-310
             if (accept_c(c, -P.beta * dE1, q2, g)) {
                 sflip(sp, xm);                                             // spinflip!(X, C, move)
                 mu[i] = (int8_t)munew;
@@ -549,7 +551,7 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
             }
         } else {
             // direct branch: apply_move! (DeltaE.jl:232-295), undone by a second apply_move! on rejection
-            const double dE1 = re_residual<SLICE>(v, pv, xm, km, i);
+            const double dE1 = re_residual<SLICE, LDS>(v, pv, xm, km, i);
             for (int pass = 0; pass < 2; ++pass) {
                 sflip(sp, xm);
                 const int s_new = sbit(sp, xm);
@@ -606,7 +608,7 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
     }
     if constexpr (LDS && kCommSlice<SLICE>) {
         __syncthreads();
-        const int nm = M * (int)comm_mk_row(P.cm.K2, P.cm.PW), nd = M * (int)comm_ds_row(P.cm.K2, P.cm.PW);
+        const int nm = M * (int)comm_mk_row(P.cm.K2, P.cm.PW, comm_kind_of_slice(SLICE) == CK_QU), nd = M * (int)comm_ds_row(P.cm.K2, P.cm.PW, comm_kind_of_slice(SLICE) == CK_QU);
         for (int i = (int)threadIdx.x; i < nm; i += (int)blockDim.x) g_pv.mk[i] = pv.mk[i];
         for (int i = (int)threadIdx.x; i < nd; i += (int)blockDim.x) g_pv.ds[i] = pv.ds[i];
     }
@@ -704,7 +706,7 @@ __global__ __launch_bounds__(64) void re_check_kernel(ReParams P, int cache)
             }
     }
     if constexpr (kPercSlice<SLICE>) bad = bad || perc_state_bad<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, 0, Nk, N);
-    if constexpr (kCommSlice<SLICE>) bad = bad || comm_state_bad<SLICE == RE_CRELU>(P.cm, comm_view(P.cm, r), sp, 0, Nk, N);
+    if constexpr (kCommSlice<SLICE>) bad = bad || comm_state_bad<comm_kind_of_slice(SLICE)>(P.cm, comm_view<comm_kind_of_slice(SLICE)>(P.cm, r), sp, 0, Nk, N);
     if (cache) {
         int cnt[2 * (kReMmax / 2)];
         for (int k = 0; k < 2 * L; ++k) cnt[k] = 0;

@@ -500,7 +500,8 @@ inline bool chunk_layout(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODE
                                                        ctx->model == RRRMC_MODEL_RE_EMPTY || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_RE_SKN ||
                                                        ctx->model == RRRMC_MODEL_LE_EMPTY || ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_LE_SKN ||
                                                        (ctx->model >= RRRMC_MODEL_PERC_STEP && ctx->model <= RRRMC_MODEL_LE_COMM_RELU) ||
-                                                       ctx->model == RRRMC_MODEL_SAT || ctx->model == RRRMC_MODEL_RE_SAT || ctx->model == RRRMC_MODEL_LE_SAT; }
+                                                       ctx->model == RRRMC_MODEL_SAT || ctx->model == RRRMC_MODEL_RE_SAT || ctx->model == RRRMC_MODEL_LE_SAT ||
+                                                       ctx->model == RRRMC_MODEL_COMM_QU || ctx->model == RRRMC_MODEL_RE_COMM_QU || ctx->model == RRRMC_MODEL_LE_COMM_QU; }
 inline bool sparse_int_model(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_SPARSE_PM1 || ctx->model == RRRMC_MODEL_SPARSE_LEVELS; }
 inline double lv_to_f64(const rrrmc_ctx* ctx, long long units) { return (double)(units * ctx->lv_mul) / ctx->lv_div; }
 
@@ -1714,6 +1715,7 @@ int32_t rrrmc_re_energies(rrrmc_ctx* ctx, double* out)
         case RE_PLIN: hipLaunchKernelGGL(re_energies_kernel<RE_PLIN>, grid, blk, 0, ctx->stream, P); break;
         case RE_CSTEP: hipLaunchKernelGGL(re_energies_kernel<RE_CSTEP>, grid, blk, 0, ctx->stream, P); break;
         case RE_CRELU: hipLaunchKernelGGL(re_energies_kernel<RE_CRELU>, grid, blk, 0, ctx->stream, P); break;
+        case RE_CQU: hipLaunchKernelGGL(re_energies_kernel<RE_CQU>, grid, blk, 0, ctx->stream, P); break;
         case RE_SAT: hipLaunchKernelGGL(re_energies_kernel<RE_SAT>, grid, blk, 0, ctx->stream, P); break;
         default: hipLaunchKernelGGL(re_energies_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P); break;
     }
@@ -1742,7 +1744,11 @@ int32_t rrrmc_set_patterns(rrrmc_ctx* ctx, const uint64_t* xi, int64_t P)
 // ---- the binary committee machines: exported entry points (host_comm.hpp) ----
 int32_t rrrmc_ctx_create_comm(rrrmc_ctx** out, int64_t K1, int64_t K2, int32_t relu, int64_t R, int32_t device, uint32_t replica0)
 {
-    return comm_ctx_create(out, K1, K2, relu, R, device, replica0);
+    return comm_ctx_create(out, K1, K2, relu ? CK_RELU : CK_STEP, R, device, replica0);
+}
+int32_t rrrmc_ctx_create_comm_qu(rrrmc_ctx** out, int64_t K1, int64_t K2, int64_t R, int32_t device, uint32_t replica0)
+{
+    return comm_ctx_create(out, K1, K2, CK_QU, R, device, replica0);
 }
 
 int32_t rrrmc_set_comm_patterns(rrrmc_ctx* ctx, int64_t K2, const uint64_t* xi, const uint64_t* y, int64_t P)
@@ -1751,7 +1757,7 @@ int32_t rrrmc_set_comm_patterns(rrrmc_ctx* ctx, int64_t K2, const uint64_t* xi, 
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
     if (!is_comm(ctx) && !comm_slices(ctx) && !quant_pat_comm(ctx))
-        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_comm_patterns is for contexts made by rrrmc_ctx_create_comm, or by rrrmc_ctx_create_re / _le / _quant_pattern with a committee machine slice kind");
+        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_comm_patterns is for contexts made by rrrmc_ctx_create_comm / _comm_qu, or by rrrmc_ctx_create_re / _le / _quant_pattern with a committee machine slice kind");
     return comm_set_patterns(ctx, K2, xi, y, P, is_comm(ctx) ? 1 : is_le(ctx) ? ctx->qM + 1 : ctx->qM);
 }
 
@@ -1941,15 +1947,16 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
     if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
     const int32_t qpat = model == RRRMC_MODEL_QUANT_PERC_STEP ? RRRMC_RE_SLICE_PERC_STEP : model == RRRMC_MODEL_QUANT_PERC_LINEAR ? RRRMC_RE_SLICE_PERC_LINEAR
-                         : model == RRRMC_MODEL_QUANT_COMM_STEP ? RRRMC_RE_SLICE_COMM_STEP : model == RRRMC_MODEL_QUANT_COMM_RELU ? RRRMC_RE_SLICE_COMM_RELU : 0;
+                         : model == RRRMC_MODEL_QUANT_COMM_STEP ? RRRMC_RE_SLICE_COMM_STEP : model == RRRMC_MODEL_QUANT_COMM_RELU ? RRRMC_RE_SLICE_COMM_RELU
+                         : model == RRRMC_MODEL_QUANT_COMM_QU ? RRRMC_RE_SLICE_COMM_QU : 0;
     const bool quant = model == RRRMC_MODEL_QUANT_RRG || model == RRRMC_MODEL_QUANT_SK || model == RRRMC_MODEL_QUANT_SKN || model == RRRMC_MODEL_QUANT_F64 || qpat;
     const bool re = model == RRRMC_MODEL_RE_EMPTY || model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_RE_SKN || model == RRRMC_MODEL_RE_PERC_STEP || model == RRRMC_MODEL_RE_PERC_LINEAR ||
-                    model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_RE_COMM_RELU || model == RRRMC_MODEL_RE_SAT;
+                    model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_RE_COMM_RELU || model == RRRMC_MODEL_RE_SAT || model == RRRMC_MODEL_RE_COMM_QU;
     const bool le = model == RRRMC_MODEL_LE_EMPTY || model == RRRMC_MODEL_LE_SK || model == RRRMC_MODEL_LE_SKN || model == RRRMC_MODEL_LE_PERC_STEP || model == RRRMC_MODEL_LE_PERC_LINEAR ||
-                    model == RRRMC_MODEL_LE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_RELU || model == RRRMC_MODEL_LE_SAT;
+                    model == RRRMC_MODEL_LE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_RELU || model == RRRMC_MODEL_LE_SAT || model == RRRMC_MODEL_LE_COMM_QU;
     const bool sat = model == RRRMC_MODEL_SAT;
     const bool pc = model == RRRMC_MODEL_PERC_STEP || model == RRRMC_MODEL_PERC_LINEAR;
-    const bool cm = model == RRRMC_MODEL_COMM_STEP || model == RRRMC_MODEL_COMM_RELU;
+    const bool cm = model == RRRMC_MODEL_COMM_STEP || model == RRRMC_MODEL_COMM_RELU || model == RRRMC_MODEL_COMM_QU;
     if (cm && (K < 1 || N % K != 0)) {
         delete ctx;
         return fail(nullptr, RRRMC_ERR_INVALID_ARG, "a committee machine takes N = K1*K2 and K = K2 with N %% K2 == 0, given N = %lld, K = %lld", (long long)N, (long long)K);
@@ -1961,6 +1968,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                               : model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_STEP ? RRRMC_RE_SLICE_COMM_STEP
                               : model == RRRMC_MODEL_RE_COMM_RELU || model == RRRMC_MODEL_LE_COMM_RELU ? RRRMC_RE_SLICE_COMM_RELU
                               : model == RRRMC_MODEL_RE_SAT || model == RRRMC_MODEL_LE_SAT ? RRRMC_RE_SLICE_SAT
+                              : model == RRRMC_MODEL_RE_COMM_QU || model == RRRMC_MODEL_LE_COMM_QU ? RRRMC_RE_SLICE_COMM_QU
                                                                                                        : RRRMC_RE_SLICE_EMPTY;
     ctx->model = quant ? RRRMC_MODEL_QUANT_RRG : model; ctx->K = K; ctx->R = R; ctx->replica0 = replica0; ctx->device = device_ids[0];
     ctx->N = quant || re ? N * M : le ? N * (M + 1) : N;
@@ -1983,6 +1991,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : le ? rrrmc_ctx_create_le(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : pc ? rrrmc_ctx_create_perc(&c, N, model == RRRMC_MODEL_PERC_LINEAR, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : sat ? rrrmc_ctx_create_sat(&c, N, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : model == RRRMC_MODEL_COMM_QU ? rrrmc_ctx_create_comm_qu(&c, N / K, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : cm ? rrrmc_ctx_create_comm(&c, N / K, K, model == RRRMC_MODEL_COMM_RELU, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                                                             : rrrmc_ctx_create(&c, model, N, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0);
         if (rc) {

@@ -460,7 +460,7 @@ class GraphSK(_DeviceGraph):
 
 
 # RRRMC_RE_SLICE_* kind of a pattern machine -> the rrrmc_ctx_create_multi selector of the GraphQuant over it (RRRMC_MODEL_QUANT_PERC_STEP ...)
-_QUANT_PAT_MODELS = {3: 29, 4: 30, 5: 31, 6: 32}
+_QUANT_PAT_MODELS = {3: 29, 4: 30, 5: 31, 6: 32, 9: 39}
 
 
 class GraphQuant(_DeviceGraph):
@@ -470,8 +470,8 @@ class GraphQuant(_DeviceGraph):
     As the in-tree aliases do (src/QAliases.jl:43-67) the disorder is generated ONCE and shared by all slices:
     ``GraphQuant(X1, M, Γ, β)`` with ``X1`` a ``GraphRRG`` / ``GraphEA`` (±J), or a binary ``GraphSK`` — the reference's
     ``GraphQSKT(Nk, M, Γ, β)`` (src/QAliases.jl:34-43), the graph of ``scripts.jl:test_QIsing``.  ``N = Nk * M`` spins, slice-major.
-    ``ET = Float64``.  ``X1`` may also be a pattern machine — ``GraphPercStep``, ``GraphPercLinear``, ``GraphCommStep``, ``GraphCommReLU`` — whose
-    pattern matrix all slices share: the reference's ``GraphQPercStepT`` ... (src/QAliases.jl:85-159).
+    ``ET = Float64``.  ``X1`` may also be a pattern machine — ``GraphPercStep``, ``GraphPercLinear``, ``GraphCommStep``, ``GraphCommReLU``,
+    ``GraphCommQu`` — whose pattern matrix all slices share: the reference's ``GraphQPercStepT`` ... (src/QAliases.jl:85-181).
     """
     model_kind = 3          # RRRMC_MODEL_QUANT_RRG
     energy_dtype = np.float64
@@ -489,7 +489,8 @@ class GraphQuant(_DeviceGraph):
     def _multi_args(self):
         # a GraphQuant over other slice families is made per device by rrrmc_ctx_create_quant_skn / _sk / _f64: the header's selectors
         # RRRMC_MODEL_QUANT_SKN / _SK / _F64
-        # ... and RRRMC_MODEL_QUANT_PERC_STEP / _PERC_LINEAR / _COMM_STEP / _COMM_RELU = 29 .. 32 (K = K2) for the pattern machines
+        # ... and RRRMC_MODEL_QUANT_PERC_STEP / _PERC_LINEAR / _COMM_STEP / _COMM_RELU = 29 .. 32 and _COMM_QU = 39 (K = K2) for the pattern
+        # machines
         if self.pat_slices:
             return _QUANT_PAT_MODELS[self.pat_slices], self.Nk, self.K, self.M
         return (9 if self.skn_slices else 8 if self.sk_slices else 10 if self.f64_slices else 3), self.Nk, self.K, self.M
@@ -646,7 +647,7 @@ class GraphPercLinear(_GraphPerc):
 class _GraphComm(_DeviceGraph):
     """A two-layer binary committee machine: ``K2`` hidden units of ``K1`` binary synapses each, N = K1 K2 (unit k owns synapses
     k K1 .. (k + 1) K1 - 1), trained on ``P`` random ±1 patterns.  ``xi`` holds the patterns as P rows of ceil(N/64) chunks (the layout of
-    ``GraphPercStep``), ``y`` (GraphCommReLU only) the P labels as ceil(P/64) words.  ``fc=True`` draws each pattern over K1 inputs and
+    ``GraphPercStep``), ``y`` (GraphCommReLU and GraphCommQu) the P labels as ceil(P/64) words.  ``fc=True`` draws each pattern over K1 inputs and
     repeats its columns K2 times (CommStep.jl:85-93).  ``seed`` names the draw (``rrrmc_gen_comm_patterns``, host only);
     ``from_patterns(K2, ξ[, y])`` takes an explicit P x N 0/1 matrix (and P labels), as ``GraphCommStep(K2, ξ, ξv)`` does."""
     relu = False
@@ -671,7 +672,7 @@ class _GraphComm(_DeviceGraph):
     def _check_k(cls, K1, K2):
         par = "even" if cls.relu else "odd"
         if K1 < 1 or K1 % 2 != (0 if cls.relu else 1):
-            raise ValueError("K1 must be %s, given: %d" % (par, K1))            # CommStep.jl:65-66, CommReLU.jl:68-69
+            raise ValueError("K1 must be %s, given: %d" % (par, K1))            # CommStep.jl:65-66, CommReLU.jl:68-69, CommQu.jl:72-73
         if K2 < 1 or K2 % 2 != (0 if cls.relu else 1):
             raise ValueError("K2 must be %s, given: %d" % (par, K2))
 
@@ -682,7 +683,7 @@ class _GraphComm(_DeviceGraph):
     @classmethod
     def from_patterns(cls, K2, xi, y=None):
         """the graph of an explicit pattern matrix: ``xi`` is a P x N array of 0/1 (or booleans), N a multiple of K2; ``y`` the P labels
-        (0/1) of a GraphCommReLU, and nothing for a GraphCommStep"""
+        (0/1) of a GraphCommReLU or GraphCommQu, and nothing for a GraphCommStep"""
         K2 = int(K2)
         xi = np.asarray(xi)
         if xi.ndim != 2 or xi.shape[0] < 1 or xi.shape[1] < 1:
@@ -695,7 +696,7 @@ class _GraphComm(_DeviceGraph):
         cls._check_k(N // K2, K2)
         if cls.relu:
             if y is None:
-                raise ValueError("a GraphCommReLU needs the labels y")
+                raise ValueError("a %s needs the labels y" % cls.__name__)
             y = np.asarray(y)
             if y.shape != (P,):
                 raise ValueError("y must hold P = %d labels, given an array of shape %s" % (P, y.shape))      # CommReLU.jl:67
@@ -713,7 +714,7 @@ class _GraphComm(_DeviceGraph):
         return unpack_patterns(self.xi, self.N)
 
     def labels(self):
-        """the P labels of 0/1 (GraphCommReLU); None for GraphCommStep"""
+        """the P labels of 0/1 (GraphCommReLU, GraphCommQu); None for GraphCommStep"""
         return None if self.y is None else unpack_patterns(self.y.reshape(1, -1), self.P)[0]
 
 
@@ -733,6 +734,19 @@ class GraphCommReLU(_GraphComm):
     energy_dtype = np.int64
     relu = True
     __doc__ += _GraphComm.__doc__
+
+
+class GraphCommQu(_GraphComm):
+    """``GraphCommQu(K1, K2, P; fc)`` (src/graphs/CommQu.jl:80-101): hidden units that answer with the square of their stability, the first
+    K2/2 with weight +1 and the rest −1, K1 and K2 even, and a random label per pattern (drawn as GraphCommReLU's: CommQu.gen_ξ is
+    CommReLU's); the energy is the number of misclassified patterns.  ``ET = Int``."""
+    model_kind = 36         # RRRMC_MODEL_COMM_QU
+    energy_dtype = np.int64
+    relu = True             # even K1, K2 and labelled patterns, as GraphCommReLU
+    __doc__ += _GraphComm.__doc__
+
+    def _create(self, ctx, R, device, replica0):
+        check(lib().rrrmc_ctx_create_comm_qu(ctx, self.K1, self.K2, R, device, replica0))
 
 
 class GraphSAT(_DeviceGraph):
@@ -817,6 +831,8 @@ class GraphSAT(_DeviceGraph):
 def _ensemble_slice_kind(slice_graph):
     if isinstance(slice_graph, GraphSAT):
         return 8            # RRRMC_RE_SLICE_SAT (7 is unassigned)
+    if isinstance(slice_graph, GraphCommQu):
+        return 9            # RRRMC_RE_SLICE_COMM_QU
     return (0 if slice_graph is None else 1 if isinstance(slice_graph, GraphSK) else 2 if isinstance(slice_graph, GraphSKNormal)
             else 3 if isinstance(slice_graph, GraphPercStep) else 4 if isinstance(slice_graph, GraphPercLinear)
             else 5 if isinstance(slice_graph, GraphCommStep) else 6)
@@ -851,6 +867,11 @@ def GraphCommReLURE(*args, fc=False, seed=DEFAULT_SEED):
     return _pattern_ensemble(GraphRobustEnsemble, GraphCommReLU, "K1, K2, P", args, fc=fc, seed=seed)
 
 
+def GraphCommQuRE(*args, fc=False, seed=DEFAULT_SEED):
+    """``GraphCommQuRE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommQuRE(X::GraphCommQu, M, γ, β)`` (src/REAliases.jl:168-186)."""
+    return _pattern_ensemble(GraphRobustEnsemble, GraphCommQu, "K1, K2, P", args, fc=fc, seed=seed)
+
+
 def GraphCommStepLE(*args, fc=False, seed=DEFAULT_SEED):
     """``GraphCommStepLE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommStepLE(X::GraphCommStep, M, γ, β)`` (src/LEAliases.jl): a Local Entropy
     ensemble of M committee machines and a centre that share one pattern matrix."""
@@ -860,6 +881,11 @@ def GraphCommStepLE(*args, fc=False, seed=DEFAULT_SEED):
 def GraphCommReLULE(*args, fc=False, seed=DEFAULT_SEED):
     """``GraphCommReLULE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommReLULE(X::GraphCommReLU, M, γ, β)`` (src/LEAliases.jl)."""
     return _pattern_ensemble(GraphLocalEntropy, GraphCommReLU, "K1, K2, P", args, fc=fc, seed=seed)
+
+
+def GraphCommQuLE(*args, fc=False, seed=DEFAULT_SEED):
+    """``GraphCommQuLE(K1, K2, P, M, γ, β; fc)`` / ``GraphCommQuLE(X::GraphCommQu, M, γ, β)`` (src/LEAliases.jl:168-186)."""
+    return _pattern_ensemble(GraphLocalEntropy, GraphCommQu, "K1, K2, P", args, fc=fc, seed=seed)
 
 
 def _pattern_quant(G, sig, args, **kw):
@@ -887,6 +913,11 @@ def GraphQCommStepT(*args, fc=False, seed=DEFAULT_SEED):
 def GraphQCommReLUT(*args, fc=False, seed=DEFAULT_SEED):
     """``GraphQCommReLUT(K1, K2, P, M, Γ, β; fc)`` / ``GraphQCommReLUT(X::GraphCommReLU, M, Γ, β)`` (src/QAliases.jl:139-159)."""
     return _pattern_quant(GraphCommReLU, "K1, K2, P", args, fc=fc, seed=seed)
+
+
+def GraphQCommQuT(*args, fc=False, seed=DEFAULT_SEED):
+    """``GraphQCommQuT(K1, K2, P, M, Γ, β; fc)`` / ``GraphQCommQuT(X::GraphCommQu, M, Γ, β)`` (src/QAliases.jl:161-181)."""
+    return _pattern_quant(GraphCommQu, "K1, K2, P", args, fc=fc, seed=seed)
 
 
 def GraphSATRE(*args, seed=DEFAULT_SEED):
@@ -949,14 +980,14 @@ class GraphRobustEnsemble(_DeviceGraph):
             raise ValueError("M must be greater than 2, given: %d" % M)                  # RE.jl:37
         if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT)):
             raise TypeError("the slices of a GraphRobustEnsemble are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, "
-                            "GraphCommStep, GraphCommReLU or GraphSAT")
+                            "GraphCommStep, GraphCommReLU, GraphCommQu or GraphSAT")
         if slice_graph is not None and slice_graph.N != int(Nk):
             raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
         self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
         self.N = self.Nk * self.M
         self.X1 = slice_graph
         self.slice_kind = _ensemble_slice_kind(slice_graph)
-        self.model_kind = (11, 12, 13, 19, 20, 25, 26, None, 34)[self.slice_kind]  # RRRMC_MODEL_RE_EMPTY / _SK / _SKN / _PERC_* / _COMM_* / _SAT
+        self.model_kind = (11, 12, 13, 19, 20, 25, 26, None, 34, 37)[self.slice_kind]  # RRRMC_MODEL_RE_EMPTY / _SK / _SKN / _PERC_* / _COMM_* / _SAT / _COMM_QU
         self.J = getattr(slice_graph, "J", None)
         self._engine = None                             # the Engine running this graph: REenergies reads the live configuration there
 
@@ -1014,7 +1045,7 @@ class GraphLocalEntropy(_DeviceGraph):
             raise ValueError("M must be greater than 2, given: %d" % M)                  # LE.jl:24
         if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT)):
             raise TypeError("the slices of a GraphLocalEntropy are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, "
-                            "GraphCommStep, GraphCommReLU or GraphSAT")
+                            "GraphCommStep, GraphCommReLU, GraphCommQu or GraphSAT")
         if slice_graph is not None and slice_graph.N != int(Nk):
             raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
         self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
@@ -1022,7 +1053,7 @@ class GraphLocalEntropy(_DeviceGraph):
         self.N = self.Nk * (self.M + 1)
         self.X1 = slice_graph
         self.slice_kind = _ensemble_slice_kind(slice_graph)
-        self.model_kind = (14, 15, 16, 21, 22, 27, 28, None, 35)[self.slice_kind]  # RRRMC_MODEL_LE_EMPTY / _SK / _SKN / _PERC_* / _COMM_* / _SAT
+        self.model_kind = (14, 15, 16, 21, 22, 27, 28, None, 35, 38)[self.slice_kind]  # RRRMC_MODEL_LE_EMPTY / _SK / _SKN / _PERC_* / _COMM_* / _SAT / _COMM_QU
         self.J = getattr(slice_graph, "J", None)
         self._engine = None                             # the Engine running this graph: the observables read the live configuration there
 
