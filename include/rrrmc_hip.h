@@ -107,7 +107,13 @@ enum rrrmc_model {
     RRRMC_MODEL_COMM_QU = 36,        /* GraphCommQu(K1, K2, P): energy = the number of misclassified patterns (reported as Float64) */
     RRRMC_MODEL_RE_COMM_QU = 37,     /* GraphCommQuRE */
     RRRMC_MODEL_LE_COMM_QU = 38,     /* GraphCommQuLE */
-    RRRMC_MODEL_QUANT_COMM_QU = 39   /* GraphQCommQuT (the contexts report RRRMC_MODEL_QUANT_RRG) */
+    RRRMC_MODEL_QUANT_COMM_QU = 39,  /* GraphQCommQuT (the contexts report RRRMC_MODEL_QUANT_RRG) */
+    /* GraphTopologicalLocalEntropy (src/graphs/TLE.jl, src/TLEAliases.jl): the models of contexts made by rrrmc_ctx_create_tle, and the
+       selectors of rrrmc_ctx_create_multi for it (N = Nk, M; K ignored).  40 .. 43 are unassigned. */
+    RRRMC_MODEL_TLE_EMPTY = 44,  /* Graph0TLE */
+    RRRMC_MODEL_TLE_SK = 45,     /* GraphSKTLE */
+    RRRMC_MODEL_TLE_SKN = 46,    /* GraphTopologicalLocalEntropy(Nk, M, gamma, lambda, beta, GraphSKNormal, J) */
+    RRRMC_MODEL_TLE_SAT = 47     /* GraphSATTLE */
 };
 
 /* slice families of rrrmc_ctx_create_re */
@@ -433,6 +439,45 @@ RRRMC_API int32_t rrrmc_le_distances(rrrmc_ctx *ctx, int64_t *out);
 /* Host-only (no device needed): dElist[L] = allDeltaE(GraphLE{M, gamma/beta}) (LE.jl:176-179), L = M/2 + 2 for even M and (M+1)/2 for odd M
  * (a buffer of M/2 + 2 entries always suffices). */
 RRRMC_API int32_t rrrmc_le_tables(int64_t M, double gamma, double beta, double *dElist);
+
+/* ---- GraphTopologicalLocalEntropy (src/graphs/TLE.jl; RRRMC_MODEL_TLE_*) -----------------------------------------
+ * The Local Entropy ensemble with a second, topological coupling over the slice graph's own neighbourhoods: the inner graph
+ * GraphTLE{M,gammaT,lambdaT} (gammaT = gamma / beta, lambdaT = lambda / beta, TLE.jl:390-396) keeps GraphLE's integer field lfields1 and
+ *   lfields2 = sigma_(i,k) sigma_c,i sum_{i2 in d(i)} sigma_c,i2 sigma_(i2,k) on replica site (i,k), the sum of those over k on centre i,
+ * with DeltaE0 = 2 gammaT lfields1 + 2 lambdaT lfields2 and energy(X0) = n gammaT + r lambdaT (integers n, r; TLE.jl:79-142, 301-311).  Sites,
+ * site order, residuals, the shared coupling set and what E leaves out (the centre's own energy) are GraphLocalEntropy's.  d(i), the
+ * neighbour lists, are neighbors(g0, i) of the slice graph: empty for GraphEmpty, all other sites ascending for GraphSK / GraphSKNormal,
+ * neighb[i] (first-appearance order) for GraphSAT.  allDeltaE has tens to hundreds of levels: L = |unique |DeltaE1 + DeltaE2|| with
+ * DeltaE2 = 2 d lambdaT for |d| <= M max|d(i)| (TLE.jl:335-347).
+ *   Limits (RRRMC_ERR_UNSUPPORTED): 3 <= M <= 31 (M <= 2: RRRMC_ERR_INVALID_ARG, the reference's check), N = Nk (M+1) <= 65 535,
+ *   2L <= 65 535, each slice kind's own limits, and R * 2L * N * 2 bytes of dense set storage <= 16 GiB per device.
+ * rrrmc_ctx_create_tle: slice_kind RRRMC_RE_SLICE_EMPTY / _SK / _SKN / _SAT (the other kinds: RRRMC_ERR_UNSUPPORTED; 7 and values outside
+ * rrrmc_re_slice: RRRMC_ERR_INVALID_ARG); then the couplings or clauses (rrrmc_set_couplings_bits, rrrmc_set_couplings_dense,
+ * rrrmc_set_clauses), rrrmc_tle_set_topology and rrrmc_tle_set_params, in that order.  Samplers: rrrmc_rrr_mc_async (fourK ignored) and
+ * rrrmc_standard_mc_async / rrrmc_standard_mc_f64, with the resume, debug-check, timing, results, spin and snapshot entry points of the other
+ * models; rrrmc_le_energies (= TLEenergies, TLE.jl:437-453), rrrmc_le_cenergy and rrrmc_le_distances serve these contexts too.
+ * rrrmc_bkl_mc_async, rrrmc_wtm_mc_async and rrrmc_extremal_opt_async return RRRMC_ERR_UNSUPPORTED; rrrmc_rrr_cache (int8 class ids) is not
+ * served: use rrrmc_tle_cache. */
+RRRMC_API int32_t rrrmc_ctx_create_tle(rrrmc_ctx **out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0);
+/* d(i) as ordered 0-based lists in CSR form: rowptr[Nk + 1] (rowptr[0] = 0), cols[rowptr[Nk]].  The checks of TLE.jl:34-46 — entries in
+ * range, no self-loop, no duplicate, symmetry — fail with RRRMC_ERR_INVALID_ARG and the reference's wording (1-based numbers) in
+ * rrrmc_last_error.  A new topology ends a resumed run and asks for rrrmc_tle_set_params again.  rrrmc_tle_check_topology: the same checks
+ * on the host only (no device); maxdeg_out (may be NULL) receives max |d(i)|. */
+RRRMC_API int32_t rrrmc_tle_set_topology(rrrmc_ctx *ctx, const int32_t *rowptr, const int32_t *cols);
+RRRMC_API int32_t rrrmc_tle_check_topology(int64_t Nk, const int32_t *rowptr, const int32_t *cols, int64_t *maxdeg_out);
+/* The parameters of GraphTopologicalLocalEntropy(Nk, M, gamma, lambda, beta_graph, ...), after the topology: builds allDeltaE, and the
+ * class of every (lfields1, lfields2) pair by findk evaluated literally (DeltaE.jl:26-60, :83).  gamma / beta_graph, lambda / beta_graph and
+ * the largest level must be finite; zeros and negative values are allowed.  A change ends a resumed run. */
+RRRMC_API int32_t rrrmc_tle_set_params(rrrmc_ctx *ctx, double gamma, double lambda, double beta_graph);
+/* Host-only (no device needed): allDeltaE(GraphTLE{M, gamma/beta, lambda/beta}) for lists with max |d(i)| = maxdeg.  L_out receives its
+ * length L; dElist_out (NULL: only L is written) receives the L levels. */
+RRRMC_API int32_t rrrmc_tle_tables(int64_t M, double gamma, double lambda, double beta, int64_t maxdeg, double *dElist_out, int64_t *L_out);
+/* The DeltaECache after the last rrrMC call: pos_out[R * N] the class a + L up of every ABI site, sizes_out[R * 2L] the set sizes (either
+ * may be NULL). */
+RRRMC_API int32_t rrrmc_tle_cache(rrrmc_ctx *ctx, int32_t *pos_out, int32_t *sizes_out);
+/* The kernel build of the last rrrMC call: 0 none yet, 1 the chain's hot state in LDS (chosen when it fits and all R wavefronts are
+ * resident at once), 2 in global memory.  RRRMC_TLE_NO_LDS=1 forces 2, RRRMC_TLE_LDS=1 forces 1 whenever the state fits. */
+RRRMC_API int32_t rrrmc_tle_build(rrrmc_ctx *ctx, int32_t *build_out);
 
 /* rrrMC(X::DoubleGraph, beta, iters; step, staged_thr, staged_thr_fact) (src/RRRMC.jl:221-290) for all R replicas.
  *   fourK = round(2/beta * log(coth(beta * Gamma / M)), digits = 8)  (QT.jl:165) is computed by the caller.

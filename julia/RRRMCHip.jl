@@ -432,6 +432,83 @@ end
 re_hook(X::RRRMC.LE.GraphLocalEntropy, hook::Nothing) = hook
 re_hook(X::RRRMC.LE.GraphLocalEntropy, hook) = (it, X_, C, a, b) -> (le_slices!(X, C); hook(it, X_, C, a, b))
 
+# ---- GraphTopologicalLocalEntropy (src/graphs/TLE.jl:351-502): GraphLocalEntropy's layout with the inner graph GraphTLE{M,γT,λT} ---------
+# Graph0TLE, GraphSKTLE and GraphSATTLE (src/TLEAliases.jl) arrive here as GraphTopologicalLocalEntropy{M,γT,λT,G} with G = GraphEmpty,
+# GraphSK, GraphSAT; GraphEATLE (GraphEANormal slices) and the pattern machines are refused by the library (RRRMC_ERR_UNSUPPORTED).  The
+# neighbour lists are X.X0.neighb, 1-based in the reference and 0-based across the ABI, in list order.  γT and λT are type parameters:
+# rrrmc_tle_set_params takes (γ, λ, β) = (γT, λT, 1).  The observables go through le_energies / le_cenergy / le_distances.
+const TLE_EMPTY, TLE_SK, TLE_SKN, TLE_SAT = 44, 45, 46, 47       # rrrmc_ctx_create_tle; multi selectors
+const TLE_MODELS = (TLE_EMPTY, TLE_SK, TLE_SKN, 0, 0, 0, 0, 0, TLE_SAT, 0)   # by slice kind 0..9
+function Ctx(X::RRRMC.TLE.GraphTopologicalLocalEntropy{M,γT,λT,G}, R::Integer; device = 0, replica0 = 0, devices = nothing) where {M,γT,λT,G}
+    Nk = X.Nk
+    kind = ens_kind(G, "Topological Local Entropy ensemble")
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    if devices === nothing || TLE_MODELS[kind + 1] == 0           # (a slice kind without a selector: the single-device call names the refusal)
+        check(ccall((:rrrmc_ctx_create_tle, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, Int64, Int32, UInt32), ref, Nk, M, kind, R, device, replica0))
+    else
+        ref[] = create(TLE_MODELS[kind + 1], Nk, 0, M, R; replica0 = replica0, devices = devices)
+    end
+    ctx = Ctx(ref[], R, Nk * (M + 1), true)
+    X1 = X.X1[1]
+    if kind == 1
+        Jc = sk_bits(X1.J)
+        GC.@preserve Jc check(ccall((:rrrmc_set_couplings_bits, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt64}), ctx.p, Jc), ctx.p)
+    elseif kind == 2
+        Jm = Matrix{Float64}(undef, Nk, Nk); for i = 1:Nk; Jm[:, i] = X1.J[i]; end
+        GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
+    end
+    kind >= 3 && set_patterns!(ctx, X1)
+    neighb = X.X0.neighb
+    rowptr = Int32[0; cumsum(length.(neighb))]
+    cols = Int32[i1 - 1 for ni in neighb for i1 in ni]
+    isempty(cols) && push!(cols, 0)
+    GC.@preserve rowptr cols check(ccall((:rrrmc_tle_set_topology, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), ctx.p, rowptr, cols), ctx.p)
+    check(ccall((:rrrmc_tle_set_params, LIB), Int32, (Ptr{Cvoid}, Float64, Float64, Float64), ctx.p, γT, λT, 1.0), ctx.p)
+    return ctx
+end
+# the constructor's checks of neighbour lists (TLE.jl:34-46) on the host, no device: returns max |∂i|
+function tle_check_topology(neighb::Vector{Vector{Int}})
+    rowptr = Int32[0; cumsum(length.(neighb))]
+    cols = Int32[i1 - 1 for ni in neighb for i1 in ni]
+    isempty(cols) && push!(cols, 0)
+    md = Ref{Int64}(0)
+    GC.@preserve rowptr cols check(ccall((:rrrmc_tle_check_topology, LIB), Int32, (Int64, Ptr{Int32}, Ptr{Int32}, Ref{Int64}), length(neighb), rowptr, cols, md))
+    return Int(md[])
+end
+# allΔE(GraphTLE{M,γT,λT}) on the host (TLE.jl:335-347) for lists with max |∂i| = maxdeg, no device
+function tle_tables(M::Integer, γT::Float64, λT::Float64, maxdeg::Integer)
+    L = Ref{Int64}(0)
+    check(ccall((:rrrmc_tle_tables, LIB), Int32, (Int64, Float64, Float64, Float64, Int64, Ptr{Float64}, Ref{Int64}), M, γT, λT, 1.0, maxdeg, C_NULL, L))
+    out = Vector{Float64}(undef, L[])
+    check(ccall((:rrrmc_tle_tables, LIB), Int32, (Int64, Float64, Float64, Float64, Int64, Ptr{Float64}, Ref{Int64}), M, γT, λT, 1.0, maxdeg, out, L))
+    return out
+end
+# the DeltaECache after the last rrrMC call: (pos[N, R], sizes[2L, R])
+function tle_cache(ctx::Ctx, L::Integer)
+    pos = Matrix{Int32}(undef, ctx.N, ctx.R)
+    sizes = Matrix{Int32}(undef, 2L, ctx.R)
+    check(ccall((:rrrmc_tle_cache, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), ctx.p, pos, sizes), ctx.p)
+    return pos, sizes
+end
+function tle_build(ctx::Ctx)
+    b = Ref{Int32}(0)
+    check(ccall((:rrrmc_tle_build, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), ctx.p, b), ctx.p)
+    return Int(b[])
+end
+# Cc and C1[k] from a configuration of the whole graph (what energy(X, C) does, TLE.jl:413-435), before a user's hook runs: the reference's
+# own RRRMC.TLEenergies(X), cenergy(X) and distances(X) then read the sample's configuration
+function le_slices!(X::RRRMC.TLE.GraphTopologicalLocalEntropy{M}, C::RRRMC.Config) where {M}
+    for i = 1:X.Nk
+        X.Cc.s[i] = C.s[(i - 1) * (M + 1) + 1]
+        for k = 1:M
+            X.C1[k].s[i] = C.s[(i - 1) * (M + 1) + 1 + k]
+        end
+    end
+    return X
+end
+re_hook(X::RRRMC.TLE.GraphTopologicalLocalEntropy, hook::Nothing) = hook
+re_hook(X::RRRMC.TLE.GraphTopologicalLocalEntropy, hook) = (it, X_, C, a, b) -> (le_slices!(X, C); hook(it, X_, C, a, b))
+
 # ---- configurations ------------------------------------------------------------------------------------------------------------------
 seed!(ctx::Ctx, seed) = seed > 0 && check(ccall((:rrrmc_seed, LIB), Int32, (Ptr{Cvoid}, UInt64), ctx.p, seed), ctx.p)   # seed ≤ 0: keep going (RRRMC.jl:89)
 

@@ -40,6 +40,7 @@ SYMBOLS = [
     "rrrmc_ctx_create_comm", "rrrmc_ctx_create_comm_qu", "rrrmc_set_comm_patterns", "rrrmc_gen_comm_patterns",
     "rrrmc_ctx_create_quant_pattern", "rrrmc_quant_renergies", "rrrmc_quant_pattern_build",
     "rrrmc_ctx_create_sat", "rrrmc_set_clauses", "rrrmc_sat_build", "rrrmc_sweep_build", "rrrmc_gen_ksat", "rrrmc_check_clauses",
+    "rrrmc_ctx_create_tle", "rrrmc_tle_set_topology", "rrrmc_tle_check_topology", "rrrmc_tle_set_params", "rrrmc_tle_tables", "rrrmc_tle_cache", "rrrmc_tle_build",
 ]
 
 
@@ -278,6 +279,20 @@ def lib():
     L.rrrmc_le_distances.argtypes = [vp, i64p]
     L.rrrmc_le_tables.restype = C.c_int32
     L.rrrmc_le_tables.argtypes = [C.c_int64, C.c_double, C.c_double, f64p]
+    L.rrrmc_ctx_create_tle.restype = C.c_int32
+    L.rrrmc_ctx_create_tle.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_uint32]
+    L.rrrmc_tle_set_topology.restype = C.c_int32
+    L.rrrmc_tle_set_topology.argtypes = [vp, i32p, i32p]
+    L.rrrmc_tle_check_topology.restype = C.c_int32
+    L.rrrmc_tle_check_topology.argtypes = [C.c_int64, i32p, i32p, C.POINTER(C.c_int64)]
+    L.rrrmc_tle_set_params.restype = C.c_int32
+    L.rrrmc_tle_set_params.argtypes = [vp, C.c_double, C.c_double, C.c_double]
+    L.rrrmc_tle_tables.restype = C.c_int32
+    L.rrrmc_tle_tables.argtypes = [C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int64, vp, C.POINTER(C.c_int64)]
+    L.rrrmc_tle_cache.restype = C.c_int32
+    L.rrrmc_tle_cache.argtypes = [vp, vp, vp]
+    L.rrrmc_tle_build.restype = C.c_int32
+    L.rrrmc_tle_build.argtypes = [vp, C.POINTER(C.c_int32)]
     _lib = L
     return L
 

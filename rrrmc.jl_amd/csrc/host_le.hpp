@@ -5,9 +5,9 @@ inline bool is_le(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_LE_EM
                                                 ctx->model == RRRMC_MODEL_LE_PERC_STEP || ctx->model == RRRMC_MODEL_LE_PERC_LINEAR ||
                                                 ctx->model == RRRMC_MODEL_LE_COMM_STEP || ctx->model == RRRMC_MODEL_LE_COMM_RELU || ctx->model == RRRMC_MODEL_LE_SAT ||
                                                 ctx->model == RRRMC_MODEL_LE_COMM_QU; }
-inline int le_slice_of(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_LE_SK ? RE_SK : ctx->model == RRRMC_MODEL_LE_SKN ? RE_SKN :
+inline int le_slice_of(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_TLE_SK ? RE_SK : ctx->model == RRRMC_MODEL_LE_SKN || ctx->model == RRRMC_MODEL_TLE_SKN ? RE_SKN :
                                                       ctx->model == RRRMC_MODEL_LE_PERC_STEP ? RE_PSTEP : ctx->model == RRRMC_MODEL_LE_PERC_LINEAR ? RE_PLIN :
-                                                      ctx->model == RRRMC_MODEL_LE_COMM_STEP ? RE_CSTEP : ctx->model == RRRMC_MODEL_LE_COMM_RELU ? RE_CRELU : ctx->model == RRRMC_MODEL_LE_SAT ? RE_SAT :
+                                                      ctx->model == RRRMC_MODEL_LE_COMM_STEP ? RE_CSTEP : ctx->model == RRRMC_MODEL_LE_COMM_RELU ? RE_CRELU : ctx->model == RRRMC_MODEL_LE_SAT || ctx->model == RRRMC_MODEL_TLE_SAT ? RE_SAT :
                                                       ctx->model == RRRMC_MODEL_LE_COMM_QU ? RE_CQU : RE_EMPTY; }
 inline int le_levels(int64_t M) { return (int)(M % 2 == 0 ? M / 2 + 2 : (M + 1) / 2); }        // length of allΔE(GraphLE) (LE.jl:176-179)
 
@@ -65,8 +65,8 @@ LeParams le_params(rrrmc_ctx* ctx, double beta)
 {
     LeParams P{};
     const int64_t M = ctx->qM, L = le_levels(M);
-    if (ctx->model == RRRMC_MODEL_LE_SK) { P.Jb = ctx->q_Jb; P.Wk = (int)ctx->q_Wk; P.sN = std::sqrt((double)ctx->qNk); }
-    if (ctx->model == RRRMC_MODEL_LE_SKN) { P.Jd = ctx->sk_J; P.slf = ctx->q_slf; P.smv = ctx->q_smv; P.scur = ctx->q_scur; }
+    if (le_slice_of(ctx) == RE_SK) { P.Jb = ctx->q_Jb; P.Wk = (int)ctx->q_Wk; P.sN = std::sqrt((double)ctx->qNk); }
+    if (le_slice_of(ctx) == RE_SKN) { P.Jd = ctx->sk_J; P.slf = ctx->q_slf; P.smv = ctx->q_smv; P.scur = ctx->q_scur; }
     if (le_slice_of(ctx) == RE_PSTEP || le_slice_of(ctx) == RE_PLIN) P.pc = perc_params(ctx, M + 1);
     if (le_slice_of(ctx) == RE_CSTEP || le_slice_of(ctx) == RE_CRELU || le_slice_of(ctx) == RE_CQU) P.cm = comm_params(ctx, M + 1);
     if (le_slice_of(ctx) == RE_SAT) P.sat = sat_table(ctx);

@@ -40,6 +40,7 @@
 #include "sat_kernels.hpp"
 #include "re_kernels.hpp"
 #include "le_kernels.hpp"
+#include "tle_kernels.hpp"
 
 using namespace rrrmc;
 
@@ -282,6 +283,17 @@ struct rrrmc_ctx {
     int64_t* le_dist = nullptr;    // [R][M][M] distances
     double le_gT = 0.0;            // γT = γ / β (LE.jl:221-225)
     std::vector<uint8_t> le_hcode; // class codes of lfields = -M .. M (host_le.hpp)
+    // ---- GraphTopologicalLocalEntropy (RRRMC_MODEL_TLE_*; host_tle.hpp): a Local Entropy context whose re_tab (allΔE [L], ft [L]), q_sv,
+    //      q_st and q_T are sized by rrrmc_tle_set_params (L = tle_L); le_gT = γT ----
+    int32_t* tle_rowptr = nullptr; // [Nk + 1] the neighbour lists ∂i, CSR
+    int32_t* tle_cols = nullptr;   // [tle_rowptr[Nk]]
+    uint32_t* tle_code = nullptr;  // [2M + 1][2 M maxdeg + 1] class codes by (lfields1, lfields2) (tle_core.hpp)
+    int32_t* tle_lf2 = nullptr;    // [R][N] lfields2 by ABI site
+    uint16_t* tle_cls = nullptr;   // [R][N] DeltaECache.pos
+    int64_t tle_maxdeg = 0, tle_L = 0;
+    double tle_lT = 0.0;           // λT = λ / β (TLE.jl:390-396)
+    bool tle_topology_set = false;
+    int tle_build = 0;             // the build of the last rrrMC call: 1 hot state in LDS, 2 in global memory; 0 none yet
     // ---- the binary perceptron (RRRMC_MODEL_PERC_*, and the slices of RRRMC_MODEL_RE_PERC_* / _LE_PERC_*; host_perc.hpp): spins in q_spins,
     //      E in sk_E, counts in q_stats ----
     uint64_t* pc_col = nullptr;    // [Nk][PW] patterns, one column per synapse
@@ -501,7 +513,8 @@ inline bool chunk_layout(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODE
                                                        ctx->model == RRRMC_MODEL_LE_EMPTY || ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_LE_SKN ||
                                                        (ctx->model >= RRRMC_MODEL_PERC_STEP && ctx->model <= RRRMC_MODEL_LE_COMM_RELU) ||
                                                        ctx->model == RRRMC_MODEL_SAT || ctx->model == RRRMC_MODEL_RE_SAT || ctx->model == RRRMC_MODEL_LE_SAT ||
-                                                       ctx->model == RRRMC_MODEL_COMM_QU || ctx->model == RRRMC_MODEL_RE_COMM_QU || ctx->model == RRRMC_MODEL_LE_COMM_QU; }
+                                                       ctx->model == RRRMC_MODEL_COMM_QU || ctx->model == RRRMC_MODEL_RE_COMM_QU || ctx->model == RRRMC_MODEL_LE_COMM_QU ||
+                                                       (ctx->model >= RRRMC_MODEL_TLE_EMPTY && ctx->model <= RRRMC_MODEL_TLE_SAT); }
 inline bool sparse_int_model(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_SPARSE_PM1 || ctx->model == RRRMC_MODEL_SPARSE_LEVELS; }
 inline double lv_to_f64(const rrrmc_ctx* ctx, long long units) { return (double)(units * ctx->lv_mul) / ctx->lv_div; }
 
@@ -648,6 +661,7 @@ inline void smp_commit(rrrmc_ctx* ctx, int kind, int64_t n) { ctx->smp_kind = ki
 #include "host_sat.hpp"
 #include "host_re.hpp"
 #include "host_le.hpp"
+#include "host_tle.hpp"
 int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact);
 
 }  // namespace
@@ -961,6 +975,7 @@ void rrrmc_ctx_destroy(rrrmc_ctx* ctx)
     free_dev(ctx->cs_spins); free_dev(ctx->cs_buf); free_dev(ctx->cs_u16);
     free_dev(ctx->snap); free_dev(ctx->d_pairs); free_dev(ctx->d_ovl); free_dev(ctx->d_qobs);
     free_dev(ctx->re_sp); free_dev(ctx->re_mu); free_dev(ctx->re_tab); free_dev(ctx->re_Eslice); free_dev(ctx->le_dist);
+    free_dev(ctx->tle_rowptr); free_dev(ctx->tle_cols); free_dev(ctx->tle_code); free_dev(ctx->tle_lf2); free_dev(ctx->tle_cls);
     free_dev(ctx->sat_off); free_dev(ctx->sat_ent); free_dev(ctx->sat_spT);
     free_dev(ctx->pc_col); free_dev(ctx->pc_row); free_dev(ctx->pc_ds); free_dev(ctx->pc_pm); free_dev(ctx->pc_mm);
     free_dev(ctx->cm_col); free_dev(ctx->cm_row); free_dev(ctx->cm_lab); free_dev(ctx->cm_ds); free_dev(ctx->cm_mk);
@@ -986,7 +1001,7 @@ int32_t rrrmc_set_graph(rrrmc_ctx* ctx, const int32_t* A, const int8_t* J)
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
     if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_QUANT_RRG)
-        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph is for sparse +-J models; use rrrmc_set_couplings_dense%s", is_re(ctx) || is_le(ctx) ? " / rrrmc_set_couplings_bits (GraphRobustEnsemble, GraphLocalEntropy)" : "");
+        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph is for sparse +-J models; use rrrmc_set_couplings_dense%s", is_re(ctx) || is_le(ctx) || is_tle(ctx) ? " / rrrmc_set_couplings_bits (GraphRobustEnsemble, GraphLocalEntropy)" : "");
     if (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk)
         return fail(ctx, RRRMC_ERR_STATE, "this GraphQuant has binary GraphSK slices: give their couplings with rrrmc_set_couplings_bits");
     if (quant_pat(ctx))
@@ -1287,6 +1302,7 @@ int32_t rrrmc_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int6
     if (is_comm(ctx)) return comm_mc_async(ctx, beta, iters, step);
     if (is_sat(ctx)) return sat_mc_async(ctx, beta, iters, step);
     if (is_re(ctx)) return re_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
+    if (is_tle(ctx)) return tle_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (is_le(ctx)) return le_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (ctx->model == RRRMC_MODEL_QUANT_RRG) {
         if (!(ctx->last_fourK > 0.0)) return fail(ctx, RRRMC_ERR_STATE, "standardMC on a GraphQuant needs fourK: call rrrmc_quant_set_field first");
@@ -1320,7 +1336,7 @@ int32_t rrrmc_set_debug_checks(rrrmc_ctx* ctx, int32_t on)
 {
     RRRMC_MULTI(ctx, false, rrrmc_set_debug_checks(c, on));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_perc(ctx) && !is_comm(ctx) && !quant_pat(ctx) && !is_sat(ctx))
+    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_tle(ctx) && !is_perc(ctx) && !is_comm(ctx) && !quant_pat(ctx) && !is_sat(ctx))
         return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy, the perceptron, the committee machine and the K-SAT graphs, and GraphQuant over perceptrons and committee machines");
     ctx->debug_checks = on != 0;
     return RRRMC_OK;
@@ -1889,7 +1905,7 @@ static int32_t le_observable_out(rrrmc_ctx* ctx, int what, void* out)
 {
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
-    if (!is_le(ctx)) return fail(ctx, RRRMC_ERR_STATE, "the LE observables are for contexts made by rrrmc_ctx_create_le");
+    if (!is_le(ctx) && !is_tle(ctx)) return fail(ctx, RRRMC_ERR_STATE, "the LE observables are for contexts made by rrrmc_ctx_create_le / _tle");
     if (!out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "out is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1930,6 +1946,75 @@ int32_t rrrmc_le_distances(rrrmc_ctx* ctx, int64_t* out)
     return le_observable_out(ctx, 2, out);
 }
 
+// ---- GraphTopologicalLocalEntropy: exported entry points (host_tle.hpp) ------------------------------------------------------------
+int32_t rrrmc_ctx_create_tle(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0)
+{
+    return tle_ctx_create(out, Nk, M, slice_kind, R, device, replica0);
+}
+
+int32_t rrrmc_tle_check_topology(int64_t Nk, const int32_t* rowptr, const int32_t* cols, int64_t* maxdeg_out)
+{
+    int64_t md = 0;
+    char msg[256];
+    if (tle_check_topology(Nk, rowptr, cols, &md, msg, sizeof msg)) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "%s", msg);
+    if (maxdeg_out) *maxdeg_out = md;
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_tle_tables(int64_t M, double gamma, double lambda, double beta, int64_t maxdeg, double* dElist_out, int64_t* L_out)
+{
+    std::vector<double> dE;
+    const int32_t rc = tle_host_tables(nullptr, M, gamma, lambda, beta, maxdeg, dE);
+    if (rc) return rc;
+    if (L_out) *L_out = (int64_t)dE.size();
+    if (dElist_out) std::memcpy(dElist_out, dE.data(), sizeof(double) * dE.size());
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_tle_set_topology(rrrmc_ctx* ctx, const int32_t* rowptr, const int32_t* cols)
+{
+    RRRMC_MULTI(ctx, false, rrrmc_tle_set_topology(c, rowptr, cols));
+    smp_drop(ctx);
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!is_tle(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_tle_set_topology is for contexts made by rrrmc_ctx_create_tle");
+    return tle_set_topology(ctx, rowptr, cols);
+}
+
+int32_t rrrmc_tle_set_params(rrrmc_ctx* ctx, double gamma, double lambda, double beta_graph)
+{
+    RRRMC_MULTI(ctx, false, rrrmc_tle_set_params(c, gamma, lambda, beta_graph));
+    smp_drop(ctx);
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!is_tle(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_tle_set_params is for contexts made by rrrmc_ctx_create_tle");
+    return tle_set_params(ctx, gamma, lambda, beta_graph);
+}
+
+int32_t rrrmc_tle_cache(rrrmc_ctx* ctx, int32_t* pos_out, int32_t* sizes_out)
+{
+    RRRMC_MULTI(ctx, true, rrrmc_tle_cache(c, at_row(pos_out, r0 * c->N), at_row(sizes_out, r0 * 2 * c->tle_L)));
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!is_tle(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_tle_cache is for contexts made by rrrmc_ctx_create_tle");
+    if (!ctx->results_valid || !ctx->last_call_rrr || !ctx->q_cache_valid) return fail(ctx, RRRMC_ERR_STATE, "no rrrMC call has been made");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (pos_out) {
+        std::vector<uint16_t> cls((size_t)ctx->R * (size_t)ctx->N);
+        HIP_TRY(ctx, hipMemcpy(cls.data(), ctx->tle_cls, sizeof(uint16_t) * cls.size(), hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < cls.size(); ++j) pos_out[j] = (int32_t)cls[j];
+    }
+    if (sizes_out) HIP_TRY(ctx, hipMemcpy(sizes_out, ctx->q_st, sizeof(int32_t) * (size_t)ctx->R * 2 * (size_t)ctx->tle_L, hipMemcpyDeviceToHost));
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_tle_build(rrrmc_ctx* ctx, int32_t* build_out)
+{
+    if (!ctx || !build_out) return RRRMC_ERR_INVALID_ARG;
+    if (is_multi(ctx)) return rrrmc_tle_build(ctx->kids[0], build_out);
+    if (!is_tle(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_tle_build is for contexts made by rrrmc_ctx_create_tle");
+    *build_out = ctx->tle_build;
+    return RRRMC_OK;
+}
+
 // One context over several devices: the reference's user makes ONE call from ONE process (src/RRRMC.jl:81-88).
 // Replicas never interact, so the context is a list of per-device contexts over shards of whole 32-replica groups in global-id
 // order (the random streams are addressed by global replica id: the results do not depend on ndev); every entry point forwards
@@ -1954,6 +2039,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                     model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_RE_COMM_RELU || model == RRRMC_MODEL_RE_SAT || model == RRRMC_MODEL_RE_COMM_QU;
     const bool le = model == RRRMC_MODEL_LE_EMPTY || model == RRRMC_MODEL_LE_SK || model == RRRMC_MODEL_LE_SKN || model == RRRMC_MODEL_LE_PERC_STEP || model == RRRMC_MODEL_LE_PERC_LINEAR ||
                     model == RRRMC_MODEL_LE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_RELU || model == RRRMC_MODEL_LE_SAT || model == RRRMC_MODEL_LE_COMM_QU;
+    const bool tle = model >= RRRMC_MODEL_TLE_EMPTY && model <= RRRMC_MODEL_TLE_SAT;
     const bool sat = model == RRRMC_MODEL_SAT;
     const bool pc = model == RRRMC_MODEL_PERC_STEP || model == RRRMC_MODEL_PERC_LINEAR;
     const bool cm = model == RRRMC_MODEL_COMM_STEP || model == RRRMC_MODEL_COMM_RELU || model == RRRMC_MODEL_COMM_QU;
@@ -1961,18 +2047,18 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
         delete ctx;
         return fail(nullptr, RRRMC_ERR_INVALID_ARG, "a committee machine takes N = K1*K2 and K = K2 with N %% K2 == 0, given N = %lld, K = %lld", (long long)N, (long long)K);
     }
-    const int32_t ens_slice = model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_LE_SK ? RRRMC_RE_SLICE_SK
-                              : model == RRRMC_MODEL_RE_SKN || model == RRRMC_MODEL_LE_SKN ? RRRMC_RE_SLICE_SKN
+    const int32_t ens_slice = model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_LE_SK || model == RRRMC_MODEL_TLE_SK ? RRRMC_RE_SLICE_SK
+                              : model == RRRMC_MODEL_RE_SKN || model == RRRMC_MODEL_LE_SKN || model == RRRMC_MODEL_TLE_SKN ? RRRMC_RE_SLICE_SKN
                               : model == RRRMC_MODEL_RE_PERC_STEP || model == RRRMC_MODEL_LE_PERC_STEP ? RRRMC_RE_SLICE_PERC_STEP
                               : model == RRRMC_MODEL_RE_PERC_LINEAR || model == RRRMC_MODEL_LE_PERC_LINEAR ? RRRMC_RE_SLICE_PERC_LINEAR
                               : model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_STEP ? RRRMC_RE_SLICE_COMM_STEP
                               : model == RRRMC_MODEL_RE_COMM_RELU || model == RRRMC_MODEL_LE_COMM_RELU ? RRRMC_RE_SLICE_COMM_RELU
-                              : model == RRRMC_MODEL_RE_SAT || model == RRRMC_MODEL_LE_SAT ? RRRMC_RE_SLICE_SAT
+                              : model == RRRMC_MODEL_RE_SAT || model == RRRMC_MODEL_LE_SAT || model == RRRMC_MODEL_TLE_SAT ? RRRMC_RE_SLICE_SAT
                               : model == RRRMC_MODEL_RE_COMM_QU || model == RRRMC_MODEL_LE_COMM_QU ? RRRMC_RE_SLICE_COMM_QU
                                                                                                        : RRRMC_RE_SLICE_EMPTY;
     ctx->model = quant ? RRRMC_MODEL_QUANT_RRG : model; ctx->K = K; ctx->R = R; ctx->replica0 = replica0; ctx->device = device_ids[0];
-    ctx->N = quant || re ? N * M : le ? N * (M + 1) : N;
-    if (re || le) { ctx->qNk = N; ctx->qM = M; }
+    ctx->N = quant || re ? N * M : le || tle ? N * (M + 1) : N;
+    if (re || le || tle) { ctx->qNk = N; ctx->qM = M; }
     if (pc || sat) { ctx->qNk = N; ctx->qM = 1; }
     if (cm) { ctx->qNk = N; ctx->qM = 1; ctx->cm_K2 = K; ctx->K = 0; }
     if (quant) { ctx->qNk = N; ctx->qM = M; ctx->q_sk = model == RRRMC_MODEL_QUANT_SK; ctx->q_skn = model == RRRMC_MODEL_QUANT_SKN; ctx->q_spf = model == RRRMC_MODEL_QUANT_F64; ctx->q_pat = qpat; }
@@ -1989,6 +2075,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : qpat ? rrrmc_ctx_create_quant_pattern(&c, qpat, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : re ? rrrmc_ctx_create_re(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : le ? rrrmc_ctx_create_le(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : tle ? rrrmc_ctx_create_tle(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : pc ? rrrmc_ctx_create_perc(&c, N, model == RRRMC_MODEL_PERC_LINEAR, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : sat ? rrrmc_ctx_create_sat(&c, N, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_COMM_QU ? rrrmc_ctx_create_comm_qu(&c, N / K, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
@@ -2216,6 +2303,7 @@ int32_t rrrmc_rrr_mc_async(rrrmc_ctx* ctx, double beta, double fourK, int64_t it
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone committee machine graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone GraphSAT (a DeltaECache of max_conn + 1 levels over variable-degree neighbourhoods): standardMC is, and rrrMC on GraphSATRE / GraphSATLE");
     if (is_re(ctx)) return re_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
+    if (is_tle(ctx)) return tle_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (is_le(ctx)) return le_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model != RRRMC_MODEL_QUANT_RRG) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not available for model kind %d", ctx->model);
     if (ctx->q_pat && !(ctx->last_fourK > 0.0)) return fail(ctx, RRRMC_ERR_STATE, "a GraphQuant over pattern machines needs (beta, fourK): call rrrmc_quant_set_field first");
@@ -2233,6 +2321,7 @@ int32_t rrrmc_bkl_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t s
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone GraphSAT (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
+    if (is_tle(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphTopologicalLocalEntropy (rrrMC and standardMC are)");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for a GraphQuant over pattern machines (DeltaECacheCont over AllButOne neighbourhoods): rrrMC and standardMC are");
     if (!std::isfinite(beta)) return fail(ctx, RRRMC_ERR_INVALID_ARG, "beta must be finite, given: %g", beta);
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
@@ -2276,6 +2365,7 @@ int32_t rrrmc_wtm_mc_async(rrrmc_ctx* ctx, double beta, int64_t samples, double 
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone GraphSAT (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
+    if (is_tle(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphTopologicalLocalEntropy (rrrMC and standardMC are)");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for a GraphQuant over pattern machines (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
         return spf_cont_async(ctx, 2, beta, samples, 1, step, 0.0, 5.0);
@@ -2307,6 +2397,7 @@ int32_t rrrmc_extremal_opt_async(rrrmc_ctx* ctx, const double* ftau, int64_t ite
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone GraphSAT (standardMC is)");
     if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
     if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
+    if (is_tle(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphTopologicalLocalEntropy (rrrMC and standardMC are)");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for a GraphQuant over pattern machines (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)        // not DiscrGraphs: EOCacheCont
         return spf_cont_async(ctx, 3, 0.0, iters, step, 1.0, 0.0, 0.0, ftau);
@@ -2377,6 +2468,7 @@ int32_t rrrmc_rrr_cache(rrrmc_ctx* ctx, int8_t* pos_out, int32_t* sizes_out)
 {
     RRRMC_MULTI(ctx, true, rrrmc_rrr_cache(c, at_row(pos_out, r0 * ctx->N), at_row(sizes_out, r0 * (ctx->model == RRRMC_MODEL_QUANT_RRG ? 4 : is_re(ctx) ? 2 * re_levels(ctx->qM) : is_le(ctx) ? 2 * le_levels(ctx->qM) : 16))));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (is_tle(ctx)) return fail(ctx, RRRMC_ERR_STATE, "a GraphTopologicalLocalEntropy has more classes than an int8 names: use rrrmc_tle_cache");
     if (is_re(ctx) || is_le(ctx)) {             // classes of the ABI sites, sizes_out[R * 2L]
         if (!ctx->results_valid || !ctx->last_call_rrr || !ctx->q_cache_valid) return fail(ctx, RRRMC_ERR_STATE, "no rrrMC call has been made");
         HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2427,7 +2519,7 @@ int32_t rrrmc_set_couplings_dense(rrrmc_ctx* ctx, const double* J)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_dense(c, J));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qskn = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn) || ctx->model == RRRMC_MODEL_RE_SKN || ctx->model == RRRMC_MODEL_LE_SKN;   // slice graphs: J is Nk x Nk
+    const bool qskn = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn) || ctx->model == RRRMC_MODEL_RE_SKN || ctx->model == RRRMC_MODEL_LE_SKN || ctx->model == RRRMC_MODEL_TLE_SKN;   // slice graphs: J is Nk x Nk
     if (ctx->model != RRRMC_MODEL_SK_NORMAL && !qskn) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_dense is for RRRMC_MODEL_SK_NORMAL (or a GraphQuant over GraphSKNormal slices)");
     if (!J) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J is NULL");
     const int64_t N = qskn ? ctx->qNk : ctx->N;
@@ -2476,6 +2568,10 @@ int32_t rrrmc_energy_f64(rrrmc_ctx* ctx, double* E_out)
         if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphRobustEnsemble needs (gamma, beta): call rrrmc_re_set_params first");
         ctx->std_cache_live = false;
         rc = re_run_init(ctx, 1.0, false);
+    } else if (is_tle(ctx)) {
+        if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphTopologicalLocalEntropy needs its neighbour lists and (gamma, lambda, beta): call rrrmc_tle_set_topology and rrrmc_tle_set_params first");
+        ctx->std_cache_live = false;
+        rc = tle_run_init(ctx, 1.0, false);
     } else if (is_le(ctx)) {
         if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphLocalEntropy needs (gamma, beta): call rrrmc_le_set_params first");
         ctx->std_cache_live = false;
@@ -2572,7 +2668,7 @@ int32_t rrrmc_set_couplings_bits(rrrmc_ctx* ctx, const uint64_t* Jc)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_bits(c, Jc));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qsk = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk) || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_LE_SK;     // the slice graph of a GraphQSKT / GraphSKRE / GraphSKLE
+    const bool qsk = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk) || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_TLE_SK;     // the slice graph of a GraphQSKT / GraphSKRE / GraphSKLE
     if (ctx->model != RRRMC_MODEL_SK_BINARY && !qsk)
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_bits is for RRRMC_MODEL_SK_BINARY and for contexts made by rrrmc_ctx_create_quant_sk");
     if (!Jc) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J_chunks is NULL");

@@ -237,6 +237,20 @@ class Engine:
         check(lib().rrrmc_rrr_cache(self._ctx, pos.ctypes.data, sizes.ctypes.data), self._ctx)
         return pos, sizes
 
+    def tle_cache(self):
+        """(pos[R, N], sizes[R, 2L]) of the DeltaECache after the last rrrMC call on a GraphTopologicalLocalEntropy (int32: the class ids
+        do not fit the int8 of ``rrr_cache``); L = len(X.tables())."""
+        pos = np.zeros((self.R, self.X.N), np.int32)
+        sizes = np.zeros((self.R, 2 * len(self.X.tables())), np.int32)
+        check(lib().rrrmc_tle_cache(self._ctx, pos.ctypes.data, sizes.ctypes.data), self._ctx)
+        return pos, sizes
+
+    def tle_build(self):
+        """the kernel build of the last rrrMC call on a GraphTopologicalLocalEntropy: 1 hot state in LDS, 2 in global memory, 0 none yet"""
+        b = C.c_int32(0)
+        check(lib().rrrmc_tle_build(self._ctx, C.byref(b)), self._ctx)
+        return int(b.value)
+
     def re_energies(self):
         """REenergies (RE.jl:285-301) of the live configuration: (M,) for one replica, (R, M) otherwise.  Read-only: a run the engine
         continues is not disturbed."""

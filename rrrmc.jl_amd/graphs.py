@@ -1076,6 +1076,120 @@ def GraphSKLE(Nk, M, gamma, beta, seed=DEFAULT_SEED):
     return GraphLocalEntropy(Nk, M, gamma, beta, GraphSK(Nk, seed=seed))
 
 
+def _tle_check_neighb(Nk, M, neighb):
+    """the checks of GraphTLE's constructor (TLE.jl:27-46), 0-based lists; the messages carry the reference's 1-based numbers"""
+    if M <= 2:
+        raise ValueError("M must be greater than 2, given: %d" % M)                      # TLE.jl:29
+    if len(neighb) != Nk:
+        raise ValueError("invalid neighb argument, expected length %d, given: %d" % (Nk, len(neighb)))
+    for i, ni in enumerate(neighb):
+        if not all(0 <= j < Nk for j in ni):
+            raise ValueError("invalid neighb[%d] argument, all elements must be between 1 and %d" % (i + 1, Nk))
+        if i in ni:
+            raise ValueError("invalid neighb[%d], contains itself" % (i + 1))
+        for i1 in range(len(ni)):
+            if ni[i1] in ni[i1 + 1:]:
+                raise ValueError("duplicated element %d in neighb[%d]" % (i1 + 1, i + 1))
+    sets = [set(ni) for ni in neighb]
+    for i, ni in enumerate(neighb):
+        for i1 in ni:
+            if i not in sets[i1]:
+                raise ValueError("neighb is not symmetrical, %d ∈ ∂%d but %d ∉ ∂%d" % (i1 + 1, i + 1, i + 1, i1 + 1))
+
+
+class GraphTopologicalLocalEntropy(_DeviceGraph):
+    """``GraphTopologicalLocalEntropy(Nk, M, γ, λ, β, slice_graph)`` — the Local Entropy ensemble with a topological interaction
+    (src/graphs/TLE.jl:351-396): as ``GraphLocalEntropy``, M replicas of one graph and a centre, coupled by ``GraphTLE{M,γT,λT}`` with
+    γT = γ / β and λT = λ / β: ΔE0 = 2γT lfields1 + 2λT lfields2, where lfields1 is GraphLE's field and lfields2 on replica site (i,k) is
+    σ_(i,k) σc_i Σ_{i2 ∈ ∂i} σc_i2 σ_(i2,k) (on a centre: the sum of its replicas').  ∂i = ``neighb[i]`` is ``neighbors(slice_graph, i)``:
+    empty for ``None`` (GraphEmpty: ``Graph0TLE``), all other sites ascending for a binary ``GraphSK`` (``GraphSKTLE``) or a
+    ``GraphSKNormal``, ``GraphSAT.neighb`` for a ``GraphSAT`` (``GraphSATTLE``).  Sites, their order and the observables are
+    ``GraphLocalEntropy``'s.  ``ET = Float64``.  See ``TLEenergies``, ``cenergy`` and ``distances``."""
+    energy_dtype = np.float64
+    K = 0
+
+    def _create(self, ctx, R, device, replica0):
+        check(lib().rrrmc_ctx_create_tle(ctx, self.Nk, self.M, self.slice_kind, R, device, replica0))
+
+    def _multi_args(self):
+        return self.model_kind, self.Nk, self.K, self.M
+
+    def _upload(self, ctx):
+        if self.X1 is not None:
+            self.X1._upload_couplings(ctx)
+        check(lib().rrrmc_tle_set_topology(ctx, self._rowptr, self._cols), ctx)
+        check(lib().rrrmc_tle_set_params(ctx, self.gamma, self.lam, self.beta), ctx)
+
+    def __init__(self, Nk, M, gamma, lam, beta, slice_graph=None):
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, GraphSAT)):
+            raise TypeError("the slices of a GraphTopologicalLocalEntropy are GraphEmpty (None), GraphSK, GraphSKNormal or GraphSAT")
+        if slice_graph is not None and slice_graph.N != int(Nk):
+            raise ValueError("expected %d spins, got %d" % (Nk, slice_graph.N))           # TLE.jl:392
+        self.Nk, self.M, self.gamma, self.lam, self.beta = int(Nk), int(M), float(gamma), float(lam), float(beta)
+        if slice_graph is None:
+            neighb = [[] for _ in range(self.Nk)]
+        elif isinstance(slice_graph, GraphSAT):
+            neighb = [list(ni) for ni in slice_graph.neighb]
+        else:
+            neighb = [[j for j in range(self.Nk) if j != i] for i in range(self.Nk)]      # AllButOne
+        _tle_check_neighb(self.Nk, self.M, neighb)
+        self.neighb = neighb
+        self.gammaT, self.lambdaT = self.gamma / self.beta, self.lam / self.beta           # TLE.jl:390-396
+        self.N = self.Nk * (self.M + 1)
+        self.X1 = slice_graph
+        self.slice_kind = _ensemble_slice_kind(slice_graph)
+        self.model_kind = {0: 44, 1: 45, 2: 46, 8: 47}[self.slice_kind]                   # RRRMC_MODEL_TLE_EMPTY / _SK / _SKN / _SAT
+        self.J = getattr(slice_graph, "J", None)
+        self.max_deg = max(len(ni) for ni in neighb)
+        self._rowptr = np.zeros(self.Nk + 1, np.int32)
+        self._rowptr[1:] = np.cumsum([len(ni) for ni in neighb])
+        self._cols = np.array([j for ni in neighb for j in ni] or [0], np.int32)
+        self._engine = None                             # the Engine running this graph: the observables read the live configuration there
+
+    def tables(self):
+        """allΔE of GraphTLE{M,γT,λT} (rrrmc_tle_tables: host only, no device)"""
+        L = C.c_int64(0)
+        check(lib().rrrmc_tle_tables(self.M, self.gamma, self.lam, self.beta, self.max_deg, None, C.byref(L)))
+        dE = np.zeros(L.value, np.float64)
+        check(lib().rrrmc_tle_tables(self.M, self.gamma, self.lam, self.beta, self.max_deg, dE.ctypes.data, C.byref(L)))
+        return dE
+
+    _rrr_classes = property(lambda self: 2 * len(self.tables()))
+
+
+def Graph0TLE(Nk, M, gamma, lam, beta):
+    """``Graph0TLE(Nk, M, γ, λ, β)`` = ``GraphTopologicalLocalEntropy(Nk, M, γ, λ, β, GraphEmpty, Nk)`` (src/TLEAliases.jl): no neighbours,
+    so the model coincides with ``Graph0LE(Nk, M, γ, β)``."""
+    return GraphTopologicalLocalEntropy(Nk, M, gamma, lam, beta, None)
+
+
+def GraphSKTLE(Nk, M, gamma, lam, beta, seed=DEFAULT_SEED):
+    """``GraphSKTLE(Nk, M, γ, λ, β)`` = ``GraphTopologicalLocalEntropy(Nk, M, γ, λ, β, GraphSK, SK.gen_J(Nk))`` (src/TLEAliases.jl): the
+    couplings are drawn once and shared by the centre and the M slices; every site neighbours every other."""
+    return GraphTopologicalLocalEntropy(Nk, M, gamma, lam, beta, GraphSK(Nk, seed=seed))
+
+
+def GraphSATTLE(*args, seed=DEFAULT_SEED):
+    """``GraphSATTLE(N, K, α, M, γ, λ, β)`` / ``GraphSATTLE(X::GraphSAT, M, γ, λ, β)`` (src/TLEAliases.jl): a Topological Local Entropy
+    ensemble of M replicas of one K-SAT instance and a centre; two variables are neighbours when they share a clause."""
+    if isinstance(args[0], GraphSAT):
+        if len(args) != 5:
+            raise TypeError("expected (X, M, γ, λ, β)")
+        X, M, gamma, lam, beta = args
+    else:
+        if len(args) != 7:
+            raise TypeError("expected (N, K, α, M, γ, λ, β) or (X, M, γ, λ, β)")
+        *cargs, M, gamma, lam, beta = args
+        X = GraphSAT(*cargs, seed=seed)
+    return GraphTopologicalLocalEntropy(X.N, M, gamma, lam, beta, X)
+
+
+def TLEenergies(X, C=None):
+    """``TLEenergies(X)`` (TLE.jl:437-453): the energy of every replica of the ensemble as its own graph defines it; shapes and reading
+    as ``LEenergies``."""
+    return _le_observable(X, C, "TLEenergies", "le_energies")
+
+
 def _le_observable(X, C, name, fn):
     from .engine import Engine
     if C is not None:

@@ -7,6 +7,7 @@
   python tools/bench_models.py comm [R ...] GraphCommStepRE / LE(201, 5, 400, 5), GraphCommReLURE / LE(168, 6, 400, 5) and the two
                                             stand-alone graphs: the same legs
   python tools/bench_models.py sat [R ...]  GraphSAT(1000, 3, 4.2), β = 2: standardMC through the wave and the thread build
+  python tools/bench_models.py tle [R ...]  GraphSATTLE(1000, 3, 4.2, 3) and GraphSKTLE(201, 3) beside LE: rrrMC (both builds) and standardMC
   python tools/bench_models.py satre [R ...] GraphSATRE(1001, 3, 4.2, 5) beside GraphPercStepRE(1001, 400, 5): rrrMC, both builds
 """
 import json
@@ -256,6 +257,42 @@ def bench_le(Nk=1024, M=5, gamma=2.0, beta=0.4, iters=1 << 14, step=1 << 12, see
         print(json.dumps(out), flush=True)
 
 
+def bench_tle(M=3, gamma=1.0, lam=0.5, beta_g=1.0, beta=1.0, iters=10000, seed=7):
+    """GraphSATTLE(1000, 3, 4.2, 3) and GraphSKTLE(201, 3) (γ = 1, λ = 0.5, β = 1) beside GraphSATLE / GraphSKLE at the same shape: rrrMC
+    through TLE's LDS and global-memory builds and standardMC, kernel iterations/s per replica count (python tools/bench_models.py tle 8
+    128 2048; profiles/r14/tle.md).  Every figure: one warm-up call, then two timed calls continuing the chain, the faster one reported."""
+    pkg = entry.load_package()
+    S = pkg.GraphSAT(1000, 3, 4.2, seed=seed)
+    models = (("GraphSATTLE(1000,3,4.2,%d)" % M, pkg.GraphSATTLE(S, M, gamma, lam, beta_g), pkg.GraphSATLE(S, M, gamma, beta_g)),
+              ("GraphSKTLE(201,%d)" % M, pkg.GraphSKTLE(201, M, gamma, lam, beta_g, seed=seed), pkg.GraphSKLE(201, M, gamma, beta_g, seed=seed)))
+    envs = ("RRRMC_TLE_NO_LDS", "RRRMC_TLE_LDS")
+    for label, Xt, Xl in models:
+        for R in ([int(a) for a in sys.argv[2:]] or [8, 128, 2048]):
+            out = {"model": label, "gamma": gamma, "lambda": lam, "beta_graph": beta_g, "beta": beta, "replicas": R, "iters": iters,
+                   "classes": 2 * len(Xt.tables()), "max_deg": Xt.max_deg}
+            legs = (("tle_rrr_lds", Xt, "rrr", {"RRRMC_TLE_LDS": "1"}), ("tle_rrr_global", Xt, "rrr", {"RRRMC_TLE_NO_LDS": "1"}),
+                    ("le_rrr", Xl, "rrr", {}), ("tle_standard", Xt, "std", {}), ("le_standard", Xl, "std", {}))
+            for name, X, sampler, env in legs:
+                for k in envs:
+                    os.environ.pop(k, None)
+                os.environ.update(env)
+                with pkg.Engine(X, R) as eng:
+                    eng.seed(5)
+                    eng.init_spins_random()
+                    best = None
+                    for rep in range(3):
+                        acc = (eng.rrr_mc(beta, iters, iters) if sampler == "rrr" else eng.standard_mc(beta, iters, iters))[1]
+                        _, sweep_ms, _ = eng.last_timing()
+                        if rep and (best is None or sweep_ms < best[0]):
+                            best = (sweep_ms, float(acc.mean()) / iters)
+                    out[name] = {"kernel_iterations_per_s": float(R) * iters / (best[0] * 1e-3), "kernel_ms": best[0], "acceptance": best[1]}
+                    if name.startswith("tle_rrr"):
+                        out[name]["build"] = eng.tle_build()
+            for k in envs:
+                os.environ.pop(k, None)
+            print(json.dumps(out), flush=True)
+
+
 def bench_perc(Nk=1001, P=400, M=5, gamma=2.0, beta=0.4, iters=1 << 14, step=1 << 12, seed=0x5EED, reps=3):
     """GraphPercStepRE(1001, 400, 5), GraphPercStepLE(1001, 400, 5) (γ = 2, β = 0.4: bench_re's point over perceptron slices) and the
     stand-alone GraphPercStep(1001, 400): rrrMC through the thread and the LDS build and standardMC, kernel iterations/s per replica count
@@ -403,4 +440,4 @@ def bench_satre(Nk=1001, K=3, alpha=4.2, P=400, M=5, gamma=2.0, beta=0.4, iters=
 
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "sk"
-    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm, "sat": bench_sat, "satre": bench_satre}[which]()
+    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm, "sat": bench_sat, "satre": bench_satre, "tle": bench_tle}[which]()
