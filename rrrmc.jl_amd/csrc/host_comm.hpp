@@ -3,19 +3,19 @@
 // and the pattern matrix, labels and Stabilities that the Robust Ensemble and Local Entropy contexts with committee slices share with them.
 // Included by rrrmc_hip.hip inside its anonymous namespace, before host_re.hpp; not a stand-alone translation unit.
 inline bool is_comm(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_COMM_STEP || ctx->model == RRRMC_MODEL_COMM_RELU || ctx->model == RRRMC_MODEL_COMM_QU; }
-inline bool comm_slices(const rrrmc_ctx* ctx)
+inline bool comm_slices(const rrrmc_ctx* ctx)          // an ensemble over committee machine slices (ens_models.hpp)
 {
-    return ctx->model == RRRMC_MODEL_RE_COMM_STEP || ctx->model == RRRMC_MODEL_RE_COMM_RELU || ctx->model == RRRMC_MODEL_LE_COMM_STEP ||
-           ctx->model == RRRMC_MODEL_LE_COMM_RELU || ctx->model == RRRMC_MODEL_RE_COMM_QU || ctx->model == RRRMC_MODEL_LE_COMM_QU;
+    const int32_t s = ens_slice(ctx->model);
+    return s == RRRMC_RE_SLICE_COMM_STEP || s == RRRMC_RE_SLICE_COMM_RELU || s == RRRMC_RE_SLICE_COMM_QU;
 }
 inline bool comm_relu(const rrrmc_ctx* ctx)
 {
-    return ctx->model == RRRMC_MODEL_COMM_RELU || ctx->model == RRRMC_MODEL_RE_COMM_RELU || ctx->model == RRRMC_MODEL_LE_COMM_RELU ||
+    return ctx->model == RRRMC_MODEL_COMM_RELU || ens_slice(ctx->model) == RRRMC_RE_SLICE_COMM_RELU ||
            (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_pat == RRRMC_RE_SLICE_COMM_RELU);
 }
 inline bool comm_qu(const rrrmc_ctx* ctx)
 {
-    return ctx->model == RRRMC_MODEL_COMM_QU || ctx->model == RRRMC_MODEL_RE_COMM_QU || ctx->model == RRRMC_MODEL_LE_COMM_QU ||
+    return ctx->model == RRRMC_MODEL_COMM_QU || ens_slice(ctx->model) == RRRMC_RE_SLICE_COMM_QU ||
            (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_pat == RRRMC_RE_SLICE_COMM_QU);
 }
 // GraphCommReLU and GraphCommQu: K1, K2 even, labelled patterns

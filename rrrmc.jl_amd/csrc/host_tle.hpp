@@ -2,8 +2,8 @@
 // GraphSAT slices, tle_kernels.hpp).  Included by rrrmc_hip.hip inside its anonymous namespace, after host_le.hpp; not a stand-alone
 // translation unit.  A TLE context is a Local Entropy context (the same spins, μ, slice state, scalars, observables) whose level tables and
 // DeltaECache arrays are sized by rrrmc_tle_set_params — the number of levels depends on the topology and on (γT, λT) — and which adds the
-// neighbour lists, the class-code table, lfields2 and 16-bit class ids.
-inline bool is_tle(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_TLE_EMPTY || ctx->model == RRRMC_MODEL_TLE_SK || ctx->model == RRRMC_MODEL_TLE_SKN || ctx->model == RRRMC_MODEL_TLE_SAT; }
+// neighbour lists, the class-code table, lfields2 and 16-bit class ids.  What the three ensembles share is in host_ens.hpp; the TLE kernels
+// are dispatched over TleSlices, the four slice kinds they are built for.
 
 // Device-memory rule: the sets are dense, [2L][N] 16-bit members per replica, as in the other ensembles; a context whose sets would take
 // more than kTleSetBytesMax in all is refused.
@@ -20,14 +20,6 @@ TleParams tle_params(rrrmc_ctx* ctx, double beta)
     return P;
 }
 
-#define TLE_LAUNCH(ctx, KERNEL, grid, blk, lds, ...)                                                                                        \
-    switch (le_slice_of(ctx)) {                                                                                                              \
-        case RE_SK: hipLaunchKernelGGL(KERNEL<RE_SK>, grid, blk, lds, (ctx)->stream, __VA_ARGS__); break;                                    \
-        case RE_SKN: hipLaunchKernelGGL(KERNEL<RE_SKN>, grid, blk, lds, (ctx)->stream, __VA_ARGS__); break;                                  \
-        case RE_SAT: hipLaunchKernelGGL(KERNEL<RE_SAT>, grid, blk, lds, (ctx)->stream, __VA_ARGS__); break;                                  \
-        default: hipLaunchKernelGGL(KERNEL<RE_EMPTY>, grid, blk, lds, (ctx)->stream, __VA_ARGS__); break;                                    \
-    }
-
 // energy(X, C) and, for rrrMC, a fresh DeltaECache: the start of a reference call (src/RRRMC.jl:95, :236-238); ft needs the sampler's β
 int32_t tle_run_init(rrrmc_ctx* ctx, double beta, bool cache)
 {
@@ -37,65 +29,51 @@ int32_t tle_run_init(rrrmc_ctx* ctx, double beta, bool cache)
     const TleParams P = tle_params(ctx, beta);
     int32_t rc = re_to_slices(ctx, P);
     if (rc) return rc;
-    TLE_LAUNCH(ctx, tle_init_kernel, dim3((unsigned)ctx->R), dim3(kReInitThreads), 0, P, cache ? 1 : 0);
+    const dim3 grid((unsigned)ctx->R), blk(kReInitThreads);
+    if (!with_slice(TleSlices{}, ens_slice(ctx->model), [&](auto s) { hipLaunchKernelGGL(tle_init_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); }))
+        return ens_bad_slice(ctx);
     HIP_TRY(ctx, hipGetLastError());
     return RRRMC_OK;
 }
 
 typedef void (*tle_kernel_fn)(TleParams);
+// nullptr: no such slice
 tle_kernel_fn tle_rrr_fn(int slice, bool lds)
 {
-    switch (slice) {
-        case RE_SK: return lds ? tle_rrr_kernel<true, RE_SK> : tle_rrr_kernel<false, RE_SK>;
-        case RE_SKN: return lds ? tle_rrr_kernel<true, RE_SKN> : tle_rrr_kernel<false, RE_SKN>;
-        case RE_SAT: return lds ? tle_rrr_kernel<true, RE_SAT> : tle_rrr_kernel<false, RE_SAT>;
-        default: return lds ? tle_rrr_kernel<true, RE_EMPTY> : tle_rrr_kernel<false, RE_EMPTY>;
-    }
+    tle_kernel_fn fn = nullptr;
+    with_slice(TleSlices{}, slice, [&](auto s) { fn = lds ? tle_rrr_kernel<true, decltype(s)::value> : tle_rrr_kernel<false, decltype(s)::value>; });
+    return fn;
+}
+
+// debug mode: the consistency check behind a sampler call (reported by the next sync, post_sync_checks)
+int32_t tle_debug_check(rrrmc_ctx* ctx, const TleParams& P0, bool cache)
+{
+    const int32_t rc = dbg_flag_ensure(ctx);
+    if (rc) return rc;
+    TleParams P = P0;
+    P.flag = ctx->dbg_flag;
+    const dim3 grid((unsigned)((ctx->R + 63) / 64)), blk(64);
+    if (!with_slice(TleSlices{}, ens_slice(ctx->model), [&](auto s) { hipLaunchKernelGGL(tle_check_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, P, cache ? 1 : 0); }))
+        return ens_bad_slice(ctx);
+    HIP_TRY(ctx, hipGetLastError());
+    return RRRMC_OK;
 }
 
 // rrrMC(X::DoubleGraph) (standard = false) or standardMC (standard = true) on a GraphTopologicalLocalEntropy
 int32_t tle_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact)
 {
-    int32_t rc = RRRMC_OK;
-    if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphTopologicalLocalEntropy needs its neighbour lists and (γ, λ, β): call rrrmc_tle_set_topology and rrrmc_tle_set_params first");
-    if (iters < 0) return fail(ctx, RRRMC_ERR_INVALID_ARG, "iters must be >= 0, given %lld", (long long)iters);
-    if (step < 1) return fail(ctx, RRRMC_ERR_INVALID_ARG, "step must be >= 1, given %lld", (long long)step);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->results_valid = false; ctx->last_call_wtm = false; ctx->last_call_eo = false;
-    ctx->timing_valid = false;
-    SmpState S{};
-    if (!standard) { rc = smp_begin(ctx, 1, beta, staged_thr, staged_thr_fact, 0.0, step, nullptr, &S); if (rc) return rc; }
-    else S.samp0 = step;
-    const int64_t nsamp = standard ? iters / step : smp_nsamp(ctx, iters, step);
-    const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->R;
-    if (es_need > ctx->sk_Es_cap) {
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
-    while (ctx->ev_sweep.size() < 2) {
-        hipEvent_t e;
-        HIP_TRY(ctx, hipEventCreate(&e));
-        ctx->ev_sweep.push_back(e);
-    }
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_begin, st));
-    ctx->stats_stride = 2;
-    const bool cont = (standard && ctx->resume && ctx->std_cache_live) || S.resume;
-    if (!cont) { rc = tle_run_init(ctx, beta, !standard); if (rc) return rc; }
-    else {
-        rc = re_to_slices(ctx, tle_params(ctx, beta));          // (the same bits the run left: nothing in between changed the configuration)
-        if (rc) return rc;
-        if (!standard) HIP_TRY(ctx, hipMemsetAsync(ctx->q_stats, 0, sizeof(int64_t) * (size_t)ctx->R * 2, st));
-    }
+    EnsCall C;
+    int32_t rc = ens_call_begin(ctx, standard, beta, iters, step, staged_thr, staged_thr_fact, &C);
+    if (rc) return rc;
+    rc = C.cont ? ens_call_resume(ctx, tle_params(ctx, beta), standard) : tle_run_init(ctx, beta, !standard);
+    if (rc) return rc;
     TleParams P = tle_params(ctx, beta);
-    P.staged_thr = staged_thr;
-    P.lambda = staged_thr_fact / (double)ctx->N;              // RRRMC.jl:243
-    P.g0 = ctx->it_done; P.iters = iters; P.step = step; P.samp0 = S.samp0;
+    ens_call_params(ctx, C, iters, step, staged_thr, staged_thr_fact, &P);
+    hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_sweep[0], st));
     if (standard) {
-        TLE_LAUNCH(ctx, tle_standard_kernel, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, P);
+        const dim3 grid(rrr_blocks(ctx->R)), blk(rrr_tpb(ctx->R));
+        if (!with_slice(TleSlices{}, ens_slice(ctx->model), [&](auto s) { hipLaunchKernelGGL(tle_standard_kernel<decltype(s)::value>, grid, blk, 0, st, P); })) return ens_bad_slice(ctx);
     } else {
         // The build: the replica's hot state in LDS (the sets stay in global memory) when it fits and all R wavefronts are resident at
         // once, else everything in global memory.  Measured (profiles/r14/tle.md): on GraphSATTLE(1000, 3, 4.2, 3) the LDS build is 1.13x
@@ -111,52 +89,33 @@ int32_t tle_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, 
         const bool resident = state <= (size_t)kLdsLimit && (size_t)ctx->R <= (size_t)cus * ((size_t)kLdsLimit / state);
         const bool use_lds = state <= (size_t)kLdsLimit && !(no_lds && no_lds[0] == '1') && (resident || (want_lds && want_lds[0] == '1'));
         const size_t lds = tle_rrr_lds_bytes(use_lds, ctx->N, ctx->qW, ctx->qNk, 2 * ctx->tle_L);
-        const tle_kernel_fn fn = tle_rrr_fn(le_slice_of(ctx), use_lds);
+        const tle_kernel_fn fn = tle_rrr_fn(ens_slice(ctx->model), use_lds);
+        if (!fn) return ens_bad_slice(ctx);
         HIP_TRY(ctx, raise_lds_attr(reinterpret_cast<const void*>(fn), lds));
         hipLaunchKernelGGL(fn, dim3((unsigned)ctx->R), dim3(kTleWave), lds, st, P);
         ctx->tle_build = use_lds ? 1 : 2;
     }
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_sweep[1], st));
-    hipLaunchKernelGGL(re_from_slices_kernel, dim3((unsigned)((P.W + 255) / 256), (unsigned)P.R), dim3(256), 0, st, static_cast<const ReParams&>(P));
-    HIP_TRY(ctx, hipGetLastError());
-    if (ctx->debug_checks) {
-        if (!ctx->dbg_flag) { HIP_TRY(ctx, hipMalloc(&ctx->dbg_flag, sizeof(int32_t) * 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, st)); }
-        P.flag = ctx->dbg_flag;
-        TLE_LAUNCH(ctx, tle_check_kernel, dim3((unsigned)((ctx->R + 63) / 64)), dim3(64), 0, P, standard ? 0 : 1);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_end, st));
-    ctx->sweep_launches = 1;
-    ctx->nsamp = nsamp;
-    ctx->it_done += (uint64_t)iters;
-    if (!standard) smp_commit(ctx, 1, iters);
-    ctx->results_valid = true;
-    ctx->timing_valid = true;
-    ctx->last_call_rrr = true;          // accepted / staged counts live in q_stats
-    ctx->q_cache_valid = !standard;
-    ctx->std_cache_live = standard;
-    return RRRMC_OK;
+    return ens_call_end(ctx, P, C, standard, iters, [&] { return tle_debug_check(ctx, P, !standard); });
 }
 
 int32_t tle_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0)
 {
     if (!out) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
-    if (slice_kind < RRRMC_RE_SLICE_EMPTY || slice_kind > RRRMC_RE_SLICE_COMM_QU || slice_kind == 7)
+    if (ens_model(ENS_LE, slice_kind) == kEnsNoModel)          // (the Local Entropy ensemble has every slice kind there is)
         return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind must be one of rrrmc_re_slice, given: %d", slice_kind);
-    if (slice_kind != RRRMC_RE_SLICE_EMPTY && slice_kind != RRRMC_RE_SLICE_SK && slice_kind != RRRMC_RE_SLICE_SKN && slice_kind != RRRMC_RE_SLICE_SAT)
+    if (ens_model(ENS_TLE, slice_kind) == kEnsNoModel)
         return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "slice kind %d: the Topological Local Entropy kernels cover GraphEmpty, GraphSK, GraphSKNormal and GraphSAT slices", slice_kind);
     if (Nk < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "Nk and R must be >= 1");
     if (M <= 2) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "M must be greater than 2, given: %lld", (long long)M);      // TLE.jl:29
     if (M > kTleMmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "M = %lld: the Topological Local Entropy kernels cover M <= %d", (long long)M, kTleMmax);
     if (Nk * (M + 1) > kTleNmax)
         return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N = Nk*(M+1) = %lld is beyond the Topological Local Entropy kernels (16-bit set members: N <= 65535)", (long long)(Nk * (M + 1)));
-    const int32_t rc = le_ctx_create(out, Nk, M, slice_kind, R, device, replica0);
+    const int32_t rc = ens_ctx_create(ENS_LE, out, Nk, M, slice_kind, R, device, replica0);
     if (rc) return rc;
     rrrmc_ctx* ctx = *out;
-    ctx->model = slice_kind == RRRMC_RE_SLICE_SK ? RRRMC_MODEL_TLE_SK : slice_kind == RRRMC_RE_SLICE_SKN ? RRRMC_MODEL_TLE_SKN :
-                 slice_kind == RRRMC_RE_SLICE_SAT ? RRRMC_MODEL_TLE_SAT : RRRMC_MODEL_TLE_EMPTY;
+    ctx->model = ens_model(ENS_TLE, slice_kind);
     // the arrays sized by the level count come with rrrmc_tle_set_params
     free_dev(ctx->q_cls); free_dev(ctx->q_sv); free_dev(ctx->q_st); free_dev(ctx->q_T); free_dev(ctx->re_tab);
     ctx->re_htab.clear(); ctx->re_hft.clear(); ctx->le_hcode.clear();

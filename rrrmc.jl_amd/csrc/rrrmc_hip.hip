@@ -15,9 +15,11 @@
 #include <thread>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
+#include "ens_models.hpp"
 #include "sk_kernels.hpp"
 #include "sk_block_kernel.hpp"
 #include "sk_hblock_kernel.hpp"
@@ -269,7 +271,7 @@ struct rrrmc_ctx {
     size_t pairs_cap = 0;
     int32_t* d_ovl = nullptr;      // [pairs_cap][Rpad]
     int32_t* d_qobs = nullptr;     // GraphQuant: e0[R], Eslice[R][M], ovs_raw[R][M/2]
-    // ---- GraphRobustEnsemble (RRRMC_MODEL_RE_*): spins in q_spins / qW (ABI site order), qNk / qM, slices in q_Jb (binary SK) or sk_J +
+    // ---- GraphRobustEnsemble (ENS_RE of ens_models.hpp): spins in q_spins / qW (ABI site order), qNk / qM, slices in q_Jb (binary SK) or sk_J +
     //      q_slf / q_smv / q_scur (GraphSKNormal), the DeltaECache in q_cls / q_sv / q_spos / q_st / q_T / q_z, E in sk_E, counts in q_stats ----
     uint32_t* re_sp = nullptr;     // [R][qW] slice-major working copy of the spins
     int8_t* re_mu = nullptr;       // [R][Nk]
@@ -278,12 +280,12 @@ struct rrrmc_ctx {
     std::vector<double> re_htab;   // host copy of the first two tables
     std::vector<double> re_hft;    // staging of ft
     bool re_params_set = false;
-    // ---- GraphLocalEntropy (RRRMC_MODEL_LE_*): the Robust Ensemble's buffers above with M + 1 rows (row 0 the centre); re_htab = allΔE,
+    // ---- GraphLocalEntropy (ENS_LE): the Robust Ensemble's buffers above with M + 1 rows (row 0 the centre); re_htab = allΔE,
     //      re_tab = allΔE, ft, the class codes; re_Eslice = [R][M + 1] (row 0: cenergy) ----
     int64_t* le_dist = nullptr;    // [R][M][M] distances
     double le_gT = 0.0;            // γT = γ / β (LE.jl:221-225)
     std::vector<uint8_t> le_hcode; // class codes of lfields = -M .. M (host_le.hpp)
-    // ---- GraphTopologicalLocalEntropy (RRRMC_MODEL_TLE_*; host_tle.hpp): a Local Entropy context whose re_tab (allΔE [L], ft [L]), q_sv,
+    // ---- GraphTopologicalLocalEntropy (ENS_TLE; host_tle.hpp): a Local Entropy context whose re_tab (allΔE [L], ft [L]), q_sv,
     //      q_st and q_T are sized by rrrmc_tle_set_params (L = tle_L); le_gT = γT ----
     int32_t* tle_rowptr = nullptr; // [Nk + 1] the neighbour lists ∂i, CSR
     int32_t* tle_cols = nullptr;   // [tle_rowptr[Nk]]
@@ -294,7 +296,7 @@ struct rrrmc_ctx {
     double tle_lT = 0.0;           // λT = λ / β (TLE.jl:390-396)
     bool tle_topology_set = false;
     int tle_build = 0;             // the build of the last rrrMC call: 1 hot state in LDS, 2 in global memory; 0 none yet
-    // ---- the binary perceptron (RRRMC_MODEL_PERC_*, and the slices of RRRMC_MODEL_RE_PERC_* / _LE_PERC_*; host_perc.hpp): spins in q_spins,
+    // ---- the binary perceptron (RRRMC_MODEL_PERC_*, and the perceptron slices of the ensembles; host_perc.hpp): spins in q_spins,
     //      E in sk_E, counts in q_stats ----
     uint64_t* pc_col = nullptr;    // [Nk][PW] patterns, one column per synapse
     uint32_t* pc_row = nullptr;    // [P][2 ceil(Nk/64)] patterns, one row per pattern (the ABI's chunks)
@@ -302,7 +304,7 @@ struct rrrmc_ctx {
     uint64_t* pc_pm = nullptr;     // [R][rows][PW] the set p
     uint64_t* pc_mm = nullptr;     // [R][rows][PW] the set m
     int64_t pc_P = 0;
-    // ---- the binary committee machines (RRRMC_MODEL_COMM_*, and the slices of RRRMC_MODEL_RE_COMM_* / _LE_COMM_*; host_comm.hpp): spins
+    // ---- the binary committee machines (RRRMC_MODEL_COMM_*, and the committee slices of the ensembles; host_comm.hpp): spins
     //      in q_spins, E in sk_E, counts in q_stats ----
     uint64_t* cm_col = nullptr;    // [Nk][PW] patterns, one column per synapse
     uint32_t* cm_row = nullptr;    // [P][2 ceil(Nk/64)] patterns, one row per pattern (the ABI's chunks)
@@ -310,7 +312,7 @@ struct rrrmc_ctx {
     int16_t* cm_ds = nullptr;      // [R][rows][K2 + 1][64 PW] Δ1 of every unit, Δ2
     uint64_t* cm_mk = nullptr;     // [R][rows][2 K2 + 2][PW] the sets p1, m1 of every unit, p2, m2
     int64_t cm_P = 0, cm_K2 = 0;
-    // ---- random K-SAT (RRRMC_MODEL_SAT, and the slices of RRRMC_MODEL_RE_SAT / _LE_SAT; host_sat.hpp): spins in q_spins, E in sk_E, counts
+    // ---- random K-SAT (RRRMC_MODEL_SAT, and the K-SAT slices of the ensembles; host_sat.hpp): spins in q_spins, E in sk_E, counts
     //      in q_stats; no per-chain cache ----
     uint32_t* sat_off = nullptr;   // [Nk + 1] the occurrence program's CSR (sat_core.hpp)
     SatEntry* sat_ent = nullptr;   // [sat_off[Nk]] one 16-byte entry per occurrence
@@ -509,12 +511,9 @@ hipError_t raise_lds_attr(const void* fn, size_t bytes)
 }
 
 inline bool chunk_layout(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_QUANT_RRG || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_SPARSE_LEVELS ||
-                                                       ctx->model == RRRMC_MODEL_RE_EMPTY || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_RE_SKN ||
-                                                       ctx->model == RRRMC_MODEL_LE_EMPTY || ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_LE_SKN ||
-                                                       (ctx->model >= RRRMC_MODEL_PERC_STEP && ctx->model <= RRRMC_MODEL_LE_COMM_RELU) ||
-                                                       ctx->model == RRRMC_MODEL_SAT || ctx->model == RRRMC_MODEL_RE_SAT || ctx->model == RRRMC_MODEL_LE_SAT ||
-                                                       ctx->model == RRRMC_MODEL_COMM_QU || ctx->model == RRRMC_MODEL_RE_COMM_QU || ctx->model == RRRMC_MODEL_LE_COMM_QU ||
-                                                       (ctx->model >= RRRMC_MODEL_TLE_EMPTY && ctx->model <= RRRMC_MODEL_TLE_SAT); }
+                                                       ctx->model == RRRMC_MODEL_PERC_STEP || ctx->model == RRRMC_MODEL_PERC_LINEAR ||
+                                                       ctx->model == RRRMC_MODEL_COMM_STEP || ctx->model == RRRMC_MODEL_COMM_RELU || ctx->model == RRRMC_MODEL_COMM_QU ||
+                                                       ctx->model == RRRMC_MODEL_SAT || ens_family(ctx->model) != ENS_NONE; }
 inline bool sparse_int_model(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_SPARSE_PM1 || ctx->model == RRRMC_MODEL_SPARSE_LEVELS; }
 inline double lv_to_f64(const rrrmc_ctx* ctx, long long units) { return (double)(units * ctx->lv_mul) / ctx->lv_div; }
 
@@ -600,12 +599,17 @@ __global__ void dbg_compare_f64_kernel(const double* a, const double* b, long lo
 __global__ void dbg_inject_i32_kernel(int32_t* a) { a[0] += 2; }          // fault injection for the test of the failing branch
 __global__ void dbg_inject_f64_kernel(double* a) { a[0] += 1.0; }
 inline bool dbg_inject() { const char* e = std::getenv("RRRMC_DEBUG_INJECT"); return e && e[0] == '1'; }
+// the checks' flag, allocated on first use.  It is zeroed when it is allocated and by rrrmc_sync after reading it, never by a check: a mismatch
+// found after an earlier queued call must survive until the sync that reports it.
+int32_t dbg_flag_ensure(rrrmc_ctx* ctx)
+{
+    if (!ctx->dbg_flag) { HIP_TRY(ctx, hipMalloc(&ctx->dbg_flag, sizeof(int32_t) * 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, ctx->stream)); }
+    return RRRMC_OK;
+}
 // after a standardMC call of the +-J model: d_E (tracked) against energy(X, C) recomputed from the spins
 int32_t debug_check_pm1(rrrmc_ctx* ctx)
 {
-    // (the flag is zeroed when it is allocated and by rrrmc_sync after reading it, never here: a mismatch found after an earlier queued call
-    //  must survive until the sync that reports it)
-    if (!ctx->dbg_flag) { HIP_TRY(ctx, hipMalloc(&ctx->dbg_flag, sizeof(int32_t) * 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, ctx->stream)); }
+    { const int32_t rcf = dbg_flag_ensure(ctx); if (rcf) return rcf; }
     if (!ctx->dbg_Ei) HIP_TRY(ctx, hipMalloc(&ctx->dbg_Ei, sizeof(int32_t) * ctx->Rpad));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->dbg_Ei, ctx->d_E, sizeof(int32_t) * ctx->Rpad, hipMemcpyDeviceToDevice, ctx->stream));
     if (dbg_inject()) hipLaunchKernelGGL(dbg_inject_i32_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->dbg_Ei);       // (RRRMC_DEBUG_INJECT=1: tests only)
@@ -659,6 +663,7 @@ inline void smp_commit(rrrmc_ctx* ctx, int kind, int64_t n) { ctx->smp_kind = ki
 #include "host_comm.hpp"
 #include "host_quant_pat.hpp"
 #include "host_sat.hpp"
+#include "host_ens.hpp"
 #include "host_re.hpp"
 #include "host_le.hpp"
 #include "host_tle.hpp"
@@ -1678,7 +1683,7 @@ int32_t rrrmc_ctx_create_quant_pattern(rrrmc_ctx** out, int32_t slice_kind, int6
 // ---- GraphRobustEnsemble: exported entry points (host_re.hpp) ---------------------------------------------------------------------
 int32_t rrrmc_ctx_create_re(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0)
 {
-    return re_ctx_create(out, Nk, M, slice_kind, R, device, replica0);
+    return ens_ctx_create(ENS_RE, out, Nk, M, slice_kind, R, device, replica0);
 }
 
 int32_t rrrmc_re_tables(int64_t M, double gamma, double beta, double* dElist, double* e0)
@@ -1724,17 +1729,8 @@ int32_t rrrmc_re_energies(rrrmc_ctx* ctx, double* out)
     rc = re_to_slices(ctx, P);
     if (rc) return rc;
     const dim3 grid((unsigned)((ctx->R * ctx->qM + 63) / 64)), blk(64);
-    switch (re_slice_of(ctx)) {
-        case RE_SK: hipLaunchKernelGGL(re_energies_kernel<RE_SK>, grid, blk, 0, ctx->stream, P); break;
-        case RE_SKN: hipLaunchKernelGGL(re_energies_kernel<RE_SKN>, grid, blk, 0, ctx->stream, P); break;
-        case RE_PSTEP: hipLaunchKernelGGL(re_energies_kernel<RE_PSTEP>, grid, blk, 0, ctx->stream, P); break;
-        case RE_PLIN: hipLaunchKernelGGL(re_energies_kernel<RE_PLIN>, grid, blk, 0, ctx->stream, P); break;
-        case RE_CSTEP: hipLaunchKernelGGL(re_energies_kernel<RE_CSTEP>, grid, blk, 0, ctx->stream, P); break;
-        case RE_CRELU: hipLaunchKernelGGL(re_energies_kernel<RE_CRELU>, grid, blk, 0, ctx->stream, P); break;
-        case RE_CQU: hipLaunchKernelGGL(re_energies_kernel<RE_CQU>, grid, blk, 0, ctx->stream, P); break;
-        case RE_SAT: hipLaunchKernelGGL(re_energies_kernel<RE_SAT>, grid, blk, 0, ctx->stream, P); break;
-        default: hipLaunchKernelGGL(re_energies_kernel<RE_EMPTY>, grid, blk, 0, ctx->stream, P); break;
-    }
+    if (!with_slice(AllSlices{}, ens_slice(ctx->model), [&](auto s) { hipLaunchKernelGGL(re_energies_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, P); }))
+        return ens_bad_slice(ctx);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out, ctx->re_Eslice, sizeof(double) * (size_t)(ctx->R * ctx->qM), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1862,7 +1858,7 @@ int32_t rrrmc_gen_ksat(int64_t N, int64_t K, double alpha, uint64_t seed, int64_
 // ---- GraphLocalEntropy: exported entry points (host_le.hpp) ----------------------------------------------------------------------
 int32_t rrrmc_ctx_create_le(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0)
 {
-    return le_ctx_create(out, Nk, M, slice_kind, R, device, replica0);
+    return ens_ctx_create(ENS_LE, out, Nk, M, slice_kind, R, device, replica0);
 }
 
 int32_t rrrmc_le_tables(int64_t M, double gamma, double beta, double* dElist)
@@ -2035,11 +2031,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                          : model == RRRMC_MODEL_QUANT_COMM_STEP ? RRRMC_RE_SLICE_COMM_STEP : model == RRRMC_MODEL_QUANT_COMM_RELU ? RRRMC_RE_SLICE_COMM_RELU
                          : model == RRRMC_MODEL_QUANT_COMM_QU ? RRRMC_RE_SLICE_COMM_QU : 0;
     const bool quant = model == RRRMC_MODEL_QUANT_RRG || model == RRRMC_MODEL_QUANT_SK || model == RRRMC_MODEL_QUANT_SKN || model == RRRMC_MODEL_QUANT_F64 || qpat;
-    const bool re = model == RRRMC_MODEL_RE_EMPTY || model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_RE_SKN || model == RRRMC_MODEL_RE_PERC_STEP || model == RRRMC_MODEL_RE_PERC_LINEAR ||
-                    model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_RE_COMM_RELU || model == RRRMC_MODEL_RE_SAT || model == RRRMC_MODEL_RE_COMM_QU;
-    const bool le = model == RRRMC_MODEL_LE_EMPTY || model == RRRMC_MODEL_LE_SK || model == RRRMC_MODEL_LE_SKN || model == RRRMC_MODEL_LE_PERC_STEP || model == RRRMC_MODEL_LE_PERC_LINEAR ||
-                    model == RRRMC_MODEL_LE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_RELU || model == RRRMC_MODEL_LE_SAT || model == RRRMC_MODEL_LE_COMM_QU;
-    const bool tle = model >= RRRMC_MODEL_TLE_EMPTY && model <= RRRMC_MODEL_TLE_SAT;
+    const bool re = ens_family(model) == ENS_RE, le = ens_family(model) == ENS_LE, tle = ens_family(model) == ENS_TLE;
     const bool sat = model == RRRMC_MODEL_SAT;
     const bool pc = model == RRRMC_MODEL_PERC_STEP || model == RRRMC_MODEL_PERC_LINEAR;
     const bool cm = model == RRRMC_MODEL_COMM_STEP || model == RRRMC_MODEL_COMM_RELU || model == RRRMC_MODEL_COMM_QU;
@@ -2047,15 +2039,6 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
         delete ctx;
         return fail(nullptr, RRRMC_ERR_INVALID_ARG, "a committee machine takes N = K1*K2 and K = K2 with N %% K2 == 0, given N = %lld, K = %lld", (long long)N, (long long)K);
     }
-    const int32_t ens_slice = model == RRRMC_MODEL_RE_SK || model == RRRMC_MODEL_LE_SK || model == RRRMC_MODEL_TLE_SK ? RRRMC_RE_SLICE_SK
-                              : model == RRRMC_MODEL_RE_SKN || model == RRRMC_MODEL_LE_SKN || model == RRRMC_MODEL_TLE_SKN ? RRRMC_RE_SLICE_SKN
-                              : model == RRRMC_MODEL_RE_PERC_STEP || model == RRRMC_MODEL_LE_PERC_STEP ? RRRMC_RE_SLICE_PERC_STEP
-                              : model == RRRMC_MODEL_RE_PERC_LINEAR || model == RRRMC_MODEL_LE_PERC_LINEAR ? RRRMC_RE_SLICE_PERC_LINEAR
-                              : model == RRRMC_MODEL_RE_COMM_STEP || model == RRRMC_MODEL_LE_COMM_STEP ? RRRMC_RE_SLICE_COMM_STEP
-                              : model == RRRMC_MODEL_RE_COMM_RELU || model == RRRMC_MODEL_LE_COMM_RELU ? RRRMC_RE_SLICE_COMM_RELU
-                              : model == RRRMC_MODEL_RE_SAT || model == RRRMC_MODEL_LE_SAT || model == RRRMC_MODEL_TLE_SAT ? RRRMC_RE_SLICE_SAT
-                              : model == RRRMC_MODEL_RE_COMM_QU || model == RRRMC_MODEL_LE_COMM_QU ? RRRMC_RE_SLICE_COMM_QU
-                                                                                                       : RRRMC_RE_SLICE_EMPTY;
     ctx->model = quant ? RRRMC_MODEL_QUANT_RRG : model; ctx->K = K; ctx->R = R; ctx->replica0 = replica0; ctx->device = device_ids[0];
     ctx->N = quant || re ? N * M : le || tle ? N * (M + 1) : N;
     if (re || le || tle) { ctx->qNk = N; ctx->qM = M; }
@@ -2073,9 +2056,9 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : model == RRRMC_MODEL_QUANT_SKN ? rrrmc_ctx_create_quant_skn(&c, N, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_QUANT_F64 ? rrrmc_ctx_create_quant_f64(&c, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : qpat ? rrrmc_ctx_create_quant_pattern(&c, qpat, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
-                           : re ? rrrmc_ctx_create_re(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
-                           : le ? rrrmc_ctx_create_le(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
-                           : tle ? rrrmc_ctx_create_tle(&c, N, M, ens_slice, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : re ? rrrmc_ctx_create_re(&c, N, M, ens_slice(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : le ? rrrmc_ctx_create_le(&c, N, M, ens_slice(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : tle ? rrrmc_ctx_create_tle(&c, N, M, ens_slice(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : pc ? rrrmc_ctx_create_perc(&c, N, model == RRRMC_MODEL_PERC_LINEAR, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : sat ? rrrmc_ctx_create_sat(&c, N, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_COMM_QU ? rrrmc_ctx_create_comm_qu(&c, N / K, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
@@ -2319,9 +2302,7 @@ int32_t rrrmc_bkl_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t s
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone GraphSAT (standardMC is)");
-    if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
-    if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
-    if (is_tle(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the GraphTopologicalLocalEntropy (rrrMC and standardMC are)");
+    if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "bklMC");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for a GraphQuant over pattern machines (DeltaECacheCont over AllButOne neighbourhoods): rrrMC and standardMC are");
     if (!std::isfinite(beta)) return fail(ctx, RRRMC_ERR_INVALID_ARG, "beta must be finite, given: %g", beta);
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
@@ -2363,9 +2344,7 @@ int32_t rrrmc_wtm_mc_async(rrrmc_ctx* ctx, double beta, int64_t samples, double 
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone GraphSAT (standardMC is)");
-    if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
-    if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
-    if (is_tle(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the GraphTopologicalLocalEntropy (rrrMC and standardMC are)");
+    if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "wtmMC");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for a GraphQuant over pattern machines (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
         return spf_cont_async(ctx, 2, beta, samples, 1, step, 0.0, 5.0);
@@ -2395,9 +2374,7 @@ int32_t rrrmc_extremal_opt_async(rrrmc_ctx* ctx, const double* ftau, int64_t ite
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone GraphSAT (standardMC is)");
-    if (is_re(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphRobustEnsemble (rrrMC and standardMC are)");
-    if (is_le(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphLocalEntropy (rrrMC and standardMC are)");
-    if (is_tle(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the GraphTopologicalLocalEntropy (rrrMC and standardMC are)");
+    if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "extremal_opt");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for a GraphQuant over pattern machines (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)        // not DiscrGraphs: EOCacheCont
         return spf_cont_async(ctx, 3, 0.0, iters, step, 1.0, 0.0, 0.0, ftau);
@@ -2519,7 +2496,7 @@ int32_t rrrmc_set_couplings_dense(rrrmc_ctx* ctx, const double* J)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_dense(c, J));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qskn = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn) || ctx->model == RRRMC_MODEL_RE_SKN || ctx->model == RRRMC_MODEL_LE_SKN || ctx->model == RRRMC_MODEL_TLE_SKN;   // slice graphs: J is Nk x Nk
+    const bool qskn = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn) || ens_slice(ctx->model) == RRRMC_RE_SLICE_SKN;   // slice graphs: J is Nk x Nk
     if (ctx->model != RRRMC_MODEL_SK_NORMAL && !qskn) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_dense is for RRRMC_MODEL_SK_NORMAL (or a GraphQuant over GraphSKNormal slices)");
     if (!J) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J is NULL");
     const int64_t N = qskn ? ctx->qNk : ctx->N;
@@ -2564,18 +2541,10 @@ int32_t rrrmc_energy_f64(rrrmc_ctx* ctx, double* E_out)
     } else if (is_sat(ctx)) {
         ctx->std_cache_live = false;
         rc = sat_run_init(ctx);
-    } else if (is_re(ctx)) {
-        if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphRobustEnsemble needs (gamma, beta): call rrrmc_re_set_params first");
+    } else if (ens_family(ctx->model) != ENS_NONE) {
+        if (!ctx->re_params_set) return ens_needs_params(ctx, false);
         ctx->std_cache_live = false;
-        rc = re_run_init(ctx, 1.0, false);
-    } else if (is_tle(ctx)) {
-        if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphTopologicalLocalEntropy needs its neighbour lists and (gamma, lambda, beta): call rrrmc_tle_set_topology and rrrmc_tle_set_params first");
-        ctx->std_cache_live = false;
-        rc = tle_run_init(ctx, 1.0, false);
-    } else if (is_le(ctx)) {
-        if (!ctx->re_params_set) return fail(ctx, RRRMC_ERR_STATE, "a GraphLocalEntropy needs (gamma, beta): call rrrmc_le_set_params first");
-        ctx->std_cache_live = false;
-        rc = le_run_init(ctx, 1.0, false);
+        rc = is_re(ctx) ? re_run_init(ctx, 1.0, false) : is_le(ctx) ? le_run_init(ctx, 1.0, false) : tle_run_init(ctx, 1.0, false);
     } else if (ctx->model == RRRMC_MODEL_SPARSE_F64) {
         rc = spf_run_energy(ctx);
     } else if (ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED) {
@@ -2668,7 +2637,7 @@ int32_t rrrmc_set_couplings_bits(rrrmc_ctx* ctx, const uint64_t* Jc)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_bits(c, Jc));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qsk = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk) || ctx->model == RRRMC_MODEL_RE_SK || ctx->model == RRRMC_MODEL_LE_SK || ctx->model == RRRMC_MODEL_TLE_SK;     // the slice graph of a GraphQSKT / GraphSKRE / GraphSKLE
+    const bool qsk = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk) || ens_slice(ctx->model) == RRRMC_RE_SLICE_SK;     // the slice graph of a GraphQSKT / GraphSKRE / GraphSKLE
     if (ctx->model != RRRMC_MODEL_SK_BINARY && !qsk)
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_bits is for RRRMC_MODEL_SK_BINARY and for contexts made by rrrmc_ctx_create_quant_sk");
     if (!Jc) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J_chunks is NULL");
