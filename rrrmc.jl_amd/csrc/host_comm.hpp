@@ -86,13 +86,13 @@ int32_t comm_set_patterns(rrrmc_ctx* ctx, int64_t K2, const uint64_t* xi, const 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (P != ctx->cm_P || K2 != ctx->cm_K2 || !ctx->cm_col) {
-        free_dev(ctx->cm_col); free_dev(ctx->cm_row); free_dev(ctx->cm_lab); free_dev(ctx->cm_ds); free_dev(ctx->cm_mk);
+        dev_free(ctx, ctx->cm_col); dev_free(ctx, ctx->cm_row); dev_free(ctx, ctx->cm_lab); dev_free(ctx, ctx->cm_ds); dev_free(ctx, ctx->cm_mk);
         ctx->cm_P = 0; ctx->graph_set = false;
-        HIP_TRY(ctx, hipMalloc(&ctx->cm_col, sizeof(uint64_t) * (size_t)(N * PW)));
-        HIP_TRY(ctx, hipMalloc(&ctx->cm_row, sizeof(uint64_t) * (size_t)(P * nch)));
-        HIP_TRY(ctx, hipMalloc(&ctx->cm_lab, sizeof(uint64_t) * (size_t)(2 * PW)));
-        HIP_TRY(ctx, hipMalloc(&ctx->cm_ds, sizeof(int16_t) * (size_t)ctx->R * (size_t)rows * comm_ds_row((int)K2, (int)PW, qu)));
-        HIP_TRY(ctx, hipMalloc(&ctx->cm_mk, sizeof(uint64_t) * (size_t)ctx->R * (size_t)rows * comm_mk_row((int)K2, (int)PW, qu)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->cm_col, (size_t)(N * PW)));
+        HIP_TRY(ctx, dev_alloc_bytes(ctx, ctx->cm_row, sizeof(uint64_t) * (size_t)(P * nch)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->cm_lab, (size_t)(2 * PW)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->cm_ds, (size_t)ctx->R * (size_t)rows * comm_ds_row((int)K2, (int)PW, qu)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->cm_mk, (size_t)ctx->R * (size_t)rows * comm_mk_row((int)K2, (int)PW, qu)));
         ctx->cm_P = P; ctx->cm_K2 = K2;
     }
     HIP_TRY(ctx, hipMemcpy(ctx->cm_col, col.data(), sizeof(uint64_t) * col.size(), hipMemcpyHostToDevice));
@@ -139,12 +139,7 @@ int32_t comm_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step)
     ctx->timing_valid = false;
     const int64_t nsamp = iters / step;
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->R;
-    if (es_need > ctx->sk_Es_cap) {
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->sk_Es, ctx->sk_Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -167,7 +162,7 @@ int32_t comm_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step)
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_sweep[1], st));
     if (ctx->debug_checks) {
-        if (!ctx->dbg_flag) { HIP_TRY(ctx, hipMalloc(&ctx->dbg_flag, sizeof(int32_t) * 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, st)); }
+        if (!ctx->dbg_flag) { HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_flag, 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, st)); }
         P.flag = ctx->dbg_flag;
         const dim3 grid((unsigned)((ctx->R + 63) / 64)), blk(64);
         switch (kind) {
@@ -196,36 +191,18 @@ int32_t comm_ctx_create(rrrmc_ctx** out, int64_t K1, int64_t K2, int kind, int64
     if (R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "R must be >= 1");
     { const int32_t rck = comm_check_k(nullptr, K1, K2, kind != CK_STEP); if (rck) return rck; }
     if (replica0 % 32) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "replica0 must be a multiple of 32 (given %u)", replica0);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, RRRMC_ERR_HIP, "no HIP device is visible: this library has no CPU path");
-    if (device < 0 || device >= ndev) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-    rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
-    if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
+    rrrmc_ctx* ctx = nullptr;
+    { const int32_t rcb = ctx_create_begin(&ctx, device, false); if (rcb) return rcb; }
     const int64_t N = K1 * K2;
     ctx->model = kind == CK_QU ? RRRMC_MODEL_COMM_QU : kind == CK_RELU ? RRRMC_MODEL_COMM_RELU : RRRMC_MODEL_COMM_STEP;
     ctx->N = N; ctx->K = 0; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = N; ctx->qM = 1; ctx->qW = 2 * ((N + 63) / 64);
     ctx->cm_K2 = K2;
-    ctx->device = device; ctx->replica0 = replica0;
-#define COMM_TRY(expr)                                                                                           \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            int32_t rc_ = fail(nullptr, RRRMC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));           \
-            rrrmc_ctx_destroy(ctx);                                                                              \
-            return rc_;                                                                                          \
-        }                                                                                                        \
-    } while (0)
-    COMM_TRY(hipSetDevice(device));
-    COMM_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    COMM_TRY(hipEventCreate(&ctx->ev_begin));
-    COMM_TRY(hipEventCreate(&ctx->ev_end));
-    COMM_TRY(hipMalloc(&ctx->q_spins, sizeof(uint32_t) * R * ctx->qW));
-    COMM_TRY(hipMalloc(&ctx->q_stats, sizeof(int64_t) * R * 2));
-    COMM_TRY(hipMalloc(&ctx->sk_E, sizeof(double) * R));
-    COMM_TRY(hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
-#undef COMM_TRY
+    ctx->replica0 = replica0;
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_spins, R * ctx->qW));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_stats, R * 2));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_E, R));
+    CTX_CREATE_TRY(ctx, false, hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
     *out = ctx;
     return RRRMC_OK;
 }

@@ -1,6 +1,6 @@
 // Host side of the discretised DoubleGraphs (Graph{RRG,EA}NormalDiscretized) under rrrMC.
 // Included by rrrmc_hip.hip inside its anonymous namespace, after the context struct and the common helpers
-// (fail, HIP_TRY, free_dev, ensure_state); not a stand-alone translation unit.
+// (fail, HIP_TRY, dev_alloc / dev_free, ensure_state); not a stand-alone translation unit.
 // ---- DoubleGraphs Graph{RRG,EA}NormalDiscretized host side -----------------------------------------------------------
 double host_det_exp(double x);
 int32_t dbl_ctx_create(rrrmc_ctx** out, int64_t N, int64_t K, int64_t R, int32_t device, uint32_t replica0)
@@ -8,44 +8,26 @@ int32_t dbl_ctx_create(rrrmc_ctx** out, int64_t N, int64_t K, int64_t R, int32_t
     if (N < 1 || K < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "N, K, R must be >= 1 (given N=%lld K=%lld R=%lld)", (long long)N, (long long)K, (long long)R);
     if (K > kDKmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "K=%lld: the DoubleGraph kernel covers K <= %d", (long long)K, kDKmax);
     if (N > (int64_t)1 << 28) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N=%lld is beyond the DoubleGraph kernels (N <= 2^28)", (long long)N);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, RRRMC_ERR_HIP, "no HIP device is visible: this library has no CPU path");
-    if (device < 0 || device >= ndev) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-    rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
-    if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
+    rrrmc_ctx* ctx = nullptr;
+    { const int32_t rcb = ctx_create_begin(&ctx, device, true); if (rcb) return rcb; }
     ctx->model = RRRMC_MODEL_SPARSE_DISCRETIZED; ctx->N = N; ctx->K = K; ctx->R = R; ctx->Rpad = R;
     ctx->qW = 2 * ((N + 63) / 64);
-    ctx->device = device; ctx->replica0 = replica0;
-#define DB_TRY(expr)                                                                                             \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            int32_t rc_ = fail(nullptr, e_ == hipErrorOutOfMemory ? RRRMC_ERR_NOMEM : RRRMC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            rrrmc_ctx_destroy(ctx);                                                                              \
-            return rc_;                                                                                          \
-        }                                                                                                        \
-    } while (0)
-    DB_TRY(hipSetDevice(device));
-    DB_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    DB_TRY(hipEventCreate(&ctx->ev_begin));
-    DB_TRY(hipEventCreate(&ctx->ev_end));
-    DB_TRY(hipMalloc(&ctx->d_A, sizeof(int32_t) * N * K));
-    DB_TRY(hipMalloc(&ctx->db_dJ, sizeof(int8_t) * N * K));
-    DB_TRY(hipMalloc(&ctx->db_rJ, sizeof(double) * N * K));
-    DB_TRY(hipMalloc(&ctx->q_spins, sizeof(uint32_t) * R * ctx->qW));
-    DB_TRY(hipMalloc(&ctx->db_cls, (size_t)R * N));
+    ctx->replica0 = replica0;
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->d_A, N * K));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->db_dJ, N * K));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->db_rJ, N * K));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->q_spins, R * ctx->qW));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->db_cls, (size_t)R * N));
     const size_t idx_bytes = N > 65535 ? sizeof(uint32_t) : sizeof(uint16_t);          // set members / positions: 32-bit beyond 65 535 spins
-    DB_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->db_sv), idx_bytes * (size_t)R * 2 * kDLmax * N));
-    DB_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->db_spos), idx_bytes * (size_t)R * N));
-    DB_TRY(hipMalloc(&ctx->db_lf, sizeof(double) * (size_t)R * N));
-    DB_TRY(hipMalloc(&ctx->db_undo, sizeof(double) * (size_t)R * (K + 1)));
-    DB_TRY(hipMalloc(&ctx->q_stats, sizeof(int64_t) * R * 3));          // rrrMC / standardMC use a stride of 2, bklMC / wtmMC of 3
-    DB_TRY(hipMalloc(&ctx->sk_E, sizeof(double) * R));
-    DB_TRY(hipMalloc(&ctx->d_acc, sizeof(int64_t) * R));
-    DB_TRY(hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
-    DB_TRY(hipMemset(ctx->q_stats, 0, sizeof(int64_t) * R * 3));
-#undef DB_TRY
+    CTX_CREATE_TRY(ctx, true, dev_alloc_bytes(ctx, ctx->db_sv, idx_bytes * (size_t)R * 2 * kDLmax * N));
+    CTX_CREATE_TRY(ctx, true, dev_alloc_bytes(ctx, ctx->db_spos, idx_bytes * (size_t)R * N));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->db_lf, (size_t)R * N));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->db_undo, (size_t)R * (K + 1)));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->q_stats, R * 3));          // rrrMC / standardMC use a stride of 2, bklMC / wtmMC of 3
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->sk_E, R));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->d_acc, R));
+    CTX_CREATE_TRY(ctx, true, hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
+    CTX_CREATE_TRY(ctx, true, hipMemset(ctx->q_stats, 0, sizeof(int64_t) * R * 3));
     *out = ctx;
     return RRRMC_OK;
 }
@@ -86,12 +68,7 @@ int32_t dbl_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, 
     else S.samp0 = step;
     const int64_t nsamp = standard ? iters / step : smp_nsamp(ctx, iters, step);
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->R;
-    if (es_need > ctx->sk_Es_cap) {
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->sk_Es, ctx->sk_Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -101,7 +78,7 @@ int32_t dbl_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, 
     P.S = S;
     P.staged_thr = staged_thr; P.lambda = staged_thr_fact / (double)ctx->N;
     P.g0 = ctx->it_done; P.iters = iters; P.step = step;
-    if (!ctx->db_mlast) HIP_TRY(ctx, hipMalloc(&ctx->db_mlast, sizeof(int32_t) * (size_t)ctx->R));
+    if (!ctx->db_mlast) HIP_TRY(ctx, dev_alloc(ctx, ctx->db_mlast, (size_t)ctx->R));
     P.mlast = ctx->db_mlast;
     P.resume = (standard && ctx->resume && ctx->std_cache_live) ? 1 : 0;      // continue from the tracked energy / residual cache
     hipStream_t st = ctx->stream;

@@ -1,6 +1,6 @@
 // Host code that the three ensembles share (GraphRobustEnsemble, GraphLocalEntropy, GraphTopologicalLocalEntropy): the slice dispatcher, context
 // creation and the frame of a sampler call.  Included by rrrmc_hip.hip inside its anonymous namespace, after the context struct and the common
-// helpers (fail, HIP_TRY, free_dev, dbg_flag_ensure, smp_begin) and before host_re.hpp / host_le.hpp / host_tle.hpp, which keep what differs:
+// helpers (fail, HIP_TRY, dev_alloc / dev_free, dbg_flag_ensure, smp_begin) and before host_re.hpp / host_le.hpp / host_tle.hpp, which keep what differs:
 // their tables, *_params, *_run_init, the build choice and the launch.  Not a stand-alone translation unit.
 //
 // The model <-> (ensemble, slice kind) relation is the table of ens_models.hpp.  ens_slice(model) selects the kernels' SLICE template
@@ -74,12 +74,7 @@ int32_t ens_call_begin(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters
     else C->S.samp0 = step;
     C->nsamp = standard ? iters / step : smp_nsamp(ctx, iters, step);
     const size_t es_need = (size_t)(C->nsamp > 0 ? C->nsamp : 1) * ctx->R;
-    if (es_need > ctx->sk_Es_cap) {
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->sk_Es, ctx->sk_Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -148,16 +143,12 @@ int32_t ens_ctx_create(EnsFamily family, rrrmc_ctx** out, int64_t Nk, int64_t M,
     if (N > 65535)
         return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N = Nk*%s = %lld is beyond the %s kernels (16-bit set members: N <= 65535)", re ? "M" : "(M+1)", (long long)N, name);
     if (replica0 % 32) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "replica0 must be a multiple of 32 (given %u)", replica0);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, RRRMC_ERR_HIP, "no HIP device is visible: this library has no CPU path");
-    if (device < 0 || device >= ndev) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-    rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
-    if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
+    rrrmc_ctx* ctx = nullptr;
+    { const int32_t rcb = ctx_create_begin(&ctx, device, false); if (rcb) return rcb; }
     ctx->model = ens_model(family, slice_kind);
     ctx->N = N; ctx->K = 0; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = Nk; ctx->qM = M; ctx->qW = 2 * ((N + 63) / 64); ctx->q_Wk = 2 * ((Nk + 63) / 64);
-    ctx->device = device; ctx->replica0 = replica0;
+    ctx->replica0 = replica0;
     ctx->graph_set = slice_kind == RRRMC_RE_SLICE_EMPTY;          // Graph0RE / Graph0LE has no couplings to give
     // Robust Ensemble: host tables ΔElist [M], the μ-energies [M + 1]; device: the same, then ft [L].
     // Local Entropy: host tables allΔE [L], the class codes [2M + 1] apart in le_hcode; device: allΔE [L], ft [L], the codes.  re_hft stages ft [L].
@@ -165,44 +156,30 @@ int32_t ens_ctx_create(EnsFamily family, rrrmc_ctx** out, int64_t Nk, int64_t M,
     ctx->re_htab.assign((size_t)ntab_h, 0.0);
     ctx->le_hcode.assign((size_t)(8 * ncode_d), 0xFF);
     ctx->re_hft.assign((size_t)L, 0.0);
-#define ENS_TRY(expr)                                                                                            \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            int32_t rc_ = fail(nullptr, RRRMC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));           \
-            rrrmc_ctx_destroy(ctx);                                                                              \
-            return rc_;                                                                                          \
-        }                                                                                                        \
-    } while (0)
-    ENS_TRY(hipSetDevice(device));
-    ENS_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    ENS_TRY(hipEventCreate(&ctx->ev_begin));
-    ENS_TRY(hipEventCreate(&ctx->ev_end));
     if (slice_kind == RRRMC_RE_SLICE_SKN) {
-        ENS_TRY(hipMalloc(&ctx->sk_J, sizeof(double) * Nk * Nk));
-        ENS_TRY(hipMalloc(&ctx->q_slf, sizeof(double) * (size_t)R * 2 * (size_t)rows * (size_t)Nk));
-        ENS_TRY(hipMalloc(&ctx->q_smv, sizeof(int32_t) * (size_t)R * (size_t)rows));
-        ENS_TRY(hipMalloc(&ctx->q_scur, (size_t)R * (size_t)rows));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_J, Nk * Nk));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_slf, (size_t)R * 2 * (size_t)rows * (size_t)Nk));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_smv, (size_t)R * (size_t)rows));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_scur, (size_t)R * (size_t)rows));
     } else if (slice_kind == RRRMC_RE_SLICE_SK) {
-        ENS_TRY(hipMalloc(&ctx->q_Jb, sizeof(uint32_t) * Nk * ctx->q_Wk));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_Jb, Nk * ctx->q_Wk));
     }
-    ENS_TRY(hipMalloc(&ctx->re_tab, sizeof(double) * (size_t)ntab_d));
-    ENS_TRY(hipMalloc(&ctx->q_spins, sizeof(uint32_t) * R * ctx->qW));
-    ENS_TRY(hipMalloc(&ctx->re_sp, sizeof(uint32_t) * R * ctx->qW));
-    ENS_TRY(hipMalloc(&ctx->re_mu, (size_t)R * Nk));
-    ENS_TRY(hipMalloc(&ctx->q_cls, (size_t)R * N));
-    ENS_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->q_sv), sizeof(uint16_t) * (size_t)R * 2 * L * N));
-    ENS_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->q_spos), sizeof(uint16_t) * (size_t)R * N));
-    ENS_TRY(hipMalloc(&ctx->q_st, sizeof(int32_t) * R * 2 * L));
-    ENS_TRY(hipMalloc(&ctx->q_T, sizeof(double) * R * 2 * L));
-    ENS_TRY(hipMalloc(&ctx->q_z, sizeof(double) * R));
-    ENS_TRY(hipMalloc(&ctx->q_accrate, sizeof(double) * R));
-    ENS_TRY(hipMalloc(&ctx->q_stats, sizeof(int64_t) * R * 2));
-    ENS_TRY(hipMalloc(&ctx->sk_E, sizeof(double) * R));
-    ENS_TRY(hipMalloc(&ctx->re_Eslice, sizeof(double) * R * rows));
-    if (!re) ENS_TRY(hipMalloc(&ctx->le_dist, sizeof(int64_t) * R * M * M));
-    ENS_TRY(hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
-#undef ENS_TRY
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->re_tab, (size_t)ntab_d));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_spins, R * ctx->qW));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->re_sp, R * ctx->qW));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->re_mu, (size_t)R * Nk));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_cls, (size_t)R * N));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_sv, (size_t)R * 2 * L * N));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_spos, (size_t)R * N));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_st, R * 2 * L));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_T, R * 2 * L));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_z, R));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_accrate, R));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_stats, R * 2));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_E, R));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->re_Eslice, R * rows));
+    if (!re) CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->le_dist, R * M * M));
+    CTX_CREATE_TRY(ctx, false, hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
     *out = ctx;
     return RRRMC_OK;
 }

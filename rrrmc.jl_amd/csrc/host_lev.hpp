@@ -9,38 +9,20 @@ int32_t lev_ctx_create(rrrmc_ctx** out, int64_t N, int64_t K, int64_t R, int32_t
     if (N < 1 || K < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "N, K, R must be >= 1 (given N=%lld K=%lld R=%lld)", (long long)N, (long long)K, (long long)R);
     if (K > 16) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "K=%lld: the general-level kernels cover K <= 16", (long long)K);
     if (N > (int64_t)1 << 28) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N=%lld is beyond the thread-per-replica kernels (N <= 2^28)", (long long)N);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, RRRMC_ERR_HIP, "no HIP device is visible: this library has no CPU path");
-    if (device < 0 || device >= ndev) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-    rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
-    if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
+    rrrmc_ctx* ctx = nullptr;
+    { const int32_t rcb = ctx_create_begin(&ctx, device, true); if (rcb) return rcb; }
     ctx->model = RRRMC_MODEL_SPARSE_LEVELS; ctx->N = N; ctx->K = K; ctx->R = R;
     ctx->G = (R + 31) / 32; ctx->Rpad = 32 * ctx->G;
     ctx->qW = 2 * ((N + 63) / 64);
-    ctx->device = device; ctx->replica0 = replica0;
-#define LV_TRY(expr)                                                                                             \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            int32_t rc_ = fail(nullptr, e_ == hipErrorOutOfMemory ? RRRMC_ERR_NOMEM : RRRMC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            rrrmc_ctx_destroy(ctx);                                                                              \
-            return rc_;                                                                                          \
-        }                                                                                                        \
-    } while (0)
-    LV_TRY(hipSetDevice(device));
-    LV_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    LV_TRY(hipEventCreate(&ctx->ev_begin));
-    LV_TRY(hipEventCreate(&ctx->ev_end));
-    LV_TRY(hipMalloc(&ctx->d_A, sizeof(int32_t) * N * K));
-    LV_TRY(hipMalloc(&ctx->d_J, sizeof(int8_t) * N * K));
-    LV_TRY(hipMalloc(&ctx->q_spins, sizeof(uint32_t) * R * ctx->qW));
-    LV_TRY(hipMalloc(&ctx->d_E, sizeof(int32_t) * ctx->Rpad));
-    LV_TRY(hipMalloc(&ctx->d_acc, sizeof(int64_t) * ctx->Rpad));
-    LV_TRY(hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
-    LV_TRY(hipMemset(ctx->d_E, 0, sizeof(int32_t) * ctx->Rpad));
-    LV_TRY(hipMemset(ctx->d_acc, 0, sizeof(int64_t) * ctx->Rpad));
-#undef LV_TRY
+    ctx->replica0 = replica0;
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->d_A, N * K));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->d_J, N * K));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->q_spins, R * ctx->qW));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->d_E, ctx->Rpad));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->d_acc, ctx->Rpad));
+    CTX_CREATE_TRY(ctx, true, hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
+    CTX_CREATE_TRY(ctx, true, hipMemset(ctx->d_E, 0, sizeof(int32_t) * ctx->Rpad));
+    CTX_CREATE_TRY(ctx, true, hipMemset(ctx->d_acc, 0, sizeof(int64_t) * ctx->Rpad));
     *out = ctx;
     return RRRMC_OK;
 }
@@ -57,12 +39,7 @@ int32_t lev_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_
         ctx->results_valid = false; ctx->last_call_wtm = false; ctx->last_call_eo = false;
         ctx->timing_valid = false;
         const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->Rpad;
-        if (es_need > ctx->Es_cap) {
-            free_dev(ctx->d_Es);
-            ctx->Es_cap = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->d_Es, sizeof(int32_t) * es_need));
-            ctx->Es_cap = es_need;
-        }
+        HIP_TRY(ctx, dev_grow(ctx, ctx->d_Es, ctx->Es_cap, es_need));
         while (ctx->ev_sweep.size() < 2) {
             hipEvent_t e;
             HIP_TRY(ctx, hipEventCreate(&e));

@@ -41,13 +41,13 @@ int32_t perc_set_patterns(rrrmc_ctx* ctx, const uint64_t* xi, int64_t P, int64_t
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (P != ctx->pc_P) {
-        free_dev(ctx->pc_col); free_dev(ctx->pc_row); free_dev(ctx->pc_ds); free_dev(ctx->pc_pm); free_dev(ctx->pc_mm);
+        dev_free(ctx, ctx->pc_col); dev_free(ctx, ctx->pc_row); dev_free(ctx, ctx->pc_ds); dev_free(ctx, ctx->pc_pm); dev_free(ctx, ctx->pc_mm);
         ctx->pc_P = 0; ctx->graph_set = false;
-        HIP_TRY(ctx, hipMalloc(&ctx->pc_col, sizeof(uint64_t) * (size_t)(N * PW)));
-        HIP_TRY(ctx, hipMalloc(&ctx->pc_row, sizeof(uint64_t) * (size_t)(P * nch)));
-        HIP_TRY(ctx, hipMalloc(&ctx->pc_ds, sizeof(int16_t) * (size_t)(ctx->R * rows * 64 * PW)));
-        HIP_TRY(ctx, hipMalloc(&ctx->pc_pm, sizeof(uint64_t) * (size_t)(ctx->R * rows * PW)));
-        HIP_TRY(ctx, hipMalloc(&ctx->pc_mm, sizeof(uint64_t) * (size_t)(ctx->R * rows * PW)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->pc_col, (size_t)(N * PW)));
+        HIP_TRY(ctx, dev_alloc_bytes(ctx, ctx->pc_row, sizeof(uint64_t) * (size_t)(P * nch)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->pc_ds, (size_t)(ctx->R * rows * 64 * PW)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->pc_pm, (size_t)(ctx->R * rows * PW)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->pc_mm, (size_t)(ctx->R * rows * PW)));
         ctx->pc_P = P;
     }
     HIP_TRY(ctx, hipMemcpy(ctx->pc_col, col.data(), sizeof(uint64_t) * col.size(), hipMemcpyHostToDevice));
@@ -90,12 +90,7 @@ int32_t perc_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step)
     ctx->timing_valid = false;
     const int64_t nsamp = iters / step;
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->R;
-    if (es_need > ctx->sk_Es_cap) {
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->sk_Es, ctx->sk_Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -115,7 +110,7 @@ int32_t perc_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step)
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_sweep[1], st));
     if (ctx->debug_checks) {
-        if (!ctx->dbg_flag) { HIP_TRY(ctx, hipMalloc(&ctx->dbg_flag, sizeof(int32_t) * 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, st)); }
+        if (!ctx->dbg_flag) { HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_flag, 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, st)); }
         P.flag = ctx->dbg_flag;
         const dim3 grid((unsigned)((ctx->R + 63) / 64)), blk(64);
         if (lin) hipLaunchKernelGGL(perc_check_kernel<true>, grid, blk, 0, st, P);
@@ -140,34 +135,16 @@ int32_t perc_ctx_create(rrrmc_ctx** out, int64_t N, int32_t linear, int64_t R, i
     if (N < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "N and R must be >= 1");
     { const int32_t rcn = perc_check_n(N); if (rcn) return rcn; }
     if (replica0 % 32) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "replica0 must be a multiple of 32 (given %u)", replica0);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, RRRMC_ERR_HIP, "no HIP device is visible: this library has no CPU path");
-    if (device < 0 || device >= ndev) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-    rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
-    if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
+    rrrmc_ctx* ctx = nullptr;
+    { const int32_t rcb = ctx_create_begin(&ctx, device, false); if (rcb) return rcb; }
     ctx->model = linear ? RRRMC_MODEL_PERC_LINEAR : RRRMC_MODEL_PERC_STEP;
     ctx->N = N; ctx->K = 0; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = N; ctx->qM = 1; ctx->qW = 2 * ((N + 63) / 64);
-    ctx->device = device; ctx->replica0 = replica0;
-#define PERC_TRY(expr)                                                                                           \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            int32_t rc_ = fail(nullptr, RRRMC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));           \
-            rrrmc_ctx_destroy(ctx);                                                                              \
-            return rc_;                                                                                          \
-        }                                                                                                        \
-    } while (0)
-    PERC_TRY(hipSetDevice(device));
-    PERC_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    PERC_TRY(hipEventCreate(&ctx->ev_begin));
-    PERC_TRY(hipEventCreate(&ctx->ev_end));
-    PERC_TRY(hipMalloc(&ctx->q_spins, sizeof(uint32_t) * R * ctx->qW));
-    PERC_TRY(hipMalloc(&ctx->q_stats, sizeof(int64_t) * R * 2));
-    PERC_TRY(hipMalloc(&ctx->sk_E, sizeof(double) * R));
-    PERC_TRY(hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
-#undef PERC_TRY
+    ctx->replica0 = replica0;
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_spins, R * ctx->qW));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_stats, R * 2));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_E, R));
+    CTX_CREATE_TRY(ctx, false, hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
     *out = ctx;
     return RRRMC_OK;
 }

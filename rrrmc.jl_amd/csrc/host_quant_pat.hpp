@@ -93,7 +93,7 @@ int32_t quant_pat_launch(rrrmc_ctx* ctx, bool standard, const RrrParams& P)
 // debug mode: Stabilities, masks and E recomputed after the call (reported by the next sync, post_sync_checks)
 int32_t quant_pat_check(rrrmc_ctx* ctx, const RrrParams& P)
 {
-    if (!ctx->dbg_flag) { HIP_TRY(ctx, hipMalloc(&ctx->dbg_flag, sizeof(int32_t) * 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, ctx->stream)); }
+    if (!ctx->dbg_flag) { HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_flag, 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, ctx->stream)); }
     const QuantPatParams Q = quant_pat_params(ctx);
     QUANT_PAT_LAUNCH(ctx, quant_pat_check_kernel, dim3((unsigned)((ctx->R + 63) / 64)), dim3(64), 0, P, Q);
     return RRRMC_OK;
@@ -102,7 +102,7 @@ int32_t quant_pat_check(rrrmc_ctx* ctx, const RrrParams& P)
 // energy(X1[k], C1[k]) of every slice of the live configuration into re_Eslice [R][M] (queued on the context's stream)
 int32_t quant_pat_energies(rrrmc_ctx* ctx)
 {
-    if (!ctx->re_Eslice) HIP_TRY(ctx, hipMalloc(&ctx->re_Eslice, sizeof(double) * (size_t)(ctx->R * ctx->qM)));
+    if (!ctx->re_Eslice) HIP_TRY(ctx, dev_alloc(ctx, ctx->re_Eslice, (size_t)(ctx->R * ctx->qM)));
     const QuantPatParams Q = quant_pat_params(ctx);
     QUANT_PAT_LAUNCH(ctx, quant_pat_energies_kernel, dim3((unsigned)((ctx->R * ctx->qM + 63) / 64)), dim3(64), 0, Q, ctx->q_spins, (int)ctx->qNk, (int)ctx->qM, (int)ctx->qW, (int)ctx->R);
     return RRRMC_OK;

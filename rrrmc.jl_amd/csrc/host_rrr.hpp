@@ -1,6 +1,6 @@
 // Host side of the reduced-rejection samplers: GraphQuant, rrrMC on GraphSKNormal, rrrMC / bklMC on GraphRRG / GraphEA.
 // Included by rrrmc_hip.hip inside its anonymous namespace, after the context struct and the common helpers
-// (fail, HIP_TRY, free_dev, ensure_state); not a stand-alone translation unit.
+// (fail, HIP_TRY, dev_alloc / dev_free, ensure_state); not a stand-alone translation unit.
 // ---- GraphQuant / rrrMC host side -----------------------------------------------------------------------------------
 RrrParams quant_params(rrrmc_ctx* ctx, double beta, double fourK)
 {
@@ -97,16 +97,16 @@ int32_t sk_rrr_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step
     const size_t per = (size_t)Rp;
     const size_t ndbl = per * (size_t)(5 * N + 2 * N2 + 1);
     if (!ctx->rs_buf) {
-        HIP_TRY(ctx, hipMalloc(&ctx->rs_buf, sizeof(double) * ndbl));
-        HIP_TRY(ctx, hipMalloc(&ctx->rs_spins, sizeof(uint32_t) * W * per));
-        HIP_TRY(ctx, hipMalloc(&ctx->rs_status, sizeof(int32_t) * per));
-        HIP_TRY(ctx, hipMalloc(&ctx->q_stats, sizeof(int64_t) * per * 2));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->rs_buf, ndbl));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->rs_spins, W * per));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->rs_status, per));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->q_stats, per * 2));
     }
-    if ((mode == 2 || mode == 3) && !ctx->wt_time) HIP_TRY(ctx, hipMalloc(&ctx->wt_time, sizeof(double) * per));
+    if ((mode == 2 || mode == 3) && !ctx->wt_time) HIP_TRY(ctx, dev_alloc(ctx, ctx->wt_time, per));
     if (mode == 3) {
         if (!ctx->eo_cmin) {
-            HIP_TRY(ctx, hipMalloc(&ctx->eo_cmin, sizeof(uint32_t) * ctx->R * W));
-            HIP_TRY(ctx, hipMalloc(&ctx->eo_ftau, sizeof(double) * N));
+            HIP_TRY(ctx, dev_alloc(ctx, ctx->eo_cmin, ctx->R * W));
+            HIP_TRY(ctx, dev_alloc(ctx, ctx->eo_ftau, N));
         }
         ctx->eo_W = W;
         if (!S.resume) {                    // (a resumed call: the run's table is on the device already)
@@ -116,12 +116,7 @@ int32_t sk_rrr_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step
     }
     const int64_t nsamp = mode == 2 ? iters : smp_nsamp(ctx, iters, step);
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * Rp;
-    if (es_need > ctx->sk_Es_cap) {
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->sk_Es, ctx->sk_Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -133,7 +128,7 @@ int32_t sk_rrr_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step
     // the division by sN = sqrt(N) applied where the reference applies it (SK.jl:95,139).
     const bool bin = ctx->model == RRRMC_MODEL_SK_BINARY;
     if (bin) {
-        if (!ctx->sk_J) HIP_TRY(ctx, hipMalloc(&ctx->sk_J, sizeof(double) * N * N));
+        if (!ctx->sk_J) HIP_TRY(ctx, dev_alloc(ctx, ctx->sk_J, N * N));
         hipLaunchKernelGGL(skb_dense_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)N), dim3(256), 0, st, ctx->skb_J, ctx->sk_J, (int)N, (int)ctx->skb_NW);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -196,7 +191,7 @@ int32_t rp_prepare(rrrmc_ctx* ctx, RpView* v)
 {
     if (ctx->model == RRRMC_MODEL_SPARSE_LEVELS) { v->spins = ctx->q_spins; v->W = ctx->qW; v->convert = false; return RRRMC_OK; }
     v->W = (ctx->N + 31) / 32;
-    if (!ctx->rp_spins) HIP_TRY(ctx, hipMalloc(&ctx->rp_spins, sizeof(uint32_t) * ctx->R * v->W));
+    if (!ctx->rp_spins) HIP_TRY(ctx, dev_alloc(ctx, ctx->rp_spins, ctx->R * v->W));
     v->spins = ctx->rp_spins; v->convert = true;
     return RRRMC_OK;
 }
@@ -236,20 +231,15 @@ int32_t sparse_rrr_bkl_async(rrrmc_ctx* ctx, int mode, double beta, int64_t iter
     if (rc) return rc;
     const int64_t W = rv.W;
     if (!ctx->rp_cls) {
-        HIP_TRY(ctx, hipMalloc(&ctx->rp_cls, (size_t)R * N));
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->rp_sv), idx_bytes * R * 2 * L * N));
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->rp_spos), idx_bytes * R * N));
-        if (!ctx->q_stats) HIP_TRY(ctx, hipMalloc(&ctx->q_stats, sizeof(int64_t) * R * 3));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->rp_cls, (size_t)R * N));
+        HIP_TRY(ctx, dev_alloc_bytes(ctx, ctx->rp_sv, idx_bytes * R * 2 * L * N));
+        HIP_TRY(ctx, dev_alloc_bytes(ctx, ctx->rp_spos, idx_bytes * R * N));
+        if (!ctx->q_stats) HIP_TRY(ctx, dev_alloc(ctx, ctx->q_stats, R * 3));
     }
     ctx->stats_stride = 3;
     const int64_t nsamp = smp_nsamp(ctx, iters, step);
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->Rpad;
-    if (es_need > ctx->Es_cap) {
-        free_dev(ctx->d_Es);
-        ctx->Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_Es, sizeof(int32_t) * es_need));
-        ctx->Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->d_Es, ctx->Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -350,19 +340,14 @@ int32_t sparse_wtm_async(rrrmc_ctx* ctx, double beta, int64_t samples, double st
     if (rc) return rc;
     const int64_t W = rv.W;
     if (!ctx->wt_t) {
-        HIP_TRY(ctx, hipMalloc(&ctx->wt_t, sizeof(double) * R * N));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->wt_t, R * N));
         const size_t idx_bytes = N > 65535 ? sizeof(uint32_t) : sizeof(uint16_t);
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->wt_id), idx_bytes * R * N));
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->wt_pos), idx_bytes * R * N));
-        HIP_TRY(ctx, hipMalloc(&ctx->wt_time, sizeof(double) * R));
+        HIP_TRY(ctx, dev_alloc_bytes(ctx, ctx->wt_id, idx_bytes * R * N));
+        HIP_TRY(ctx, dev_alloc_bytes(ctx, ctx->wt_pos, idx_bytes * R * N));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->wt_time, R));
     }
     const size_t es_need = (size_t)(samples > 0 ? samples : 1) * ctx->Rpad;
-    if (es_need > ctx->Es_cap) {
-        free_dev(ctx->d_Es);
-        ctx->Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_Es, sizeof(int32_t) * es_need));
-        ctx->Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->d_Es, ctx->Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -426,25 +411,20 @@ int32_t sparse_eo_async(rrrmc_ctx* ctx, const double* ftau, int64_t iters, int64
     const int64_t W = rv.W;
     ctx->eo_W = W;
     if (!ctx->rp_cls) {
-        HIP_TRY(ctx, hipMalloc(&ctx->rp_cls, (size_t)R * N));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->rp_cls, (size_t)R * N));
         const size_t idx_bytes = N > 65535 ? sizeof(uint32_t) : sizeof(uint16_t);
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->rp_sv), idx_bytes * R * 2 * L * N));
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->rp_spos), idx_bytes * R * N));
-        if (!ctx->q_stats) HIP_TRY(ctx, hipMalloc(&ctx->q_stats, sizeof(int64_t) * R * 3));
+        HIP_TRY(ctx, dev_alloc_bytes(ctx, ctx->rp_sv, idx_bytes * R * 2 * L * N));
+        HIP_TRY(ctx, dev_alloc_bytes(ctx, ctx->rp_spos, idx_bytes * R * N));
+        if (!ctx->q_stats) HIP_TRY(ctx, dev_alloc(ctx, ctx->q_stats, R * 3));
     }
     if (!ctx->eo_cmin) {
-        HIP_TRY(ctx, hipMalloc(&ctx->eo_cmin, sizeof(uint32_t) * R * 2 * ((N + 63) / 64)));
-        HIP_TRY(ctx, hipMalloc(&ctx->eo_ftau, sizeof(double) * N));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->eo_cmin, R * 2 * ((N + 63) / 64)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->eo_ftau, N));
     }
     ctx->stats_stride = 3;
     const int64_t nsamp = smp_nsamp(ctx, iters, step);
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->Rpad;
-    if (es_need > ctx->Es_cap) {
-        free_dev(ctx->d_Es);
-        ctx->Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_Es, sizeof(int32_t) * es_need));
-        ctx->Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->d_Es, ctx->Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));

@@ -85,10 +85,10 @@ int32_t sat_set_clauses(rrrmc_ctx* ctx, int64_t Mc, int64_t Kmax, const int32_t*
     if (rcb) return fail(ctx, rcb == 3 ? RRRMC_ERR_UNSUPPORTED : RRRMC_ERR_INVALID_ARG, "%s", msg);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    free_dev(ctx->sat_off); free_dev(ctx->sat_ent);
+    dev_free(ctx, ctx->sat_off); dev_free(ctx, ctx->sat_ent);
     ctx->graph_set = false;
-    HIP_TRY(ctx, hipMalloc(&ctx->sat_off, sizeof(uint32_t) * off.size()));
-    HIP_TRY(ctx, hipMalloc(&ctx->sat_ent, sizeof(SatEntry) * (ent.empty() ? 1 : ent.size())));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->sat_off, off.size()));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->sat_ent, (ent.empty() ? 1 : ent.size())));
     HIP_TRY(ctx, hipMemcpy(ctx->sat_off, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice));
     if (!ent.empty()) HIP_TRY(ctx, hipMemcpy(ctx->sat_ent, ent.data(), sizeof(SatEntry) * ent.size(), hipMemcpyHostToDevice));
     ctx->sat_Mc = Mc; ctx->sat_maxconn = mc;
@@ -142,19 +142,14 @@ int32_t sat_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step)
     ctx->timing_valid = false;
     const int64_t nsamp = iters / step;
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->R;
-    if (es_need > ctx->sk_Es_cap) {
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->sk_Es, ctx->sk_Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
         ctx->ev_sweep.push_back(e);
     }
     const bool wave = sat_use_wave(ctx->R);
-    if (!wave && !ctx->sat_spT) HIP_TRY(ctx, hipMalloc(&ctx->sat_spT, sizeof(uint32_t) * (size_t)ctx->R * (size_t)ctx->qW));
+    if (!wave && !ctx->sat_spT) HIP_TRY(ctx, dev_alloc(ctx, ctx->sat_spT, (size_t)ctx->R * (size_t)ctx->qW));
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_begin, st));
     ctx->stats_stride = 2;
@@ -172,7 +167,7 @@ int32_t sat_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step)
     if (!wave) { hipLaunchKernelGGL(sat_transpose_kernel, dim3(tgrid), dim3(256), 0, st, P, 1); HIP_TRY(ctx, hipGetLastError()); }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_sweep[1], st));
     if (ctx->debug_checks) {
-        if (!ctx->dbg_flag) { HIP_TRY(ctx, hipMalloc(&ctx->dbg_flag, sizeof(int32_t) * 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, st)); }
+        if (!ctx->dbg_flag) { HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_flag, 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, st)); }
         P.flag = ctx->dbg_flag;
         hipLaunchKernelGGL(sat_check_kernel, dim3((unsigned)((ctx->R + 63) / 64)), dim3(64), 0, st, P);
         HIP_TRY(ctx, hipGetLastError());
@@ -196,34 +191,16 @@ int32_t sat_ctx_create(rrrmc_ctx** out, int64_t N, int64_t R, int32_t device, ui
     if (N < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "N and R must be >= 1");
     if (N > kSatNmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N = %lld: the K-SAT kernels cover N <= %d (16-bit variable ids)", (long long)N, kSatNmax);
     if (replica0 % 32) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "replica0 must be a multiple of 32 (given %u)", replica0);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, RRRMC_ERR_HIP, "no HIP device is visible: this library has no CPU path");
-    if (device < 0 || device >= ndev) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-    rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
-    if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
+    rrrmc_ctx* ctx = nullptr;
+    { const int32_t rcb = ctx_create_begin(&ctx, device, false); if (rcb) return rcb; }
     ctx->model = RRRMC_MODEL_SAT;
     ctx->N = N; ctx->K = 0; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = N; ctx->qM = 1; ctx->qW = 2 * ((N + 63) / 64);
-    ctx->device = device; ctx->replica0 = replica0;
-#define SAT_TRY(expr)                                                                                            \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            int32_t rc_ = fail(nullptr, RRRMC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));           \
-            rrrmc_ctx_destroy(ctx);                                                                              \
-            return rc_;                                                                                          \
-        }                                                                                                        \
-    } while (0)
-    SAT_TRY(hipSetDevice(device));
-    SAT_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    SAT_TRY(hipEventCreate(&ctx->ev_begin));
-    SAT_TRY(hipEventCreate(&ctx->ev_end));
-    SAT_TRY(hipMalloc(&ctx->q_spins, sizeof(uint32_t) * R * ctx->qW));
-    SAT_TRY(hipMalloc(&ctx->q_stats, sizeof(int64_t) * R * 2));
-    SAT_TRY(hipMalloc(&ctx->sk_E, sizeof(double) * R));
-    SAT_TRY(hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
-#undef SAT_TRY
+    ctx->replica0 = replica0;
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_spins, R * ctx->qW));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_stats, R * 2));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_E, R));
+    CTX_CREATE_TRY(ctx, false, hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
     *out = ctx;
     return RRRMC_OK;
 }

@@ -1,6 +1,6 @@
 // Host side of the dense SK models (GraphSKNormal, GraphSK): context creation, energy, standardMC orchestration.
 // Included by rrrmc_hip.hip inside its anonymous namespace, after the context struct and the common helpers
-// (fail, HIP_TRY, free_dev, ensure_state); not a stand-alone translation unit.
+// (fail, HIP_TRY, dev_alloc / dev_free, ensure_state); not a stand-alone translation unit.
 // ---- GraphSKNormal (dense Float64) host side -----------------------------------------------------------------------
 typedef void (*sk_fn)(SkParams);
 sk_fn sk_sweep_for(int spt, int nth)
@@ -125,50 +125,32 @@ int32_t sk_ctx_create(rrrmc_ctx** out, int32_t model, int64_t N, int64_t R, int3
     if (N < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "N, R must be >= 1 (given N=%lld R=%lld)", (long long)N, (long long)R);
     if (N > kSkMaxN) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N=%lld: the register-resident SK kernels cover N <= %d", (long long)N, kSkMaxN);
     if (replica0 % 32) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "replica0 must be a multiple of 32 (given %u)", replica0);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, RRRMC_ERR_HIP, "no HIP device is visible: this library has no CPU path");
-    if (device < 0 || device >= ndev) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-    rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
-    if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
+    rrrmc_ctx* ctx = nullptr;
+    { const int32_t rcb = ctx_create_begin(&ctx, device, false); if (rcb) return rcb; }
     ctx->model = model; ctx->N = N; ctx->K = 0; ctx->R = R;
     ctx->G8 = (R + kSkRB - 1) / kSkRB; ctx->Rpad = ctx->G8 * kSkRB; ctx->G = 0;
-    ctx->device = device; ctx->replica0 = replica0;
-#define SK_TRY(expr)                                                                                             \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            int32_t rc_ = fail(nullptr, RRRMC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));           \
-            rrrmc_ctx_destroy(ctx);                                                                              \
-            return rc_;                                                                                          \
-        }                                                                                                        \
-    } while (0)
-    SK_TRY(hipSetDevice(device));
-    SK_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    SK_TRY(hipEventCreate(&ctx->ev_begin));
-    SK_TRY(hipEventCreate(&ctx->ev_end));
+    ctx->replica0 = replica0;
     const size_t nf = (size_t)ctx->G8 * N * kSkRB;
     if (model == RRRMC_MODEL_SK_BINARY) {
         ctx->skb_NW = (int)(2 * ((N + 63) / 64));
-        SK_TRY(hipMalloc(&ctx->skb_J, sizeof(uint32_t) * N * ctx->skb_NW));
-        SK_TRY(hipMalloc(&ctx->skb_lf, sizeof(int32_t) * nf));
-        SK_TRY(hipMalloc(&ctx->skb_lfl, sizeof(int32_t) * nf));
-        SK_TRY(hipMemset(ctx->skb_lf, 0, sizeof(int32_t) * nf));
-        SK_TRY(hipMemset(ctx->skb_lfl, 0, sizeof(int32_t) * nf));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->skb_J, N * ctx->skb_NW));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->skb_lf, nf));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->skb_lfl, nf));
+        CTX_CREATE_TRY(ctx, false, hipMemset(ctx->skb_lf, 0, sizeof(int32_t) * nf));
+        CTX_CREATE_TRY(ctx, false, hipMemset(ctx->skb_lfl, 0, sizeof(int32_t) * nf));
     } else {
-        SK_TRY(hipMalloc(&ctx->sk_J, sizeof(double) * N * N));
-        SK_TRY(hipMalloc(&ctx->sk_J4, sizeof(double) * N * sk_ldJ(N)));
-        SK_TRY(hipMalloc(&ctx->sk_lf, sizeof(double) * nf));
-        SK_TRY(hipMalloc(&ctx->sk_lfl, sizeof(double) * nf));
-        SK_TRY(hipMemset(ctx->sk_lf, 0, sizeof(double) * nf));
-        SK_TRY(hipMemset(ctx->sk_lfl, 0, sizeof(double) * nf));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_J, N * N));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_J4, N * sk_ldJ(N)));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_lf, nf));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_lfl, nf));
+        CTX_CREATE_TRY(ctx, false, hipMemset(ctx->sk_lf, 0, sizeof(double) * nf));
+        CTX_CREATE_TRY(ctx, false, hipMemset(ctx->sk_lfl, 0, sizeof(double) * nf));
     }
-    SK_TRY(hipMalloc(&ctx->sk_move_last, sizeof(int32_t) * ctx->Rpad));
-    SK_TRY(hipMalloc(&ctx->sk_spins, ((size_t)ctx->G8 * N + 3) / 4 * 4));       // (whole words: sk_block_kernel<.., 4> updates its bits by word atomics)
-    SK_TRY(hipMalloc(&ctx->sk_E, sizeof(double) * ctx->Rpad));
-    SK_TRY(hipMalloc(&ctx->d_acc, sizeof(int64_t) * ctx->Rpad));
-    SK_TRY(hipMemset(ctx->sk_spins, 0, (size_t)ctx->G8 * N));
-#undef SK_TRY
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_move_last, ctx->Rpad));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_spins, ((size_t)ctx->G8 * N + 3) / 4 * 4));       // (whole words: sk_block_kernel<.., 4> updates its bits by word atomics)
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_E, ctx->Rpad));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_acc, ctx->Rpad));
+    CTX_CREATE_TRY(ctx, false, hipMemset(ctx->sk_spins, 0, (size_t)ctx->G8 * N));
     *out = ctx;
     return RRRMC_OK;
 }
@@ -202,12 +184,12 @@ int32_t sk_run_energy(rrrmc_ctx* ctx)
 int32_t sk_debug_check(rrrmc_ctx* ctx)
 {
     const size_t nf = (size_t)ctx->G8 * ctx->N * kSkRB;
-    if (!ctx->dbg_flag) { HIP_TRY(ctx, hipMalloc(&ctx->dbg_flag, sizeof(int32_t) * 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, ctx->stream)); }
+    if (!ctx->dbg_flag) { HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_flag, 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, ctx->stream)); }
     if (!ctx->dbg_lf) {
-        HIP_TRY(ctx, hipMalloc(&ctx->dbg_lf, sizeof(double) * nf));
-        HIP_TRY(ctx, hipMalloc(&ctx->dbg_lfl, sizeof(double) * nf));
-        HIP_TRY(ctx, hipMalloc(&ctx->dbg_E, sizeof(double) * ctx->Rpad));
-        HIP_TRY(ctx, hipMalloc(&ctx->dbg_ml, sizeof(int32_t) * ctx->Rpad));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_lf, nf));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_lfl, nf));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_E, ctx->Rpad));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_ml, ctx->Rpad));
     }
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(sk_fields_kernel, dim3((unsigned)((ctx->N + 31) / 32), (unsigned)ctx->G8), dim3(256), 0, st, ctx->sk_J, ctx->sk_spins,
@@ -237,12 +219,7 @@ int32_t sk_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t
     ctx->last_call_rrr = false;
     const int64_t nsamp = iters / step;
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->Rpad;
-    if (es_need > ctx->sk_Es_cap) {
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->sk_Es, ctx->sk_Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -302,8 +279,8 @@ int32_t sk_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t
         // once, the integer fields travel int32 -> Float64 -> int32 around the call (exact)
         const size_t nf = (size_t)ctx->G8 * ctx->N * kSkRB;
         const int64_t ld = sk_ldJ(ctx->N);
-        if (!ctx->sk_lf) { HIP_TRY(ctx, hipMalloc(&ctx->sk_lf, sizeof(double) * nf)); HIP_TRY(ctx, hipMalloc(&ctx->sk_lfl, sizeof(double) * nf)); }
-        if (!ctx->sk_J4) HIP_TRY(ctx, hipMalloc(&ctx->sk_J4, sizeof(double) * ctx->N * ld));
+        if (!ctx->sk_lf) { HIP_TRY(ctx, dev_alloc(ctx, ctx->sk_lf, nf)); HIP_TRY(ctx, dev_alloc(ctx, ctx->sk_lfl, nf)); }
+        if (!ctx->sk_J4) HIP_TRY(ctx, dev_alloc(ctx, ctx->sk_J4, ctx->N * ld));
         if (!ctx->skb_J4_valid) {
             hipLaunchKernelGGL(skb_dense4_kernel, dim3((unsigned)((ld + 255) / 256), (unsigned)ctx->N), dim3(256), 0, st, ctx->skb_J, ctx->sk_J4, (int)ctx->N,
                                ctx->skb_NW, (int)ld);
@@ -341,10 +318,10 @@ int32_t sk_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t
         const int64_t nseg = (iters + kSkSegIters - 1) / kSkSegIters;
         const int64_t cap_blk = ((iters < kSkSegIters ? iters : kSkSegIters) + kSkW - 1) / kSkW;
         if ((size_t)cap_blk > ctx->sk_blk_cap) {
-            free_dev(ctx->sk_blkJw); free_dev(ctx->sk_blkSites);
+            dev_free(ctx, ctx->sk_blkJw); dev_free(ctx, ctx->sk_blkSites);
             ctx->sk_blk_cap = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->sk_blkJw, sizeof(double) * (size_t)cap_blk * kSkW * kSkW));
-            HIP_TRY(ctx, hipMalloc(&ctx->sk_blkSites, sizeof(uint32_t) * (size_t)(cap_blk + 1) * kSkW));
+            HIP_TRY(ctx, dev_alloc(ctx, ctx->sk_blkJw, (size_t)cap_blk * kSkW * kSkW));
+            HIP_TRY(ctx, dev_alloc(ctx, ctx->sk_blkSites, (size_t)(cap_blk + 1) * kSkW));
             ctx->sk_blk_cap = (size_t)cap_blk;
         }
         while ((int64_t)ctx->ev_sweep.size() < 2 * nseg) {
@@ -352,7 +329,7 @@ int32_t sk_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t
             HIP_TRY(ctx, hipEventCreate(&e));
             ctx->ev_sweep.push_back(e);
         }
-        if (!v1 && !ctx->sk_hl) HIP_TRY(ctx, hipMalloc(&ctx->sk_hl, sizeof(double) * (size_t)ctx->Rpad * (size_t)ctx->N));
+        if (!v1 && !ctx->sk_hl) HIP_TRY(ctx, dev_alloc(ctx, ctx->sk_hl, (size_t)ctx->Rpad * (size_t)ctx->N));
         SkBlockParams Bk{};
         Bk.hl = ctx->sk_hl;
         Bk.J4 = ctx->sk_J4; Bk.blkJw = ctx->sk_blkJw; Bk.blkSites = ctx->sk_blkSites;

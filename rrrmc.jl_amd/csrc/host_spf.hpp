@@ -1,6 +1,6 @@
 // Host side of the Float64-coupling sparse models (GraphRRGNormal / GraphEANormal).
 // Included by rrrmc_hip.hip inside its anonymous namespace, after the context struct and the common helpers
-// (fail, HIP_TRY, free_dev, ensure_state); not a stand-alone translation unit.
+// (fail, HIP_TRY, dev_alloc / dev_free, ensure_state); not a stand-alone translation unit.
 // ---- Float64-coupling sparse models (GraphRRGNormal / GraphEANormal) host side ------------------------------------
 constexpr int64_t kSpfItersPerLaunch = 1 << 20;
 
@@ -9,43 +9,25 @@ int32_t spf_ctx_create(rrrmc_ctx** out, int64_t N, int64_t K, int64_t R, int32_t
     if (N < 1 || K < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "N, K, R must be >= 1 (given N=%lld K=%lld R=%lld)", (long long)N, (long long)K, (long long)R);
     if (K > kSpfMaxK) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "K=%lld: the Float64 sparse kernels cover K <= %d", (long long)K, kSpfMaxK);
     if (N > (int64_t)INT32_MAX / 64) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N=%lld is too large", (long long)N);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, RRRMC_ERR_HIP, "no HIP device is visible: this library has no CPU path");
-    if (device < 0 || device >= ndev) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-    rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
-    if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
+    rrrmc_ctx* ctx = nullptr;
+    { const int32_t rcb = ctx_create_begin(&ctx, device, true); if (rcb) return rcb; }
     ctx->model = RRRMC_MODEL_SPARSE_F64; ctx->N = N; ctx->K = K; ctx->R = R;
     ctx->pfW = (R + 63) / 64; ctx->Rpad = ctx->pfW * 64;
-    ctx->device = device; ctx->replica0 = replica0;
-#define PF_TRY(expr)                                                                                             \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            int32_t rc_ = fail(nullptr, e_ == hipErrorOutOfMemory ? RRRMC_ERR_NOMEM : RRRMC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            rrrmc_ctx_destroy(ctx);                                                                              \
-            return rc_;                                                                                          \
-        }                                                                                                        \
-    } while (0)
-    PF_TRY(hipSetDevice(device));
-    PF_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    PF_TRY(hipEventCreate(&ctx->ev_begin));
-    PF_TRY(hipEventCreate(&ctx->ev_end));
+    ctx->replica0 = replica0;
     const size_t nf = (size_t)ctx->Rpad * (size_t)N;
     const size_t nsw = (size_t)ctx->pfW * (size_t)N;
-    PF_TRY(hipMalloc(&ctx->d_A, sizeof(int32_t) * N * K));
-    PF_TRY(hipMalloc(&ctx->pf_J, sizeof(double) * N * K));
-    PF_TRY(hipMalloc(&ctx->sk_lf, sizeof(double) * nf));
-    PF_TRY(hipMalloc(&ctx->pf_undo, sizeof(double) * (size_t)ctx->Rpad * (size_t)(K + 1)));
-    PF_TRY(hipMalloc(&ctx->pf_spins, sizeof(unsigned long long) * nsw));
-    PF_TRY(hipMalloc(&ctx->pf_sites, sizeof(int32_t) * (kSpfItersPerLaunch + 2 * kSpfDepth)));
-    PF_TRY(hipMalloc(&ctx->sk_move_last, sizeof(int32_t) * ctx->Rpad));
-    PF_TRY(hipMalloc(&ctx->sk_E, sizeof(double) * ctx->Rpad));
-    PF_TRY(hipMalloc(&ctx->d_acc, sizeof(int64_t) * ctx->Rpad));
-    PF_TRY(hipMemset(ctx->pf_spins, 0, sizeof(unsigned long long) * nsw));
-    PF_TRY(hipMemset(ctx->sk_lf, 0, sizeof(double) * nf));
-    PF_TRY(hipMemset(ctx->pf_undo, 0, sizeof(double) * (size_t)ctx->Rpad * (size_t)(K + 1)));
-#undef PF_TRY
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->d_A, N * K));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->pf_J, N * K));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->sk_lf, nf));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->pf_undo, (size_t)ctx->Rpad * (size_t)(K + 1)));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->pf_spins, nsw));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->pf_sites, (kSpfItersPerLaunch + 2 * kSpfDepth)));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->sk_move_last, ctx->Rpad));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->sk_E, ctx->Rpad));
+    CTX_CREATE_TRY(ctx, true, dev_alloc(ctx, ctx->d_acc, ctx->Rpad));
+    CTX_CREATE_TRY(ctx, true, hipMemset(ctx->pf_spins, 0, sizeof(unsigned long long) * nsw));
+    CTX_CREATE_TRY(ctx, true, hipMemset(ctx->sk_lf, 0, sizeof(double) * nf));
+    CTX_CREATE_TRY(ctx, true, hipMemset(ctx->pf_undo, 0, sizeof(double) * (size_t)ctx->Rpad * (size_t)(K + 1)));
     *out = ctx;
     return RRRMC_OK;
 }
@@ -125,11 +107,11 @@ int32_t spf_run_energy(rrrmc_ctx* ctx)
 int32_t spf_debug_check(rrrmc_ctx* ctx)
 {
     const size_t nf = (size_t)ctx->Rpad * (size_t)ctx->N;
-    if (!ctx->dbg_flag) { HIP_TRY(ctx, hipMalloc(&ctx->dbg_flag, sizeof(int32_t) * 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, ctx->stream)); }
+    if (!ctx->dbg_flag) { HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_flag, 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, ctx->stream)); }
     if (!ctx->dbg_lf) {
-        HIP_TRY(ctx, hipMalloc(&ctx->dbg_lf, sizeof(double) * nf));
-        HIP_TRY(ctx, hipMalloc(&ctx->dbg_E, sizeof(double) * ctx->Rpad));
-        HIP_TRY(ctx, hipMalloc(&ctx->dbg_ml, sizeof(int32_t) * ctx->Rpad));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_lf, nf));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_E, ctx->Rpad));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_ml, ctx->Rpad));
     }
     hipStream_t st = ctx->stream;
     SpfParams P = spf_params(ctx);
@@ -161,12 +143,7 @@ int32_t spf_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_
     ctx->last_call_rrr = false;
     const int64_t nsamp = iters / step;
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->Rpad;
-    if (es_need > ctx->sk_Es_cap) {
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->sk_Es, ctx->sk_Es_cap, es_need));
     const int64_t nl = (iters + kSpfTeamItersPerLaunch - 1) / kSpfTeamItersPerLaunch;      // the shorter of the two launch lengths
     while ((int64_t)ctx->ev_sweep.size() < 2 * (nl > 0 ? nl : 1)) {
         hipEvent_t e;
@@ -184,9 +161,9 @@ int32_t spf_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_
     const SpfTeamBuild tb = team ? spf_team_build(ctx) : SpfTeamBuild{0, 0, 0};
     if (team && !tb.lds) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "spf_team_kernel has no build for K=%lld", (long long)ctx->K);
     if (team) {
-        if (!ctx->pf_plan) HIP_TRY(ctx, hipMalloc(&ctx->pf_plan, sizeof(uint32_t) * (size_t)(kSpfTeamItersPerLaunch + 2) * (size_t)spf_plan_stride((int)ctx->K)));
+        if (!ctx->pf_plan) HIP_TRY(ctx, dev_alloc(ctx, ctx->pf_plan, (size_t)(kSpfTeamItersPerLaunch + 2) * (size_t)spf_plan_stride((int)ctx->K)));
         if (!ctx->pf_status) {
-            HIP_TRY(ctx, hipMalloc(&ctx->pf_status, sizeof(int32_t)));
+            HIP_TRY(ctx, dev_alloc_bytes(ctx, ctx->pf_status, sizeof(int32_t)));
             HIP_TRY(ctx, hipMemsetAsync(ctx->pf_status, 0, sizeof(int32_t), ctx->stream));
         }
     }
@@ -257,23 +234,18 @@ int32_t spf_cont_async(rrrmc_ctx* ctx, int mode, double beta, int64_t iters, int
     const int64_t N2 = (int64_t)1 << levs;
     SmpState S{};
     { const int32_t rcs = smp_begin(ctx, mode + 1, beta, mode == 2 ? stepf : staged_thr, staged_thr_fact, quantm ? ctx->last_fourK : 0.0, mode == 2 ? 1 : step, ftau, &S); if (rcs) return rcs; }
-    if (!ctx->cs_top) HIP_TRY(ctx, hipMalloc(&ctx->cs_top, sizeof(double) * (size_t)R * (size_t)std::max<int64_t>(N2 >> kCwBottom, 1)));
+    if (!ctx->cs_top) HIP_TRY(ctx, dev_alloc(ctx, ctx->cs_top, (size_t)R * (size_t)std::max<int64_t>(N2 >> kCwBottom, 1)));
     if (!ctx->cs_buf) {
-        if (!dblm) HIP_TRY(ctx, hipMalloc(&ctx->cs_spins, sizeof(uint32_t) * R * W));
-        HIP_TRY(ctx, hipMalloc(&ctx->cs_buf, sizeof(double) * (size_t)R * (size_t)(2 * N + 2 * N2 + K + 1)));
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->cs_u16), (N > 65535 ? sizeof(uint32_t) : sizeof(uint16_t)) * (size_t)R * 2 * N));
-        HIP_TRY(ctx, hipMalloc(&ctx->rs_status, sizeof(int32_t) * R));
-        if (!ctx->q_stats) HIP_TRY(ctx, hipMalloc(&ctx->q_stats, sizeof(int64_t) * R * 3));
-        if (!ctx->wt_time) HIP_TRY(ctx, hipMalloc(&ctx->wt_time, sizeof(double) * R));
+        if (!dblm) HIP_TRY(ctx, dev_alloc(ctx, ctx->cs_spins, R * W));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->cs_buf, (size_t)R * (size_t)(2 * N + 2 * N2 + K + 1)));
+        HIP_TRY(ctx, dev_alloc_bytes(ctx, ctx->cs_u16, (N > 65535 ? sizeof(uint32_t) : sizeof(uint16_t)) * (size_t)R * 2 * N));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->rs_status, R));
+        if (!ctx->q_stats) HIP_TRY(ctx, dev_alloc(ctx, ctx->q_stats, R * 3));
+        if (!ctx->wt_time) HIP_TRY(ctx, dev_alloc(ctx, ctx->wt_time, R));
     }
     const int64_t nsamp = mode == 2 ? iters : smp_nsamp(ctx, iters, step);
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->Rpad;
-    if (es_need > ctx->sk_Es_cap) {
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->sk_Es, ctx->sk_Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -283,8 +255,8 @@ int32_t spf_cont_async(rrrmc_ctx* ctx, int mode, double beta, int64_t iters, int
     P.S = S; P.samples_before = mode == 2 ? ctx->smp_it : 0; P.ps_top = ctx->cs_top;
     if (mode == 3) {
         if (!ctx->eo_cmin) {
-            HIP_TRY(ctx, hipMalloc(&ctx->eo_cmin, sizeof(uint32_t) * R * W));
-            HIP_TRY(ctx, hipMalloc(&ctx->eo_ftau, sizeof(double) * N));
+            HIP_TRY(ctx, dev_alloc(ctx, ctx->eo_cmin, R * W));
+            HIP_TRY(ctx, dev_alloc(ctx, ctx->eo_ftau, N));
         }
         ctx->eo_W = W;
         if (!S.resume) {                // (a resumed call: the run's table is on the device already)

@@ -62,19 +62,19 @@ int32_t fast_setup(rrrmc_ctx* ctx)
     ctx->pff_nblk = nblk;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // (a failure midway leaves pff_ready false: the next call starts over, so whatever an earlier attempt allocated is released first)
-    free_dev(ctx->pff_table); free_dev(ctx->pff_absJ); free_dev(ctx->pff_bond_off); free_dev(ctx->pff_thr_hi); free_dev(ctx->pff_thr_lo); free_dev(ctx->pff_flags);
-    HIP_TRY(ctx, hipMalloc(&ctx->pff_table, sizeof(uint16_t) * table.size()));
-    HIP_TRY(ctx, hipMalloc(&ctx->pff_absJ, sizeof(double) * etab.size()));
-    HIP_TRY(ctx, hipMalloc(&ctx->pff_bond_off, sizeof(uint32_t) * bond_off.size()));
-    HIP_TRY(ctx, hipMalloc(&ctx->pff_thr_hi, sizeof(uint32_t) * (size_t)N * NT));
-    HIP_TRY(ctx, hipMalloc(&ctx->pff_thr_lo, sizeof(uint32_t) * (size_t)N * NT));
-    HIP_TRY(ctx, hipMalloc(&ctx->pff_flags, sizeof(uint32_t) * (size_t)N));
+    dev_free(ctx, ctx->pff_table); dev_free(ctx, ctx->pff_absJ); dev_free(ctx, ctx->pff_bond_off); dev_free(ctx, ctx->pff_thr_hi); dev_free(ctx, ctx->pff_thr_lo); dev_free(ctx, ctx->pff_flags);
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->pff_table, table.size()));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->pff_absJ, etab.size()));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->pff_bond_off, bond_off.size()));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->pff_thr_hi, (size_t)N * NT));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->pff_thr_lo, (size_t)N * NT));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->pff_flags, (size_t)N));
     HIP_TRY(ctx, hipMemcpy(ctx->pff_table, table.data(), sizeof(uint16_t) * table.size(), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->pff_absJ, etab.data(), sizeof(double) * etab.size(), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->pff_bond_off, bond_off.data(), sizeof(uint32_t) * bond_off.size(), hipMemcpyHostToDevice));
     for (int i = 0; i < 2; ++i) {
-        if (!ctx->d_slots[i]) HIP_TRY(ctx, hipMalloc(&ctx->d_slots[i], sizeof(uint32_t) * kMaxSlotsPerBatch));
-        if (!ctx->d_vecs[i]) HIP_TRY(ctx, hipMalloc(&ctx->d_vecs[i], sizeof(uint32_t) * kMaxSlotsPerBatch));
+        if (!ctx->d_slots[i]) HIP_TRY(ctx, dev_alloc(ctx, ctx->d_slots[i], kMaxSlotsPerBatch));
+        if (!ctx->d_vecs[i]) HIP_TRY(ctx, dev_alloc(ctx, ctx->d_vecs[i], kMaxSlotsPerBatch));
     }
     if (!ctx->plan_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->plan_stream, hipStreamNonBlocking));
     if (!ctx->ev_upload) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming));
@@ -142,13 +142,8 @@ int32_t spf_fast_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t st
     const size_t nchunks = ctx->chunks_n;
     const std::vector<rrrmc_ctx::BatchDesc>& batches = ctx->chunk_batches;
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->Rpad;
-    if (es_need > ctx->sk_Es_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
+    if (es_need > ctx->sk_Es_cap) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, dev_grow(ctx, ctx->sk_Es, ctx->sk_Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2 * batches.size() + 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));

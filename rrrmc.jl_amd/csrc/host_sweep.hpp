@@ -24,11 +24,11 @@ int32_t prepare_chunk_list(rrrmc_ctx* ctx, int64_t iters, int64_t step, int C, b
             // the device list may still be read by queued launches of earlier calls
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->plan_stream));
-            free_dev(ctx->d_chunks);
-            free_dev(ctx->d_chunks_alt);
+            dev_free(ctx, ctx->d_chunks);
+            dev_free(ctx, ctx->d_chunks_alt);
             ctx->chunks_cap = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->d_chunks, sizeof(ChunkDesc) * nch_all));
-            if (ctx->model == RRRMC_MODEL_SPARSE_PM1) HIP_TRY(ctx, hipMalloc(&ctx->d_chunks_alt, sizeof(ChunkDesc) * nch_all));      // (the fast Float64 sampler keeps one table)
+            HIP_TRY(ctx, dev_alloc(ctx, ctx->d_chunks, nch_all));
+            if (ctx->model == RRRMC_MODEL_SPARSE_PM1) HIP_TRY(ctx, dev_alloc(ctx, ctx->d_chunks_alt, nch_all));      // (the fast Float64 sampler keeps one table)
             ctx->chunks_cap = nch_all;
         }
         if (nch_all > ctx->h_chunks_cap) {
@@ -51,13 +51,13 @@ int32_t ensure_big_buffers(rrrmc_ctx* ctx)
     if (!ctx->big_mode || ctx->big_bufs_ready) return RRRMC_OK;
     const int64_t N = ctx->N, K = ctx->K;
     for (int i = 0; i < 2; ++i) {
-        if (!ctx->d_nbrs[i]) HIP_TRY(ctx, hipMalloc(&ctx->d_nbrs[i], sizeof(uint32_t) * kMaxSlotsPerBatch * big_rec_words((int)K)));
+        if (!ctx->d_nbrs[i]) HIP_TRY(ctx, dev_alloc(ctx, ctx->d_nbrs[i], kMaxSlotsPerBatch * big_rec_words((int)K)));
         if (ctx->big_masks && !ctx->d_masks[i])
-            HIP_TRY(ctx, hipMalloc(&ctx->d_masks[i], sizeof(uint32_t) * (ctx->big_cm ? (32 >> ctx->big_lgr) : 4) * ctx->batch_slots_max * ctx->G));
+            HIP_TRY(ctx, dev_alloc(ctx, ctx->d_masks[i], (ctx->big_cm ? (32 >> ctx->big_lgr) : 4) * ctx->batch_slots_max * ctx->G));
     }
     if (ctx->big_masks) {
         const int64_t S = 32 >> ctx->big_lgr;
-        if (!ctx->d_bigimg) HIP_TRY(ctx, hipMalloc(&ctx->d_bigimg, sizeof(uint32_t) * ctx->G * S * ((N + S - 1) / S)));
+        if (!ctx->d_bigimg) HIP_TRY(ctx, dev_alloc(ctx, ctx->d_bigimg, ctx->G * S * ((N + S - 1) / S)));
         HIP_TRY(ctx, raise_lds_attr(reinterpret_cast<const void*>(ctx->big_cm ? big_applyc_for_K((int)K) : big_apply_for_K((int)K)), big_lds_bytes(N, ctx->big_lgr)));
     }
     ctx->big_bufs_ready = true;
@@ -102,13 +102,8 @@ int32_t pm1_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_
     const std::vector<rrrmc_ctx::BatchDesc>& batches = ctx->chunk_batches;
 
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->Rpad;
-    if (es_need > ctx->Es_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // queued launches of earlier calls still write the old buffer
-        free_dev(ctx->d_Es);
-        ctx->Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_Es, sizeof(int32_t) * es_need));
-        ctx->Es_cap = es_need;
-    }
+    if (es_need > ctx->Es_cap) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // queued launches of earlier calls still write the old buffer
+    HIP_TRY(ctx, dev_grow(ctx, ctx->d_Es, ctx->Es_cap, es_need));
 
     std::vector<hipEvent_t>& EV = ctx->acc_mode ? ctx->ev_pool : ctx->ev_sweep;
     const size_t ebase = ctx->acc_mode ? ctx->ev_pool_used : 0;

@@ -117,7 +117,7 @@ int32_t tle_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kin
     rrrmc_ctx* ctx = *out;
     ctx->model = ens_model(ENS_TLE, slice_kind);
     // the arrays sized by the level count come with rrrmc_tle_set_params
-    free_dev(ctx->q_cls); free_dev(ctx->q_sv); free_dev(ctx->q_st); free_dev(ctx->q_T); free_dev(ctx->re_tab);
+    dev_free(ctx, ctx->q_cls); dev_free(ctx, ctx->q_sv); dev_free(ctx, ctx->q_st); dev_free(ctx, ctx->q_T); dev_free(ctx, ctx->re_tab);
     ctx->re_htab.clear(); ctx->re_hft.clear(); ctx->le_hcode.clear();
     return RRRMC_OK;
 }
@@ -132,9 +132,9 @@ int32_t tle_set_topology(rrrmc_ctx* ctx, const int32_t* rowptr, const int32_t* c
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->re_params_set = false; ctx->tle_topology_set = false;
     ctx->std_cache_live = false; ctx->q_cache_valid = false;
-    free_dev(ctx->tle_rowptr); free_dev(ctx->tle_cols);
-    HIP_TRY(ctx, hipMalloc(&ctx->tle_rowptr, sizeof(int32_t) * (size_t)(Nk + 1)));
-    HIP_TRY(ctx, hipMalloc(&ctx->tle_cols, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
+    dev_free(ctx, ctx->tle_rowptr); dev_free(ctx, ctx->tle_cols);
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->tle_rowptr, (size_t)(Nk + 1)));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->tle_cols, (size_t)(nnz > 0 ? nnz : 1)));
     HIP_TRY(ctx, hipMemcpy(ctx->tle_rowptr, rowptr, sizeof(int32_t) * (size_t)(Nk + 1), hipMemcpyHostToDevice));
     if (nnz > 0) HIP_TRY(ctx, hipMemcpy(ctx->tle_cols, cols, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
     ctx->tle_maxdeg = md;
@@ -178,14 +178,14 @@ int32_t tle_set_params(rrrmc_ctx* ctx, double gamma, double lambda, double beta_
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->re_params_set = false;
     ctx->std_cache_live = false; ctx->q_cache_valid = false;
-    free_dev(ctx->re_tab); free_dev(ctx->tle_code); free_dev(ctx->q_sv); free_dev(ctx->q_st); free_dev(ctx->q_T); free_dev(ctx->tle_cls); free_dev(ctx->tle_lf2);
-    HIP_TRY(ctx, hipMalloc(&ctx->re_tab, sizeof(double) * (size_t)(2 * L)));
-    HIP_TRY(ctx, hipMalloc(&ctx->tle_code, sizeof(uint32_t) * code.size()));
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->q_sv), sizeof(uint16_t) * (size_t)R * (size_t)(2 * L) * (size_t)N));
-    HIP_TRY(ctx, hipMalloc(&ctx->q_st, sizeof(int32_t) * (size_t)R * (size_t)(2 * L)));
-    HIP_TRY(ctx, hipMalloc(&ctx->q_T, sizeof(double) * (size_t)R * (size_t)(2 * L)));
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->tle_cls), sizeof(uint16_t) * (size_t)R * (size_t)N));
-    HIP_TRY(ctx, hipMalloc(&ctx->tle_lf2, sizeof(int32_t) * (size_t)R * (size_t)N));
+    dev_free(ctx, ctx->re_tab); dev_free(ctx, ctx->tle_code); dev_free(ctx, ctx->q_sv); dev_free(ctx, ctx->q_st); dev_free(ctx, ctx->q_T); dev_free(ctx, ctx->tle_cls); dev_free(ctx, ctx->tle_lf2);
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->re_tab, (size_t)(2 * L)));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->tle_code, code.size()));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->q_sv, (size_t)R * (size_t)(2 * L) * (size_t)N));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->q_st, (size_t)R * (size_t)(2 * L)));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->q_T, (size_t)R * (size_t)(2 * L)));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->tle_cls, (size_t)R * (size_t)N));
+    HIP_TRY(ctx, dev_alloc(ctx, ctx->tle_lf2, (size_t)R * (size_t)N));
     HIP_TRY(ctx, hipMemcpy(ctx->re_tab, dE.data(), sizeof(double) * (size_t)L, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->tle_code, code.data(), sizeof(uint32_t) * code.size(), hipMemcpyHostToDevice));
     // (a set slot that no push! has written is never read as a site: zeroed all the same, so that nothing in the arrays is indeterminate)

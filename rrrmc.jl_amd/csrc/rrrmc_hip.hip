@@ -19,6 +19,8 @@
 #include <utility>
 #include <vector>
 
+typedef hipError_t dev_err_t;
+#include "dev_mem.hpp"
 #include "ens_models.hpp"
 #include "sk_kernels.hpp"
 #include "sk_block_kernel.hpp"
@@ -46,6 +48,10 @@
 
 using namespace rrrmc;
 
+// dev_mem.hpp's two raw hooks
+hipError_t dev_raw_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+void dev_raw_free(void* p) { (void)hipFree(p); }
+
 namespace {
 
 thread_local std::string g_create_error;
@@ -61,6 +67,7 @@ unsigned long long* g_stamps = nullptr;
 }  // namespace
 
 struct rrrmc_ctx {
+    DevMem mem;                    // every device allocation below (dev_mem.hpp); rrrmc_ctx_destroy frees them through it
     int32_t model = 0;
     int64_t N = 0, K = 0, R = 0;
     int64_t G = 0, Rpad = 0;
@@ -385,7 +392,37 @@ int32_t fail(rrrmc_ctx* ctx, int32_t code, const char* fmt, ...)
             return fail(ctx, RRRMC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-template <typename T> void free_dev(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+// A creator's device calls once the context exists: a failure destroys the half-built context (which frees whatever it had reached) and
+// is the creator's result.  oom_is_nomem: hipErrorOutOfMemory is RRRMC_ERR_NOMEM (the sparse Float64, discretised and general-level
+// creators; the others report RRRMC_ERR_HIP: DESIGN.md §1a).
+#define CTX_CREATE_TRY(ctx, oom_is_nomem, expr)                                                                  \
+    do {                                                                                                         \
+        hipError_t e_ = (expr);                                                                                  \
+        if (e_ != hipSuccess) {                                                                                  \
+            int32_t rc_ = fail(nullptr, (oom_is_nomem) && e_ == hipErrorOutOfMemory ? RRRMC_ERR_NOMEM : RRRMC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+            rrrmc_ctx_destroy(ctx);                                                                              \
+            return rc_;                                                                                          \
+        }                                                                                                        \
+    } while (0)
+
+// What every creator does once its own argument checks have passed: the device is there and in range, a context on it with its stream
+// and the two events of the calls' timing.
+int32_t ctx_create_begin(rrrmc_ctx** ctx_out, int32_t device, bool oom_is_nomem)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, RRRMC_ERR_HIP, "no HIP device is visible: this library has no CPU path");
+    if (device < 0 || device >= ndev) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
+    rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
+    if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
+    ctx->device = device;
+    CTX_CREATE_TRY(ctx, oom_is_nomem, hipSetDevice(device));
+    CTX_CREATE_TRY(ctx, oom_is_nomem, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+    CTX_CREATE_TRY(ctx, oom_is_nomem, hipEventCreate(&ctx->ev_begin));
+    CTX_CREATE_TRY(ctx, oom_is_nomem, hipEventCreate(&ctx->ev_end));
+    *ctx_out = ctx;
+    return RRRMC_OK;
+}
 
 // template instantiation tables: runtime K (or sites-per-thread) -> kernel pointer
 #define RRRMC_DISPATCH_UPTO7(k, F)                                                                                     \
@@ -531,10 +568,7 @@ int32_t ensure_io(rrrmc_ctx* ctx, size_t bytes)
 {
     if (bytes <= ctx->io_cap) return RRRMC_OK;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    free_dev(ctx->d_io);
-    ctx->io_cap = 0;
-    if (hipMalloc(&ctx->d_io, bytes) != hipSuccess) { ctx->d_io = nullptr; return fail(ctx, RRRMC_ERR_NOMEM, "cannot allocate %zu bytes of transfer staging", bytes); }
-    ctx->io_cap = bytes;
+    if (dev_grow_bytes(ctx, ctx->d_io, ctx->io_cap, bytes) != hipSuccess) return fail(ctx, RRRMC_ERR_NOMEM, "cannot allocate %zu bytes of transfer staging", bytes);
     return RRRMC_OK;
 }
 
@@ -603,14 +637,14 @@ inline bool dbg_inject() { const char* e = std::getenv("RRRMC_DEBUG_INJECT"); re
 // found after an earlier queued call must survive until the sync that reports it.
 int32_t dbg_flag_ensure(rrrmc_ctx* ctx)
 {
-    if (!ctx->dbg_flag) { HIP_TRY(ctx, hipMalloc(&ctx->dbg_flag, sizeof(int32_t) * 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, ctx->stream)); }
+    if (!ctx->dbg_flag) { HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_flag, 2)); HIP_TRY(ctx, hipMemsetAsync(ctx->dbg_flag, 0, sizeof(int32_t) * 2, ctx->stream)); }
     return RRRMC_OK;
 }
 // after a standardMC call of the +-J model: d_E (tracked) against energy(X, C) recomputed from the spins
 int32_t debug_check_pm1(rrrmc_ctx* ctx)
 {
     { const int32_t rcf = dbg_flag_ensure(ctx); if (rcf) return rcf; }
-    if (!ctx->dbg_Ei) HIP_TRY(ctx, hipMalloc(&ctx->dbg_Ei, sizeof(int32_t) * ctx->Rpad));
+    if (!ctx->dbg_Ei) HIP_TRY(ctx, dev_alloc(ctx, ctx->dbg_Ei, ctx->Rpad));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->dbg_Ei, ctx->d_E, sizeof(int32_t) * ctx->Rpad, hipMemcpyDeviceToDevice, ctx->stream));
     if (dbg_inject()) hipLaunchKernelGGL(dbg_inject_i32_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->dbg_Ei);       // (RRRMC_DEBUG_INJECT=1: tests only)
     const int32_t rc = run_energy_bs(ctx, nullptr);          // d_E = energy(X, C): equal to the tracked values, or the flag says so
@@ -628,8 +662,8 @@ inline void smp_drop(rrrmc_ctx* ctx) { if (ctx) ctx->smp_kind = 0; }
 int32_t smp_begin(rrrmc_ctx* ctx, int kind, double p0, double p1, double p2, double p3, int64_t step, const double* ftau, SmpState* S)
 {
     if (!ctx->smp_f) {
-        HIP_TRY(ctx, hipMalloc(&ctx->smp_f, sizeof(double) * (size_t)ctx->R * kSmpF));
-        HIP_TRY(ctx, hipMalloc(&ctx->smp_i, sizeof(long long) * (size_t)ctx->R * kSmpI));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->smp_f, (size_t)ctx->R * kSmpF));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->smp_i, (size_t)ctx->R * kSmpI));
         HIP_TRY(ctx, hipMemsetAsync(ctx->smp_f, 0, sizeof(double) * (size_t)ctx->R * kSmpF, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(ctx->smp_i, 0, sizeof(long long) * (size_t)ctx->R * kSmpI, ctx->stream));
     }
@@ -832,16 +866,11 @@ int32_t rrrmc_ctx_create(rrrmc_ctx** out, int32_t model, int64_t N, int64_t K, i
     if (K > kMaxK) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "K=%lld: the sparse +-J kernels cover K <= %d", (long long)K, kMaxK);
     if (N > (int64_t)INT32_MAX / 8) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N=%lld is too large", (long long)N);
     if (replica0 % 32) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "replica0 must be a multiple of 32 (given %u)", replica0);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, RRRMC_ERR_HIP, "no HIP device is visible: this library has no CPU path");
-    if (device < 0 || device >= ndev) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-
-    rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
-    if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
+    rrrmc_ctx* ctx = nullptr;
+    { const int32_t rcb = ctx_create_begin(&ctx, device, false); if (rcb) return rcb; }
     ctx->model = model; ctx->N = N; ctx->K = K; ctx->R = R;
     ctx->G = (R + 31) / 32; ctx->Rpad = ctx->G * 32;
-    ctx->device = device; ctx->replica0 = replica0;
+    ctx->replica0 = replica0;
     ctx->TS = K <= 4 ? 4 : 8;
 
     // chunk length: the longest multiple of 64 that fits the 160 KiB LDS next to the state (a step of the sweep kernel has a fixed
@@ -902,48 +931,34 @@ int32_t rrrmc_ctx_create(rrrmc_ctx** out, int32_t model, int64_t N, int64_t K, i
         if (ctx->big_masks) { ctx->batch_chunks_max = kBigApplyChunks; ctx->batch_first_chunks = 64; }
     }
 
-#define CREATE_TRY(expr)                                                                                         \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            int32_t rc_ = fail(nullptr, RRRMC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));           \
-            rrrmc_ctx_destroy(ctx);                                                                              \
-            return rc_;                                                                                          \
-        }                                                                                                        \
-    } while (0)
-    CREATE_TRY(hipSetDevice(device));
-    CREATE_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    CREATE_TRY(hipEventCreate(&ctx->ev_begin));
-    CREATE_TRY(hipEventCreate(&ctx->ev_end));
-    CREATE_TRY(hipMalloc(&ctx->d_A, sizeof(int32_t) * N * K));
-    CREATE_TRY(hipMalloc(&ctx->d_J, sizeof(int8_t) * N * K));
-    CREATE_TRY(hipMalloc(&ctx->d_table, sizeof(uint16_t) * (ctx->lds_mode ? N * ctx->TS : 8)));
-    CREATE_TRY(hipMalloc(&ctx->d_U, sizeof(uint32_t) * ctx->Rpad));
-    CREATE_TRY(hipMemset(ctx->d_U, 0, sizeof(uint32_t) * ctx->Rpad));
-    CREATE_TRY(hipMalloc(&ctx->d_spins, sizeof(uint32_t) * ctx->G * N));
-    CREATE_TRY(hipMalloc(&ctx->d_E, sizeof(int32_t) * ctx->Rpad));
-    CREATE_TRY(hipMalloc(&ctx->d_acc, sizeof(int64_t) * ctx->Rpad));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_A, N * K));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_J, N * K));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_table, (ctx->lds_mode ? N * ctx->TS : 8)));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_U, ctx->Rpad));
+    CTX_CREATE_TRY(ctx, false, hipMemset(ctx->d_U, 0, sizeof(uint32_t) * ctx->Rpad));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_spins, ctx->G * N));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_E, ctx->Rpad));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_acc, ctx->Rpad));
     for (int i = 0; i < 2; ++i) {
-        CREATE_TRY(hipMalloc(&ctx->d_slots[i], sizeof(uint32_t) * kMaxSlotsPerBatch));
-        CREATE_TRY(hipMalloc(&ctx->d_vecs[i], sizeof(uint32_t) * kMaxSlotsPerBatch));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_slots[i], kMaxSlotsPerBatch));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_vecs[i], kMaxSlotsPerBatch));
     }
     // (the record / mask / image buffers of the big-N random-site path — up to 2 x 128 MiB + 2 x 2 GiB — are allocated by its first
     //  call, ensure_big_buffers: a context that only runs colour sweeps never pays for them)
-    CREATE_TRY(hipStreamCreateWithFlags(&ctx->plan_stream, hipStreamNonBlocking));
-    CREATE_TRY(hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming));
-    CREATE_TRY(hipMemset(ctx->d_spins, 0, sizeof(uint32_t) * ctx->G * N));
-    CREATE_TRY(hipMemset(ctx->d_E, 0, sizeof(int32_t) * ctx->Rpad));
-    CREATE_TRY(hipMemset(ctx->d_acc, 0, sizeof(int64_t) * ctx->Rpad));
+    CTX_CREATE_TRY(ctx, false, hipStreamCreateWithFlags(&ctx->plan_stream, hipStreamNonBlocking));
+    CTX_CREATE_TRY(ctx, false, hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming));
+    CTX_CREATE_TRY(ctx, false, hipMemset(ctx->d_spins, 0, sizeof(uint32_t) * ctx->G * N));
+    CTX_CREATE_TRY(ctx, false, hipMemset(ctx->d_E, 0, sizeof(int32_t) * ctx->Rpad));
+    CTX_CREATE_TRY(ctx, false, hipMemset(ctx->d_acc, 0, sizeof(int64_t) * ctx->Rpad));
     if (ctx->lds_mode) {
         sweep_fn fn = sweep_for_K((int)K, ctx->sweep_mode);
-        CREATE_TRY(raise_lds_attr(reinterpret_cast<const void*>(fn), ctx->lds_bytes));
+        CTX_CREATE_TRY(ctx, false, raise_lds_attr(reinterpret_cast<const void*>(fn), ctx->lds_bytes));
         for (const SweepZbBuild& zb : kSweepZbBuilds)
-            if (zb.K == (int)K && zb.mode == ctx->sweep_mode) CREATE_TRY(raise_lds_attr(reinterpret_cast<const void*>(zb.fn), ctx->lds_bytes));
-        CREATE_TRY(raise_lds_attr(reinterpret_cast<const void*>(plan_for_K((int)K)), ctx->plan_lds_bytes));
+            if (zb.K == (int)K && zb.mode == ctx->sweep_mode) CTX_CREATE_TRY(ctx, false, raise_lds_attr(reinterpret_cast<const void*>(zb.fn), ctx->lds_bytes));
+        CTX_CREATE_TRY(ctx, false, raise_lds_attr(reinterpret_cast<const void*>(plan_for_K((int)K)), ctx->plan_lds_bytes));
     }
     if (ctx->big_mode)
-        CREATE_TRY(raise_lds_attr(reinterpret_cast<const void*>(plan_big_for_K((int)K)), ctx->plan_lds_bytes));
-#undef CREATE_TRY
+        CTX_CREATE_TRY(ctx, false, raise_lds_attr(reinterpret_cast<const void*>(plan_big_for_K((int)K)), ctx->plan_lds_bytes));
     *out = ctx;
     return RRRMC_OK;
 }
@@ -958,35 +973,7 @@ void rrrmc_ctx_destroy(rrrmc_ctx* ctx)
     }
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    free_dev(ctx->d_A); free_dev(ctx->d_J); free_dev(ctx->d_table); free_dev(ctx->d_spins);
-    free_dev(ctx->d_E); free_dev(ctx->d_acc); free_dev(ctx->d_chunks); free_dev(ctx->d_chunks_alt); free_dev(ctx->d_Es);
-    free_dev(ctx->d_U); free_dev(ctx->d_io);
-    for (uint32_t*& l : ctx->d_color_list) free_dev(l);
-    free_dev(ctx->sk_J4); free_dev(ctx->sk_blkJw); free_dev(ctx->sk_blkSites); free_dev(ctx->sk_hl);
-    free_dev(ctx->sk_J); free_dev(ctx->sk_lf); free_dev(ctx->sk_lfl); free_dev(ctx->sk_move_last); free_dev(ctx->sk_spins);
-    free_dev(ctx->sk_E); free_dev(ctx->sk_Es); free_dev(ctx->skb_J); free_dev(ctx->skb_lf); free_dev(ctx->skb_lfl);
-    free_dev(ctx->q_spins); free_dev(ctx->q_cls); free_dev(ctx->q_sv); free_dev(ctx->q_spos); free_dev(ctx->q_st);
-    free_dev(ctx->q_T); free_dev(ctx->q_z); free_dev(ctx->q_accrate); free_dev(ctx->q_stats);
-    free_dev(ctx->rs_buf); free_dev(ctx->rs_spins); free_dev(ctx->rs_status);
-    free_dev(ctx->rp_spins); free_dev(ctx->rp_cls); free_dev(ctx->rp_sv); free_dev(ctx->rp_spos);
-    free_dev(ctx->pf_J); free_dev(ctx->pf_spins); free_dev(ctx->pf_undo); free_dev(ctx->pf_sites); free_dev(ctx->pf_plan); free_dev(ctx->pf_status);
-    free_dev(ctx->db_dJ); free_dev(ctx->db_rJ); free_dev(ctx->db_cls); free_dev(ctx->db_sv); free_dev(ctx->db_spos); free_dev(ctx->db_lf); free_dev(ctx->db_undo); free_dev(ctx->db_mlast);
-    free_dev(ctx->pff_table); free_dev(ctx->pff_absJ); free_dev(ctx->pff_bond_off); free_dev(ctx->pff_thr_hi); free_dev(ctx->pff_thr_lo); free_dev(ctx->pff_flags);
-    free_dev(ctx->wt_t); free_dev(ctx->wt_id); free_dev(ctx->wt_pos); free_dev(ctx->wt_time);
-    free_dev(ctx->smp_f); free_dev(ctx->smp_i); free_dev(ctx->cs_top);
-    free_dev(ctx->q_Jf); free_dev(ctx->q_flf); free_dev(ctx->q_fundo); free_dev(ctx->q_fml);
-    free_dev(ctx->eo_cmin); free_dev(ctx->eo_ftau);
-    free_dev(ctx->q_Jb); free_dev(ctx->q_slf); free_dev(ctx->q_smv); free_dev(ctx->q_scur);
-    free_dev(ctx->cs_spins); free_dev(ctx->cs_buf); free_dev(ctx->cs_u16);
-    free_dev(ctx->snap); free_dev(ctx->d_pairs); free_dev(ctx->d_ovl); free_dev(ctx->d_qobs);
-    free_dev(ctx->re_sp); free_dev(ctx->re_mu); free_dev(ctx->re_tab); free_dev(ctx->re_Eslice); free_dev(ctx->le_dist);
-    free_dev(ctx->tle_rowptr); free_dev(ctx->tle_cols); free_dev(ctx->tle_code); free_dev(ctx->tle_lf2); free_dev(ctx->tle_cls);
-    free_dev(ctx->sat_off); free_dev(ctx->sat_ent); free_dev(ctx->sat_spT);
-    free_dev(ctx->pc_col); free_dev(ctx->pc_row); free_dev(ctx->pc_ds); free_dev(ctx->pc_pm); free_dev(ctx->pc_mm);
-    free_dev(ctx->cm_col); free_dev(ctx->cm_row); free_dev(ctx->cm_lab); free_dev(ctx->cm_ds); free_dev(ctx->cm_mk);
-    for (int i = 0; i < 2; ++i) { free_dev(ctx->d_slots[i]); free_dev(ctx->d_vecs[i]); free_dev(ctx->d_nbrs[i]); free_dev(ctx->d_masks[i]); }
-    free_dev(ctx->d_bigimg);
-    free_dev(ctx->dbg_flag); free_dev(ctx->dbg_Ei); free_dev(ctx->dbg_lf); free_dev(ctx->dbg_lfl); free_dev(ctx->dbg_E); free_dev(ctx->dbg_ml);
+    dev_free_all(ctx);
     if (ctx->plan_stream) { (void)hipStreamSynchronize(ctx->plan_stream); (void)hipStreamDestroy(ctx->plan_stream); }
     if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
     for (hipEvent_t e : ctx->ev_plan) (void)hipEventDestroy(e);
@@ -1279,13 +1266,13 @@ int32_t rrrmc_get_fields(rrrmc_ctx* ctx, int64_t* lfields_out)
     if (!lfields_out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "lfields_out is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint8_t* d_nun = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d_nun, (size_t)ctx->Rpad * ctx->N));
+    HIP_TRY(ctx, dev_alloc(ctx, d_nun, (size_t)ctx->Rpad * ctx->N));
     rc = run_energy(ctx, d_nun);
-    if (rc) { (void)hipFree(d_nun); return rc; }
+    if (rc) { dev_free(ctx, d_nun); return rc; }
     std::vector<uint8_t> nun((size_t)ctx->Rpad * ctx->N);
     hipError_t e = hipMemcpyAsync(nun.data(), d_nun, nun.size(), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_nun);
+    dev_free(ctx, d_nun);
     HIP_TRY(ctx, e);
     // lfields[x] = -dE(x) = -2 (K - 2 n)   (src/graphs/RRG.jl:164-189, 236-244)
     for (int64_t r = 0; r < ctx->R; ++r)
@@ -1547,7 +1534,7 @@ int32_t rrrmc_set_coloring(rrrmc_ctx* ctx, const int32_t* color, int32_t ncolors
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (uint32_t*& l : ctx->d_color_list) free_dev(l);
+    for (uint32_t*& l : ctx->d_color_list) dev_free(ctx, l);
     ctx->d_color_list.assign((size_t)ncolors, nullptr);
     ctx->color_count.assign((size_t)ncolors, 0);
     const int W = K <= 3 ? 4 : 8;                              // words per record (colored_sweep_kernel)
@@ -1562,7 +1549,7 @@ int32_t rrrmc_set_coloring(rrrmc_ctx* ctx, const int32_t* color, int32_t ncolors
             for (int64_t k = 0; k < K; ++k)
                 recs[i * W + 1 + k] = (uint32_t)ctx->h_A[x * K + k] | (ctx->h_Jsign[x * K + k] ? 0x80000000u : 0u);
         }
-        HIP_TRY(ctx, hipMalloc(&ctx->d_color_list[c], sizeof(uint32_t) * recs.size()));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->d_color_list[c], recs.size()));
         HIP_TRY(ctx, hipMemcpy(ctx->d_color_list[c], recs.data(), sizeof(uint32_t) * recs.size(), hipMemcpyHostToDevice));
     }
     ctx->ncolors = ncolors;
@@ -1595,12 +1582,7 @@ int32_t rrrmc_colored_sweeps_async(rrrmc_ctx* ctx, double beta, int64_t sweeps, 
     ctx->timing_valid = false;
     const int64_t K = ctx->K, nsamp = sweeps / step;
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->Rpad;
-    if (es_need > ctx->Es_cap) {
-        free_dev(ctx->d_Es);
-        ctx->Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_Es, sizeof(int32_t) * es_need));
-        ctx->Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->d_Es, ctx->Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -2084,64 +2066,46 @@ int32_t quant_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t K, int64_t M, int6
     if (M <= 2) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "M must be greater than 2, given: %lld", (long long)M);   // QT.jl:47
     if (spf && K > kContKmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "K=%lld: the Float64 sparse slice kernels cover K <= %d", (long long)K, kContKmax);
     if (Nk * M > (int64_t)1 << 28) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N = Nk*M = %lld is beyond the GraphQuant kernels (N <= 2^28)", (long long)(Nk * M));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, RRRMC_ERR_HIP, "no HIP device is visible: this library has no CPU path");
-    if (device < 0 || device >= ndev) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "device %d out of range (0..%d)", device, ndev - 1);
-    rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
-    if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
+    rrrmc_ctx* ctx = nullptr;
+    { const int32_t rcb = ctx_create_begin(&ctx, device, false); if (rcb) return rcb; }
     ctx->model = RRRMC_MODEL_QUANT_RRG; ctx->N = Nk * M; ctx->K = K; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = Nk; ctx->qM = M; ctx->qW = 2 * ((Nk * M + 63) / 64);
     ctx->q_sk = sk; ctx->q_skn = skn; ctx->q_spf = spf; ctx->q_pat = pat; ctx->q_Wk = 2 * ((Nk + 63) / 64);
-    ctx->device = device; ctx->replica0 = replica0;
+    ctx->replica0 = replica0;
     const int64_t N = ctx->N;
-#define Q_TRY(expr)                                                                                              \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            int32_t rc_ = fail(nullptr, RRRMC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));           \
-            rrrmc_ctx_destroy(ctx);                                                                              \
-            return rc_;                                                                                          \
-        }                                                                                                        \
-    } while (0)
-    Q_TRY(hipSetDevice(device));
-    Q_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    Q_TRY(hipEventCreate(&ctx->ev_begin));
-    Q_TRY(hipEventCreate(&ctx->ev_end));
     if (skn) {
-        Q_TRY(hipMalloc(&ctx->sk_J, sizeof(double) * Nk * Nk));
-        Q_TRY(hipMalloc(&ctx->q_slf, sizeof(double) * (size_t)R * 2 * (size_t)M * (size_t)Nk));
-        Q_TRY(hipMalloc(&ctx->q_smv, sizeof(int32_t) * (size_t)R * (size_t)M));
-        Q_TRY(hipMalloc(&ctx->q_scur, (size_t)R * (size_t)M));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_J, Nk * Nk));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_slf, (size_t)R * 2 * (size_t)M * (size_t)Nk));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_smv, (size_t)R * (size_t)M));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_scur, (size_t)R * (size_t)M));
     } else if (sk) {
-        Q_TRY(hipMalloc(&ctx->q_Jb, sizeof(uint32_t) * Nk * ctx->q_Wk));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_Jb, Nk * ctx->q_Wk));
     } else if (spf) {
-        Q_TRY(hipMalloc(&ctx->d_A, sizeof(int32_t) * Nk * K));
-        Q_TRY(hipMalloc(&ctx->q_Jf, sizeof(double) * Nk * K));
-        Q_TRY(hipMalloc(&ctx->q_flf, sizeof(double) * (size_t)R * (size_t)M * (size_t)Nk));
-        Q_TRY(hipMalloc(&ctx->q_fundo, sizeof(double) * (size_t)R * (size_t)M * (size_t)(K + 1)));
-        Q_TRY(hipMalloc(&ctx->q_fml, sizeof(int32_t) * (size_t)R * (size_t)M));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_A, Nk * K));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_Jf, Nk * K));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_flf, (size_t)R * (size_t)M * (size_t)Nk));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_fundo, (size_t)R * (size_t)M * (size_t)(K + 1)));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_fml, (size_t)R * (size_t)M));
     } else if (pat) {
         // (patterns, labels and Stabilities are allocated by rrrmc_set_patterns / rrrmc_set_comm_patterns)
     } else {
-        Q_TRY(hipMalloc(&ctx->d_A, sizeof(int32_t) * Nk * K));
-        Q_TRY(hipMalloc(&ctx->d_J, sizeof(int8_t) * Nk * K));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_A, Nk * K));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_J, Nk * K));
     }
-    Q_TRY(hipMalloc(&ctx->q_spins, sizeof(uint32_t) * R * ctx->qW));
-    Q_TRY(hipMalloc(&ctx->q_cls, (size_t)R * N));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_spins, R * ctx->qW));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_cls, (size_t)R * N));
     {
         const size_t idx_bytes = N > 65535 ? sizeof(uint32_t) : sizeof(uint16_t);      // set members / positions: 32-bit beyond 65 535 spins
-        Q_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->q_sv), idx_bytes * R * 4 * N));
-        Q_TRY(hipMalloc(reinterpret_cast<void**>(&ctx->q_spos), idx_bytes * R * N));
+        CTX_CREATE_TRY(ctx, false, dev_alloc_bytes(ctx, ctx->q_sv, idx_bytes * R * 4 * N));
+        CTX_CREATE_TRY(ctx, false, dev_alloc_bytes(ctx, ctx->q_spos, idx_bytes * R * N));
     }
-    Q_TRY(hipMalloc(&ctx->q_st, sizeof(int32_t) * R * 4));
-    Q_TRY(hipMalloc(&ctx->q_T, sizeof(double) * R * 4));
-    Q_TRY(hipMalloc(&ctx->q_z, sizeof(double) * R));
-    Q_TRY(hipMalloc(&ctx->q_accrate, sizeof(double) * R));
-    Q_TRY(hipMalloc(&ctx->q_stats, sizeof(int64_t) * R * 3));          // 2 per replica for rrrMC, 3 for the continuous-energy samplers
-    Q_TRY(hipMalloc(&ctx->sk_E, sizeof(double) * R));
-    Q_TRY(hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
-#undef Q_TRY
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_st, R * 4));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_T, R * 4));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_z, R));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_accrate, R));
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_stats, R * 3));          // 2 per replica for rrrMC, 3 for the continuous-energy samplers
+    CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->sk_E, R));
+    CTX_CREATE_TRY(ctx, false, hipMemset(ctx->q_spins, 0, sizeof(uint32_t) * R * ctx->qW));
     *out = ctx;
     return RRRMC_OK;
 }
@@ -2165,12 +2129,7 @@ int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK,
     else S.samp0 = step;
     const int64_t nsamp = standard ? iters / step : smp_nsamp(ctx, iters, step);
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->R;
-    if (es_need > ctx->sk_Es_cap) {
-        free_dev(ctx->sk_Es);
-        ctx->sk_Es_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->sk_Es, sizeof(double) * es_need));
-        ctx->sk_Es_cap = es_need;
-    }
+    HIP_TRY(ctx, dev_grow(ctx, ctx->sk_Es, ctx->sk_Es_cap, es_need));
     while (ctx->ev_sweep.size() < 2) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
@@ -2611,13 +2570,13 @@ int32_t rrrmc_fetch_results_f64(rrrmc_ctx* ctx, double* Es_out, int64_t* accepte
     if (Es_out && ctx->nsamp > 0) {
         double* d_out = nullptr;
         const size_t bytes = sizeof(double) * (size_t)ctx->R * ctx->nsamp;
-        HIP_TRY(ctx, hipMalloc(&d_out, bytes));
+        HIP_TRY(ctx, dev_alloc_bytes(ctx, d_out, bytes));
         const dim3 grid((unsigned)((ctx->nsamp + 31) / 32), (unsigned)((ctx->Rpad + 31) / 32));
         hipLaunchKernelGGL(transpose_es_f64_kernel, grid, dim3(256), 0, ctx->stream, ctx->sk_Es, d_out, ctx->nsamp, (int)ctx->Rpad, (int)ctx->R);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(Es_out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_out);
+        dev_free(ctx, d_out);
         HIP_TRY(ctx, e);
     }
     return RRRMC_OK;
@@ -2668,15 +2627,12 @@ int32_t rrrmc_snapshot_reserve(rrrmc_ctx* ctx, int32_t nslots)
     if (nslots < 0) return fail(ctx, RRRMC_ERR_INVALID_ARG, "nslots must be >= 0");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    free_dev(ctx->snap);
+    dev_free(ctx, ctx->snap);
     ctx->snap_slots = 0;
     ctx->snap_valid.clear();
     if (nslots == 0) return RRRMC_OK;
     const size_t bytes = native_spin_bytes(ctx) * (size_t)nslots;
-    if (hipMalloc(&ctx->snap, bytes) != hipSuccess) {
-        ctx->snap = nullptr;
-        return fail(ctx, RRRMC_ERR_NOMEM, "cannot allocate %zu bytes for %d snapshots", bytes, nslots);
-    }
+    if (dev_alloc(ctx, ctx->snap, bytes) != hipSuccess) return fail(ctx, RRRMC_ERR_NOMEM, "cannot allocate %zu bytes for %d snapshots", bytes, nslots);
     ctx->snap_slots = nslots;
     ctx->snap_valid.assign((size_t)nslots, 0);
     return RRRMC_OK;
@@ -2741,10 +2697,10 @@ int32_t rrrmc_overlaps(rrrmc_ctx* ctx, int64_t npairs, const int32_t* slotA, con
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((size_t)npairs > ctx->pairs_cap) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        free_dev(ctx->d_pairs); free_dev(ctx->d_ovl);
+        dev_free(ctx, ctx->d_pairs); dev_free(ctx, ctx->d_ovl);
         ctx->pairs_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_pairs, sizeof(void*) * 2 * (size_t)npairs));
-        HIP_TRY(ctx, hipMalloc(&ctx->d_ovl, sizeof(int32_t) * (size_t)npairs * (size_t)ctx->Rpad));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->d_pairs, 2 * (size_t)npairs));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->d_ovl, (size_t)npairs * (size_t)ctx->Rpad));
         ctx->pairs_cap = (size_t)npairs;
     }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pairs, tab.data(), sizeof(void*) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -2785,7 +2741,7 @@ int32_t rrrmc_quant_observables(rrrmc_ctx* ctx, double beta, double Gamma, doubl
     const size_t lds = sizeof(uint32_t) * (size_t)(M * ((Nk + 31) / 32) + M + H + 1);
     if (lds > (size_t)64 * 1024) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "N = %lld spins per replica do not fit the observables kernel's LDS", (long long)N);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_qobs) HIP_TRY(ctx, hipMalloc(&ctx->d_qobs, sizeof(int32_t) * (size_t)R * (size_t)(1 + M + H)));
+    if (!ctx->d_qobs) HIP_TRY(ctx, dev_alloc(ctx, ctx->d_qobs, (size_t)R * (size_t)(1 + M + H)));
     int32_t* d_e0 = ctx->d_qobs;
     int32_t* d_es = d_e0 + R;
     int32_t* d_ov = d_es + R * M;
@@ -2959,7 +2915,7 @@ int32_t rrrmc_set_graph_levels(rrrmc_ctx* ctx, const int32_t* A, const int8_t* J
     HIP_TRY(ctx, hipMemcpy(ctx->d_A, A, sizeof(int32_t) * N * K, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->d_J, J, sizeof(int8_t) * N * K, hipMemcpyHostToDevice));
     // rrrMC / extremal_opt class arrays depend on L: drop those of a previous graph
-    free_dev(ctx->rp_cls); free_dev(ctx->rp_sv); free_dev(ctx->rp_spos);
+    dev_free(ctx, ctx->rp_cls); dev_free(ctx, ctx->rp_sv); dev_free(ctx, ctx->rp_spos);
     ctx->graph_set = true;
     return RRRMC_OK;
 }
@@ -3061,7 +3017,7 @@ int32_t rrrmc_set_graph_f64(rrrmc_ctx* ctx, const int32_t* A, const double* J)
             for (int64_t b = 0; b < a; ++b)
                 if (A[x * K + a] == A[x * K + b]) ctx->pf_multi_edge = true;
     if (ctx->pff_ready) {            // a new graph: the fast mode's tables are rebuilt on its next call
-        free_dev(ctx->pff_table); free_dev(ctx->pff_absJ); free_dev(ctx->pff_bond_off); free_dev(ctx->pff_thr_hi); free_dev(ctx->pff_thr_lo); free_dev(ctx->pff_flags);
+        dev_free(ctx, ctx->pff_table); dev_free(ctx, ctx->pff_absJ); dev_free(ctx, ctx->pff_bond_off); dev_free(ctx, ctx->pff_thr_hi); dev_free(ctx, ctx->pff_thr_lo); dev_free(ctx, ctx->pff_flags);
         ctx->pff_ready = false;
     }
     ctx->graph_set = true;
