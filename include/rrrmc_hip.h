@@ -208,6 +208,9 @@ RRRMC_API int32_t rrrmc_get_fields(rrrmc_ctx *ctx, int64_t *lfields_out);
  *   accepted_out  [R] accepted moves of this call.  May be NULL.
  * The configuration is resumed from the ctx and left updated (C0 is mutated in place, RRRMC.jl:93).
  * Synchronous: returns when the results are on the host.
+ * beta: any value but NaN (RRRMC_ERR_INVALID_ARG), as in the reference — except on RRRMC_MODEL_SPARSE_PM1, whose kernels (and
+ * rrrmc_colored_sweeps*) accept every move with dE <= 0 unconditionally: beta < 0, and an infinite beta on a graph of even degree (a move
+ * with dE = 0 has x = NaN there, rejected by the reference), are refused with RRRMC_ERR_UNSUPPORTED.
  */
 RRRMC_API int32_t rrrmc_standard_mc(rrrmc_ctx *ctx, double beta, int64_t iters, int64_t step,
                                     int64_t *Es_out, int64_t *accepted_out);

@@ -107,6 +107,8 @@ def _lib_locked():
         L.orc_gauss.argtypes = [C.c_uint64, C.c_uint64]
         L.orc_exp.restype = C.c_double
         L.orc_exp.argtypes = [C.c_double]
+        L.orc_log1p.restype = C.c_double
+        L.orc_log1p.argtypes = [C.c_double]
         L.orc_rand53_of.restype = C.c_double
         L.orc_rand53_of.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
         L.orc_gen_sk_gauss.argtypes = [C.c_int64, C.c_uint64, f64p]
@@ -281,6 +283,10 @@ def all_delta_e_pm1(K):
 # ---- dense Gaussian SK (GraphSKNormal) ------------------------------------------------------------
 def det_exp(x):
     return float(lib().orc_exp(x))
+
+
+def det_log1p(y):
+    return float(lib().orc_log1p(y))
 
 
 def rand53(seed, g, replica):

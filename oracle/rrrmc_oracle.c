@@ -406,6 +406,7 @@ static double gauss_draw(uint64_t seed, uint64_t n)
 
 ORC_API double orc_gauss(uint64_t seed, uint64_t n) { return gauss_draw(seed, n); }
 ORC_API double orc_exp(double x) { return orc_det_exp(x); }
+ORC_API double orc_log1p(double y) { return orc_det_log1p(y); }
 ORC_API double orc_rand53_of(uint64_t seed, uint64_t g, uint32_t replica) { return orc_rand53(seed, g, replica); }
 
 /* gen_J_gauss: SK.jl:170-179.  Row i = randn(N) scaled by 1/sqrt(N) (rmul!), then zero diagonal and the upper

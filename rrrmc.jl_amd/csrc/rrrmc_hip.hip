@@ -1280,6 +1280,22 @@ int32_t rrrmc_get_fields(rrrmc_ctx* ctx, int64_t* lfields_out)
     return RRRMC_OK;
 }
 
+namespace {
+// The +-J kernels (the LDS-resident sweep, the big-N random-site kernels, the colour-parallel sweeps) compare the ACCEPT stream with a
+// threshold for the classes with dE > 0 only and accept every class with dE <= 0 in their code.  That is accept(x) = x >= 0 || rand() < exp(x)
+// (RRRMC.jl:39, x = -beta dE) wherever beta >= 0 is finite; the reference's standardMC takes any beta, and there it differs: for beta < 0 a
+// move with dE < 0 has x < 0 (accepted with probability exp(x), never at -inf), and for an infinite beta a move with dE = 0 has x = NaN
+// (rejected).  Those calls are refused rather than answered with another chain.
+int32_t pm1_refuse_beta(rrrmc_ctx* ctx, double beta)
+{
+    if (beta < 0.0) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "beta = %g: the +-J kernels accept every move with dE <= 0, which is standardMC for beta >= 0 only", beta);
+    if (std::isinf(beta) && ctx->K % 2 == 0)
+        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "beta = %g on a graph of even degree K = %lld: a move with dE = 0 has x = -beta dE = NaN (rejected by the reference), the +-J kernels accept it",
+                    beta, (long long)ctx->K);
+    return RRRMC_OK;
+}
+}  // namespace
+
 int32_t rrrmc_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step)
 {
     RRRMC_MULTI(ctx, false, rrrmc_standard_mc_async(c, beta, iters, step));
@@ -1302,6 +1318,7 @@ int32_t rrrmc_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int6
     }
     if (ctx->model != RRRMC_MODEL_SPARSE_PM1) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "standardMC is not wired for this model on the device: use rrrmc_rrr_mc_async");
     if (!ctx->lds_mode && !ctx->big_mode) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "N=%lld is beyond the random-site kernels (N <= 2^20): use rrrmc_colored_sweeps_async", (long long)ctx->N);
+    if ((rc = pm1_refuse_beta(ctx, beta))) return rc;
     return pm1_standard_mc_async(ctx, beta, iters, step);
 }
 
@@ -1577,6 +1594,7 @@ int32_t rrrmc_colored_sweeps_async(rrrmc_ctx* ctx, double beta, int64_t sweeps, 
     if (sweeps < 0) return fail(ctx, RRRMC_ERR_INVALID_ARG, "sweeps must be >= 0, given %lld", (long long)sweeps);
     if (step < 1) return fail(ctx, RRRMC_ERR_INVALID_ARG, "step must be >= 1, given %lld", (long long)step);
     if (std::isnan(beta)) return fail(ctx, RRRMC_ERR_INVALID_ARG, "beta is NaN");
+    if ((rc = pm1_refuse_beta(ctx, beta))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->results_valid = false; ctx->last_call_wtm = false; ctx->last_call_eo = false;
     ctx->timing_valid = false;
