@@ -113,7 +113,28 @@ enum rrrmc_model {
     RRRMC_MODEL_TLE_EMPTY = 44,  /* Graph0TLE */
     RRRMC_MODEL_TLE_SK = 45,     /* GraphSKTLE */
     RRRMC_MODEL_TLE_SKN = 46,    /* GraphTopologicalLocalEntropy(Nk, M, gamma, lambda, beta, GraphSKNormal, J) */
-    RRRMC_MODEL_TLE_SAT = 47     /* GraphSATTLE */
+    RRRMC_MODEL_TLE_SAT = 47,    /* GraphSATTLE */
+    /* GraphAddFields / GraphAddSubFields (src/graphs/AddFields.jl) over one graph g: the models of contexts made by rrrmc_ctx_create_af,
+       and the selectors of rrrmc_ctx_create_multi for it (N; K = K2 for the committee machines, ignored otherwise; M ignored).
+       48 + s for GraphAddFields and 57 + s for GraphAddSubFields, s numbering the nine kinds of g in the order of rrrmc_re_slice. */
+    RRRMC_MODEL_AF_EMPTY = 48,        /* GraphAddFields(h, GraphEmpty(N)) */
+    RRRMC_MODEL_AF_SK = 49,           /* GraphAddFields(h, GraphSK(J)) */
+    RRRMC_MODEL_AF_SKN = 50,          /* GraphAddFields(h, GraphSKNormal(J)) */
+    RRRMC_MODEL_AF_PERC_STEP = 51,    /* GraphAddFields(h, GraphPercStep) */
+    RRRMC_MODEL_AF_PERC_LINEAR = 52,  /* GraphAddFields(h, GraphPercLinear) */
+    RRRMC_MODEL_AF_COMM_STEP = 53,    /* GraphAddFields(h, GraphCommStep) */
+    RRRMC_MODEL_AF_COMM_RELU = 54,    /* GraphAddFields(h, GraphCommReLU) */
+    RRRMC_MODEL_AF_SAT = 55,          /* GraphAddFields(h, GraphSAT) */
+    RRRMC_MODEL_AF_COMM_QU = 56,      /* GraphAddFields(h, GraphCommQu) */
+    RRRMC_MODEL_ASF_EMPTY = 57,       /* GraphAddSubFields(h, GraphEmpty(N)) */
+    RRRMC_MODEL_ASF_SK = 58,          /* GraphAddSubFields(h, GraphSK(J)) */
+    RRRMC_MODEL_ASF_SKN = 59,         /* GraphAddSubFields(h, GraphSKNormal(J)) */
+    RRRMC_MODEL_ASF_PERC_STEP = 60,   /* GraphAddSubFields(h, GraphPercStep) */
+    RRRMC_MODEL_ASF_PERC_LINEAR = 61, /* GraphAddSubFields(h, GraphPercLinear) */
+    RRRMC_MODEL_ASF_COMM_STEP = 62,   /* GraphAddSubFields(h, GraphCommStep) */
+    RRRMC_MODEL_ASF_COMM_RELU = 63,   /* GraphAddSubFields(h, GraphCommReLU) */
+    RRRMC_MODEL_ASF_SAT = 64,         /* GraphAddSubFields(h, GraphSAT) */
+    RRRMC_MODEL_ASF_COMM_QU = 65      /* GraphAddSubFields(h, GraphCommQu) */
 };
 
 /* slice families of rrrmc_ctx_create_re */
@@ -173,7 +194,8 @@ RRRMC_API int32_t rrrmc_ctx_create(rrrmc_ctx **out, int32_t model, int64_t N, in
  *          RRRMC_MODEL_RE_EMPTY / _SK / _SKN take (N = Nk, M) as rrrmc_ctx_create_re does (K ignored), RRRMC_MODEL_LE_EMPTY / _SK / _SKN
  *          take (N = Nk, M) as rrrmc_ctx_create_le does (K ignored), and so do RRRMC_MODEL_RE_PERC_* / RRRMC_MODEL_LE_PERC_* and
  *          RRRMC_MODEL_RE_COMM_* / RRRMC_MODEL_LE_COMM_*; RRRMC_MODEL_COMM_STEP / _RELU / _QU take (N = K1*K2, K = K2) as rrrmc_ctx_create_comm / _comm_qu do;
- *          RRRMC_MODEL_PERC_STEP / _LINEAR take N as rrrmc_ctx_create_perc does; M is ignored otherwise.
+ *          RRRMC_MODEL_PERC_STEP / _LINEAR take N as rrrmc_ctx_create_perc does; RRRMC_MODEL_AF_* / RRRMC_MODEL_ASF_* take (N, K = K2) as
+ *          rrrmc_ctx_create_af does; M is ignored otherwise.
  */
 RRRMC_API int32_t rrrmc_ctx_create_multi(rrrmc_ctx **out, int32_t model, int64_t N, int64_t K, int64_t M, int64_t R,
                                          const int32_t *device_ids, int32_t ndev, uint32_t replica0);
@@ -481,6 +503,38 @@ RRRMC_API int32_t rrrmc_tle_cache(rrrmc_ctx *ctx, int32_t *pos_out, int32_t *siz
 /* The kernel build of the last rrrMC call: 0 none yet, 1 the chain's hot state in LDS (chosen when it fits and all R wavefronts are
  * resident at once), 2 in global memory.  RRRMC_TLE_NO_LDS=1 forces 2, RRRMC_TLE_LDS=1 forces 1 whenever the state fits. */
 RRRMC_API int32_t rrrmc_tle_build(rrrmc_ctx *ctx, int32_t *build_out);
+
+/* ---- GraphAddFields / GraphAddSubFields (src/graphs/AddFields.jl; RRRMC_MODEL_AF_*, RRRMC_MODEL_ASF_*) ------------
+ * A DoubleGraph whose inner graph X0 = GraphAF(h) is a set of N independent external fields (energy(X0) = sum_i h_i sigma_i, left to
+ * right; delta_energy(X0, i) = -2 sigma_i h_i; neighbors(X0, i) = ()) over any graph g of N spins:
+ *   GraphAddFields    (sub = 0): E = energy(X0) + energy(g), DeltaE = DeltaE(X0) + DeltaE(g), residual = DeltaE(g);
+ *   GraphAddSubFields (sub = 1): E = energy(g),              DeltaE = DeltaE(g),              residual = DeltaE(g) - DeltaE(X0):
+ *     the fields only shape the proposals of rrrMC, the stationary law is g's own.
+ * rrrMC(X::DoubleGraph) runs over DeltaECacheCont + DynamicSampler on X0 (src/DeltaE.jl:297-410, src/DynamicSamplers.jl): X0 has no
+ * neighbours, so a move is one setindex!, O(log N) whatever g is.  Integer energies of g enter as exact Float64s; results through
+ * rrrmc_fetch_results_f64.
+ *   g, by its rrrmc_re_slice kind and with that kind's own upload call and limits: GraphEmpty (nothing to upload), binary GraphSK
+ *   (rrrmc_set_couplings_bits), GraphSKNormal (rrrmc_set_couplings_dense), GraphPercStep / GraphPercLinear (rrrmc_set_patterns; N odd,
+ *   N <= 32 767), GraphCommStep / GraphCommReLU / GraphCommQu (rrrmc_set_comm_patterns with the creator's K2; N = K1*K2 with each kind's
+ *   parities, N <= 32 767), GraphSAT (rrrmc_set_clauses; N <= 65 535).  N <= 65 535 for the first three.  N = 1 runs (a tree of no levels).
+ *   K2 is read for the committee machines only.
+ * rrrmc_ctx_create_af, then g's upload, then rrrmc_af_set_fields.  Samplers: rrrmc_rrr_mc_async (fourK ignored; staged_thr = 0.5 is the
+ * reference's default for a DoubleGraph) and rrrmc_standard_mc_async / rrrmc_standard_mc_f64 (the common SITE / ACCEPT_F64 streams), with
+ * the resume, debug-check, timing, results, rrrmc_rrr_stats, rrrmc_energy_f64, rrrmc_tracked_energy_f64, spin, snapshot and overlap entry
+ * points of the other models.  rrrmc_bkl_mc_async, rrrmc_wtm_mc_async and rrrmc_extremal_opt_async return RRRMC_ERR_UNSUPPORTED.
+ * A draw of the sampler that lands on an element of weight 0 (or beyond N) refreshes the tree once; if that happens with nothing to
+ * refresh, the reference's "Unrecoverable loss of precision detected in the dynamic sampler" is reported by the next rrrmc_sync / fetch
+ * (RRRMC_ERR_STATE). */
+RRRMC_API int32_t rrrmc_ctx_create_af(rrrmc_ctx **out, int32_t slice_kind, int32_t sub, int64_t N, int64_t K2, int64_t R, int32_t device,
+                                      uint32_t replica0);
+/* The fields h[N] (the same for every replica).  Non-finite entries: RRRMC_ERR_INVALID_ARG.  New fields end a resumed run. */
+RRRMC_API int32_t rrrmc_af_set_fields(rrrmc_ctx *ctx, const double *h);
+/* The kernel build of the last rrrMC call: 0 none yet, 1 the sampler's tree, DeltaEs, the spins and g's per-chain state in LDS (chosen
+ * whenever they fit 160 KiB), 2 in global memory.  RRRMC_AF_NO_LDS=1 forces 2.  Both builds give the same bits. */
+RRRMC_API int32_t rrrmc_af_build(rrrmc_ctx *ctx, int32_t *build_out);
+/* The DeltaECacheCont after the last rrrMC call: dEs_out[R * N] = DeltaEs, v_out[R * N] the sampler's weights, z_out[R], trefresh_out[R]
+ * (any may be NULL). */
+RRRMC_API int32_t rrrmc_af_cache(rrrmc_ctx *ctx, double *dEs_out, double *v_out, double *z_out, int64_t *trefresh_out);
 
 /* rrrMC(X::DoubleGraph, beta, iters; step, staged_thr, staged_thr_fact) (src/RRRMC.jl:221-290) for all R replicas.
  *   fourK = round(2/beta * log(coth(beta * Gamma / M)), digits = 8)  (QT.jl:165) is computed by the caller.

@@ -279,6 +279,51 @@ function Ctx(X::RRRMC.RE.GraphRobustEnsemble{M,γ,β,G}, R::Integer; device = 0,
     return ctx
 end
 
+# ---- GraphAddFields / GraphAddSubFields (src/graphs/AddFields.jl:58-123): external fields over one graph g ------------------------------
+# rrrMC(X::DoubleGraph) through the DynamicSampler of the inner GraphAF (one setindex! per move, whatever g is) and standardMC; bklMC /
+# wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED.  g is any graph the ensembles take as a slice; sparse graphs, GraphQuant and the
+# ensembles themselves are refused by ens_kind.  Integer energies of g arrive as exact Float64s.  (Checked statically only, as the rest of
+# this file.)
+const AddFieldsGraph = Union{RRRMC.AddFields.GraphAddFields,RRRMC.AddFields.GraphAddSubFields}
+const AF_MODELS = (48, 49, 50, 51, 52, 53, 54, 0, 55, 56)          # RRRMC_MODEL_AF_* by the kind of g; GraphAddSubFields: + 9
+function Ctx(X::AddFieldsGraph, R::Integer; device = 0, replica0 = 0, devices = nothing)
+    sub = X isa RRRMC.AddFields.GraphAddSubFields
+    g = X.X1
+    kind = ens_kind(typeof(g), sub ? "GraphAddSubFields" : "GraphAddFields")
+    K2 = g isa CommGraph ? g.K2 : 0
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    if devices === nothing
+        check(ccall((:rrrmc_ctx_create_af, LIB), Int32, (Ref{Ptr{Cvoid}}, Int32, Int32, Int64, Int64, Int64, Int32, UInt32), ref, kind, sub ? 1 : 0, X.N, K2, R, device, replica0))
+    else
+        ref[] = create(AF_MODELS[kind + 1] + (sub ? 9 : 0), X.N, K2, 0, R; replica0 = replica0, devices = devices)
+    end
+    ctx = Ctx(ref[], R, X.N, true)
+    if kind == 1
+        Jc = sk_bits(g.J)
+        GC.@preserve Jc check(ccall((:rrrmc_set_couplings_bits, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt64}), ctx.p, Jc), ctx.p)
+    elseif kind == 2
+        Jm = Matrix{Float64}(undef, X.N, X.N); for i = 1:X.N; Jm[:, i] = g.J[i]; end
+        GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
+    end
+    kind >= 3 && set_patterns!(ctx, g)
+    h = Vector{Float64}(X.X0.fields)
+    GC.@preserve h check(ccall((:rrrmc_af_set_fields, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, h), ctx.p)
+    return ctx
+end
+# which kernel ran the last rrrMC call on a GraphAddFields / GraphAddSubFields: 0 none yet, 1 the chain's state in LDS, 2 in global memory
+function af_build(ctx::Ctx)
+    b = Ref{Int32}(0)
+    check(ccall((:rrrmc_af_build, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), ctx.p, b), ctx.p)
+    return Int(b[])
+end
+# the DeltaECacheCont after the last rrrMC call: (ΔEs[N, R], v[N, R], z[R], trefresh[R]); column r = replica r
+function af_cache(ctx::Ctx)
+    dEs = Matrix{Float64}(undef, ctx.N, ctx.R); v = Matrix{Float64}(undef, ctx.N, ctx.R)
+    z = Vector{Float64}(undef, ctx.R); t = Vector{Int64}(undef, ctx.R)
+    check(ccall((:rrrmc_af_cache, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}), ctx.p, dEs, v, z, t), ctx.p)
+    return dEs, v, z, t
+end
+
 # ---- GraphPercStep / GraphPercLinear (src/graphs/PercStep.jl, PercLinear.jl), stand-alone: standardMC only ------------------------------
 # (rrrMC / bklMC / wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED).  GraphPercStep's integer energies arrive as exact Float64s.
 function Ctx(X::PercGraph, R::Integer; device = 0, replica0 = 0, devices = nothing)

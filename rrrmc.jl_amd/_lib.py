@@ -41,6 +41,7 @@ SYMBOLS = [
     "rrrmc_ctx_create_quant_pattern", "rrrmc_quant_renergies", "rrrmc_quant_pattern_build",
     "rrrmc_ctx_create_sat", "rrrmc_set_clauses", "rrrmc_sat_build", "rrrmc_sweep_build", "rrrmc_gen_ksat", "rrrmc_check_clauses",
     "rrrmc_ctx_create_tle", "rrrmc_tle_set_topology", "rrrmc_tle_check_topology", "rrrmc_tle_set_params", "rrrmc_tle_tables", "rrrmc_tle_cache", "rrrmc_tle_build",
+    "rrrmc_ctx_create_af", "rrrmc_af_set_fields", "rrrmc_af_build", "rrrmc_af_cache",
 ]
 
 
@@ -293,6 +294,14 @@ def lib():
     L.rrrmc_tle_cache.argtypes = [vp, vp, vp]
     L.rrrmc_tle_build.restype = C.c_int32
     L.rrrmc_tle_build.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.rrrmc_ctx_create_af.restype = C.c_int32
+    L.rrrmc_ctx_create_af.argtypes = [C.POINTER(vp), C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_uint32]
+    L.rrrmc_af_set_fields.restype = C.c_int32
+    L.rrrmc_af_set_fields.argtypes = [vp, f64p]
+    L.rrrmc_af_build.restype = C.c_int32
+    L.rrrmc_af_build.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.rrrmc_af_cache.restype = C.c_int32
+    L.rrrmc_af_cache.argtypes = [vp, vp, vp, vp, vp]
     _lib = L
     return L
 

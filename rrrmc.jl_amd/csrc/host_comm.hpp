@@ -3,19 +3,19 @@
 // and the pattern matrix, labels and Stabilities that the Robust Ensemble and Local Entropy contexts with committee slices share with them.
 // Included by rrrmc_hip.hip inside its anonymous namespace, before host_re.hpp; not a stand-alone translation unit.
 inline bool is_comm(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_COMM_STEP || ctx->model == RRRMC_MODEL_COMM_RELU || ctx->model == RRRMC_MODEL_COMM_QU; }
-inline bool comm_slices(const rrrmc_ctx* ctx)          // an ensemble over committee machine slices (ens_models.hpp)
+inline bool comm_slices(const rrrmc_ctx* ctx)          // an ensemble over committee machine slices (ens_models.hpp), or a field wrapper over a committee machine (af_models.hpp)
 {
-    const int32_t s = ens_slice(ctx->model);
+    const int32_t s = model_slice(ctx->model);
     return s == RRRMC_RE_SLICE_COMM_STEP || s == RRRMC_RE_SLICE_COMM_RELU || s == RRRMC_RE_SLICE_COMM_QU;
 }
 inline bool comm_relu(const rrrmc_ctx* ctx)
 {
-    return ctx->model == RRRMC_MODEL_COMM_RELU || ens_slice(ctx->model) == RRRMC_RE_SLICE_COMM_RELU ||
+    return ctx->model == RRRMC_MODEL_COMM_RELU || model_slice(ctx->model) == RRRMC_RE_SLICE_COMM_RELU ||
            (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_pat == RRRMC_RE_SLICE_COMM_RELU);
 }
 inline bool comm_qu(const rrrmc_ctx* ctx)
 {
-    return ctx->model == RRRMC_MODEL_COMM_QU || ens_slice(ctx->model) == RRRMC_RE_SLICE_COMM_QU ||
+    return ctx->model == RRRMC_MODEL_COMM_QU || model_slice(ctx->model) == RRRMC_RE_SLICE_COMM_QU ||
            (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_pat == RRRMC_RE_SLICE_COMM_QU);
 }
 // GraphCommReLU and GraphCommQu: K1, K2 even, labelled patterns
@@ -62,7 +62,7 @@ int32_t comm_set_patterns(rrrmc_ctx* ctx, int64_t K2, const uint64_t* xi, const 
     if (relu && !y) return fail(ctx, RRRMC_ERR_INVALID_ARG, "a %s needs the labels y", qu ? "GraphCommQu" : "GraphCommReLU");
     if (!relu && y) return fail(ctx, RRRMC_ERR_INVALID_ARG, "a GraphCommStep has no labels: y must be NULL");
     if (K2 < 1 || N % K2 != 0) return fail(ctx, RRRMC_ERR_INVALID_ARG, "N = %lld is not a multiple of K2 = %lld", (long long)N, (long long)K2);
-    if ((is_comm(ctx) || ctx->model == RRRMC_MODEL_QUANT_RRG) && K2 != ctx->cm_K2)
+    if ((is_comm(ctx) || ctx->model == RRRMC_MODEL_QUANT_RRG || af_family(ctx->model) != AF_NONE) && K2 != ctx->cm_K2)
         return fail(ctx, RRRMC_ERR_INVALID_ARG, "K2 = %lld, but the context was made with K2 = %lld", (long long)K2, (long long)ctx->cm_K2);
     { const int32_t rck = comm_check_k(ctx, N / K2, K2, relu); if (rck) return rck; }
     if (P < 1) return fail(ctx, RRRMC_ERR_INVALID_ARG, "P must be >= 1, given: %lld", (long long)P);

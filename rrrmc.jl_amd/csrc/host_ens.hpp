@@ -59,11 +59,12 @@ struct EnsCall {
     int64_t nsamp;
     bool cont;          // the call continues the live run: no *_run_init
 };
-// the argument checks, the run's state, room for the samples, the events; ends with ev_begin on the stream
-int32_t ens_call_begin(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact, EnsCall* C)
+// the argument checks, the run's state, room for the samples, the events; ends with ev_begin on the stream.  ensemble = false: the caller is no
+// ensemble (host_af.hpp) and has checked what its own graph needs
+int32_t ens_call_begin(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact, EnsCall* C, bool ensemble = true)
 {
     int32_t rc = RRRMC_OK;
-    if (!ctx->re_params_set) return ens_needs_params(ctx, true);
+    if (ensemble && !ctx->re_params_set) return ens_needs_params(ctx, true);
     if (iters < 0) return fail(ctx, RRRMC_ERR_INVALID_ARG, "iters must be >= 0, given %lld", (long long)iters);
     if (step < 1) return fail(ctx, RRRMC_ERR_INVALID_ARG, "step must be >= 1, given %lld", (long long)step);
     HIP_TRY(ctx, hipSetDevice(ctx->device));

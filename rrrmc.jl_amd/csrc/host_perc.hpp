@@ -2,9 +2,9 @@
 // pattern matrix and Stabilities that the Robust Ensemble and Local Entropy contexts with perceptron slices share with them.
 // Included by rrrmc_hip.hip inside its anonymous namespace, before host_re.hpp; not a stand-alone translation unit.
 inline bool is_perc(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_PERC_STEP || ctx->model == RRRMC_MODEL_PERC_LINEAR; }
-inline bool perc_slices(const rrrmc_ctx* ctx)          // an ensemble over perceptron slices (ens_models.hpp)
+inline bool perc_slices(const rrrmc_ctx* ctx)          // an ensemble over perceptron slices (ens_models.hpp), or a field wrapper over a perceptron (af_models.hpp)
 {
-    return ens_slice(ctx->model) == RRRMC_RE_SLICE_PERC_STEP || ens_slice(ctx->model) == RRRMC_RE_SLICE_PERC_LINEAR;
+    return model_slice(ctx->model) == RRRMC_RE_SLICE_PERC_STEP || model_slice(ctx->model) == RRRMC_RE_SLICE_PERC_LINEAR;
 }
 
 // GraphPercStep(ξ, ξv): isodd(N) || throw(ArgumentError) (PercStep.jl:57); the kernels' bound on N

@@ -64,7 +64,7 @@ inline int sat_build_program(int64_t N, int64_t Mc, int64_t Kmax, const int32_t*
 
 #ifndef RRRMC_SAT_HOST_CORE_ONLY
 inline bool is_sat(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_SAT; }
-inline bool sat_slices(const rrrmc_ctx* ctx) { return ens_slice(ctx->model) == RRRMC_RE_SLICE_SAT; }          // an ensemble over K-SAT slices (ens_models.hpp)
+inline bool sat_slices(const rrrmc_ctx* ctx) { return model_slice(ctx->model) == RRRMC_RE_SLICE_SAT; }          // an ensemble over K-SAT slices (ens_models.hpp), or a field wrapper over a GraphSAT (af_models.hpp)
 
 inline SatTable sat_table(const rrrmc_ctx* ctx)
 {

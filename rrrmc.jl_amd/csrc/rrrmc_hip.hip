@@ -22,6 +22,7 @@
 typedef hipError_t dev_err_t;
 #include "dev_mem.hpp"
 #include "ens_models.hpp"
+#include "af_models.hpp"
 #include "sk_kernels.hpp"
 #include "sk_block_kernel.hpp"
 #include "sk_hblock_kernel.hpp"
@@ -45,6 +46,7 @@ typedef hipError_t dev_err_t;
 #include "re_kernels.hpp"
 #include "le_kernels.hpp"
 #include "tle_kernels.hpp"
+#include "af_kernels.hpp"
 
 using namespace rrrmc;
 
@@ -303,6 +305,18 @@ struct rrrmc_ctx {
     double tle_lT = 0.0;           // λT = λ / β (TLE.jl:390-396)
     bool tle_topology_set = false;
     int tle_build = 0;             // the build of the last rrrMC call: 1 hot state in LDS, 2 in global memory; 0 none yet
+    // ---- GraphAddFields / GraphAddSubFields (af_models.hpp; host_af.hpp): g is one slice (qM = 1, qNk = N) in the buffers its kind has
+    //      above, spins in q_spins, z in q_z, acc_rate in q_accrate, E in sk_E, counts in q_stats ----
+    double* af_h = nullptr;        // [N] the fields
+    double* af_dEs = nullptr;      // [R][N] DeltaECacheCont.ΔEs
+    double* af_v = nullptr;        // [R][N2] the DynamicSampler's weights
+    double* af_ps = nullptr;       // [R][N2] its partial-sum tree, heap order
+    long long* af_tref = nullptr;  // [R] its trefresh
+    int32_t* af_status = nullptr;  // [2] chains that lost precision in an rrrMC call since the last sync, one of them (zeroed by the sync that reports it)
+    int af_levs = 0;
+    int64_t af_N2 = 0;
+    bool af_fields_set = false;
+    int af_build = 0;              // the build of the last rrrMC call: 1 LDS, 2 global memory; 0 none yet
     // ---- the binary perceptron (RRRMC_MODEL_PERC_*, and the perceptron slices of the ensembles; host_perc.hpp): spins in q_spins,
     //      E in sk_E, counts in q_stats ----
     uint64_t* pc_col = nullptr;    // [Nk][PW] patterns, one column per synapse
@@ -550,7 +564,7 @@ hipError_t raise_lds_attr(const void* fn, size_t bytes)
 inline bool chunk_layout(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_QUANT_RRG || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_SPARSE_LEVELS ||
                                                        ctx->model == RRRMC_MODEL_PERC_STEP || ctx->model == RRRMC_MODEL_PERC_LINEAR ||
                                                        ctx->model == RRRMC_MODEL_COMM_STEP || ctx->model == RRRMC_MODEL_COMM_RELU || ctx->model == RRRMC_MODEL_COMM_QU ||
-                                                       ctx->model == RRRMC_MODEL_SAT || ens_family(ctx->model) != ENS_NONE; }
+                                                       ctx->model == RRRMC_MODEL_SAT || ens_family(ctx->model) != ENS_NONE || af_family(ctx->model) != AF_NONE; }
 inline bool sparse_int_model(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_SPARSE_PM1 || ctx->model == RRRMC_MODEL_SPARSE_LEVELS; }
 inline double lv_to_f64(const rrrmc_ctx* ctx, long long units) { return (double)(units * ctx->lv_mul) / ctx->lv_div; }
 
@@ -701,6 +715,7 @@ inline void smp_commit(rrrmc_ctx* ctx, int kind, int64_t n) { ctx->smp_kind = ki
 #include "host_re.hpp"
 #include "host_le.hpp"
 #include "host_tle.hpp"
+#include "host_af.hpp"
 int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact);
 
 }  // namespace
@@ -771,6 +786,15 @@ int32_t post_sync_checks(rrrmc_ctx* ctx)
             ctx->results_valid = false; ctx->std_cache_live = false; ctx->pf_lf_live = false;
             return fail(ctx, RRRMC_ERR_STATE, "spf_team_kernel: a wait on the retired prefix ran into its limit (protocol failure); the call's results are void. "
                                               "RRRMC_SPF_TEAM=0 selects the single-wavefront kernel");
+        }
+    }
+    if (ctx->last_call_rrr && is_af(ctx) && ctx->q_cache_valid) {
+        int32_t st[2] = {0, 0};
+        HIP_TRY(ctx, hipMemcpy(st, ctx->af_status, sizeof st, hipMemcpyDeviceToHost));
+        if (st[0]) {
+            HIP_TRY(ctx, hipMemset(ctx->af_status, 0, sizeof st));
+            ctx->results_valid = false; ctx->q_cache_valid = false; smp_drop(ctx);
+            return fail(ctx, RRRMC_ERR_STATE, "replica %d (of %d): Unrecoverable loss of precision detected in the dynamic sampler", st[1], st[0]);   // DynamicSamplers.jl:147
         }
     }
     if (ctx->last_call_rrr && (ctx->model == RRRMC_MODEL_SK_NORMAL || ctx->model == RRRMC_MODEL_SPARSE_F64) && ctx->rs_status) {
@@ -1309,6 +1333,7 @@ int32_t rrrmc_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int6
     if (is_perc(ctx)) return perc_mc_async(ctx, beta, iters, step);
     if (is_comm(ctx)) return comm_mc_async(ctx, beta, iters, step);
     if (is_sat(ctx)) return sat_mc_async(ctx, beta, iters, step);
+    if (is_af(ctx)) return af_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (is_re(ctx)) return re_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (is_tle(ctx)) return tle_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (is_le(ctx)) return le_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
@@ -1345,8 +1370,8 @@ int32_t rrrmc_set_debug_checks(rrrmc_ctx* ctx, int32_t on)
 {
     RRRMC_MULTI(ctx, false, rrrmc_set_debug_checks(c, on));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_tle(ctx) && !is_perc(ctx) && !is_comm(ctx) && !quant_pat(ctx) && !is_sat(ctx))
-        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy, the perceptron, the committee machine and the K-SAT graphs, and GraphQuant over perceptrons and committee machines");
+    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_tle(ctx) && !is_af(ctx) && !is_perc(ctx) && !is_comm(ctx) && !quant_pat(ctx) && !is_sat(ctx))
+        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy, the GraphTopologicalLocalEntropy, GraphAddFields / GraphAddSubFields, the perceptron, the committee machine and the K-SAT graphs, and GraphQuant over perceptrons and committee machines");
     ctx->debug_checks = on != 0;
     return RRRMC_OK;
 }
@@ -2011,6 +2036,51 @@ int32_t rrrmc_tle_build(rrrmc_ctx* ctx, int32_t* build_out)
     return RRRMC_OK;
 }
 
+// ---- GraphAddFields / GraphAddSubFields: exported entry points (host_af.hpp) ----
+int32_t rrrmc_ctx_create_af(rrrmc_ctx** out, int32_t slice_kind, int32_t sub, int64_t N, int64_t K2, int64_t R, int32_t device, uint32_t replica0)
+{
+    return af_ctx_create(out, slice_kind, sub, N, K2, R, device, replica0);
+}
+
+int32_t rrrmc_af_set_fields(rrrmc_ctx* ctx, const double* h)
+{
+    RRRMC_MULTI(ctx, false, rrrmc_af_set_fields(c, h));
+    smp_drop(ctx);
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!is_af(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_af_set_fields is for contexts made by rrrmc_ctx_create_af (GraphAddFields, GraphAddSubFields)");
+    return af_set_fields(ctx, h);
+}
+
+int32_t rrrmc_af_build(rrrmc_ctx* ctx, int32_t* build_out)
+{
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (is_multi(ctx)) return rrrmc_af_build(ctx->kids[0], build_out);
+    if (!is_af(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_af_build is for contexts made by rrrmc_ctx_create_af (GraphAddFields, GraphAddSubFields)");
+    if (!build_out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "build_out is NULL");
+    *build_out = ctx->af_build;
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_af_cache(rrrmc_ctx* ctx, double* dEs_out, double* v_out, double* z_out, int64_t* trefresh_out)
+{
+    RRRMC_MULTI(ctx, true, rrrmc_af_cache(c, at_row(dEs_out, r0 * ctx->N), at_row(v_out, r0 * ctx->N), at_row(z_out, r0), at_row(trefresh_out, r0)));
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!is_af(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_af_cache is for contexts made by rrrmc_ctx_create_af (GraphAddFields, GraphAddSubFields)");
+    if (!ctx->results_valid || !ctx->last_call_rrr || !ctx->q_cache_valid) return fail(ctx, RRRMC_ERR_STATE, "no rrrMC call has been made");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t R = (size_t)ctx->R, N = (size_t)ctx->N;
+    if (dEs_out) HIP_TRY(ctx, hipMemcpy(dEs_out, ctx->af_dEs, sizeof(double) * R * N, hipMemcpyDeviceToHost));
+    if (v_out) HIP_TRY(ctx, hipMemcpy2D(v_out, sizeof(double) * N, ctx->af_v, sizeof(double) * (size_t)ctx->af_N2, sizeof(double) * N, R, hipMemcpyDeviceToHost));
+    if (z_out) HIP_TRY(ctx, hipMemcpy(z_out, ctx->q_z, sizeof(double) * R, hipMemcpyDeviceToHost));
+    if (trefresh_out) {
+        std::vector<long long> t(R);
+        HIP_TRY(ctx, hipMemcpy(t.data(), ctx->af_tref, sizeof(long long) * R, hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < R; ++r) trefresh_out[r] = (int64_t)t[r];
+    }
+    return RRRMC_OK;
+}
+
 // One context over several devices: the reference's user makes ONE call from ONE process (src/RRRMC.jl:81-88).
 // Replicas never interact, so the context is a list of per-device contexts over shards of whole 32-replica groups in global-id
 // order (the random streams are addressed by global replica id: the results do not depend on ndev); every entry point forwards
@@ -2033,6 +2103,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     const bool quant = model == RRRMC_MODEL_QUANT_RRG || model == RRRMC_MODEL_QUANT_SK || model == RRRMC_MODEL_QUANT_SKN || model == RRRMC_MODEL_QUANT_F64 || qpat;
     const bool re = ens_family(model) == ENS_RE, le = ens_family(model) == ENS_LE, tle = ens_family(model) == ENS_TLE;
     const bool sat = model == RRRMC_MODEL_SAT;
+    const bool af = af_family(model) != AF_NONE;
     const bool pc = model == RRRMC_MODEL_PERC_STEP || model == RRRMC_MODEL_PERC_LINEAR;
     const bool cm = model == RRRMC_MODEL_COMM_STEP || model == RRRMC_MODEL_COMM_RELU || model == RRRMC_MODEL_COMM_QU;
     if (cm && (K < 1 || N % K != 0)) {
@@ -2044,6 +2115,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     if (re || le || tle) { ctx->qNk = N; ctx->qM = M; }
     if (pc || sat) { ctx->qNk = N; ctx->qM = 1; }
     if (cm) { ctx->qNk = N; ctx->qM = 1; ctx->cm_K2 = K; ctx->K = 0; }
+    if (af) { ctx->qNk = N; ctx->qM = 1; ctx->K = 0; }
     if (quant) { ctx->qNk = N; ctx->qM = M; ctx->q_sk = model == RRRMC_MODEL_QUANT_SK; ctx->q_skn = model == RRRMC_MODEL_QUANT_SKN; ctx->q_spf = model == RRRMC_MODEL_QUANT_F64; ctx->q_pat = qpat; }
     if (qpat >= RRRMC_RE_SLICE_COMM_STEP) { ctx->cm_K2 = K; ctx->K = 0; }
     for (int32_t d = 0; d < ndev; ++d) {
@@ -2059,6 +2131,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : re ? rrrmc_ctx_create_re(&c, N, M, ens_slice(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : le ? rrrmc_ctx_create_le(&c, N, M, ens_slice(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : tle ? rrrmc_ctx_create_tle(&c, N, M, ens_slice(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : af ? rrrmc_ctx_create_af(&c, af_slice(model), af_family(model) == AF_ADDSUB, N, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : pc ? rrrmc_ctx_create_perc(&c, N, model == RRRMC_MODEL_PERC_LINEAR, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : sat ? rrrmc_ctx_create_sat(&c, N, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_COMM_QU ? rrrmc_ctx_create_comm_qu(&c, N / K, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
@@ -2262,6 +2335,7 @@ int32_t rrrmc_rrr_mc_async(rrrmc_ctx* ctx, double beta, double fourK, int64_t it
     if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone perceptron graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone committee machine graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone GraphSAT (a DeltaECache of max_conn + 1 levels over variable-degree neighbourhoods): standardMC is, and rrrMC on GraphSATRE / GraphSATLE");
+    if (is_af(ctx)) return af_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (is_re(ctx)) return re_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (is_tle(ctx)) return tle_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (is_le(ctx)) return le_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
@@ -2280,6 +2354,7 @@ int32_t rrrmc_bkl_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t s
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone GraphSAT (standardMC is)");
     if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "bklMC");
+    if (is_af(ctx)) return af_not_wired(ctx, "bklMC");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for a GraphQuant over pattern machines (DeltaECacheCont over AllButOne neighbourhoods): rrrMC and standardMC are");
     if (!std::isfinite(beta)) return fail(ctx, RRRMC_ERR_INVALID_ARG, "beta must be finite, given: %g", beta);
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
@@ -2322,6 +2397,7 @@ int32_t rrrmc_wtm_mc_async(rrrmc_ctx* ctx, double beta, int64_t samples, double 
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone GraphSAT (standardMC is)");
     if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "wtmMC");
+    if (is_af(ctx)) return af_not_wired(ctx, "wtmMC");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for a GraphQuant over pattern machines (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)
         return spf_cont_async(ctx, 2, beta, samples, 1, step, 0.0, 5.0);
@@ -2352,6 +2428,7 @@ int32_t rrrmc_extremal_opt_async(rrrmc_ctx* ctx, const double* ftau, int64_t ite
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone GraphSAT (standardMC is)");
     if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "extremal_opt");
+    if (is_af(ctx)) return af_not_wired(ctx, "extremal_opt");
     if (quant_pat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for a GraphQuant over pattern machines (rrrMC and standardMC are)");
     if (ctx->model == RRRMC_MODEL_SPARSE_F64 || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_QUANT_RRG)        // not DiscrGraphs: EOCacheCont
         return spf_cont_async(ctx, 3, 0.0, iters, step, 1.0, 0.0, 0.0, ftau);
@@ -2473,7 +2550,7 @@ int32_t rrrmc_set_couplings_dense(rrrmc_ctx* ctx, const double* J)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_dense(c, J));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qskn = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn) || ens_slice(ctx->model) == RRRMC_RE_SLICE_SKN;   // slice graphs: J is Nk x Nk
+    const bool qskn = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn) || model_slice(ctx->model) == RRRMC_RE_SLICE_SKN;   // slice graphs: J is Nk x Nk
     if (ctx->model != RRRMC_MODEL_SK_NORMAL && !qskn) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_dense is for RRRMC_MODEL_SK_NORMAL (or a GraphQuant over GraphSKNormal slices)");
     if (!J) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J is NULL");
     const int64_t N = qskn ? ctx->qNk : ctx->N;
@@ -2518,6 +2595,10 @@ int32_t rrrmc_energy_f64(rrrmc_ctx* ctx, double* E_out)
     } else if (is_sat(ctx)) {
         ctx->std_cache_live = false;
         rc = sat_run_init(ctx);
+    } else if (is_af(ctx)) {
+        if (!ctx->af_fields_set) return af_needs_fields(ctx);
+        ctx->std_cache_live = false;
+        rc = af_run_init(ctx, 1.0, false);
     } else if (ens_family(ctx->model) != ENS_NONE) {
         if (!ctx->re_params_set) return ens_needs_params(ctx, false);
         ctx->std_cache_live = false;
@@ -2614,7 +2695,7 @@ int32_t rrrmc_set_couplings_bits(rrrmc_ctx* ctx, const uint64_t* Jc)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_bits(c, Jc));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qsk = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk) || ens_slice(ctx->model) == RRRMC_RE_SLICE_SK;     // the slice graph of a GraphQSKT / GraphSKRE / GraphSKLE
+    const bool qsk = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk) || model_slice(ctx->model) == RRRMC_RE_SLICE_SK;     // the slice graph of a GraphQSKT / GraphSKRE / GraphSKLE
     if (ctx->model != RRRMC_MODEL_SK_BINARY && !qsk)
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_bits is for RRRMC_MODEL_SK_BINARY and for contexts made by rrrmc_ctx_create_quant_sk");
     if (!Jc) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J_chunks is NULL");

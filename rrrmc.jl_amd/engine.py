@@ -245,6 +245,21 @@ class Engine:
         check(lib().rrrmc_tle_cache(self._ctx, pos.ctypes.data, sizes.ctypes.data), self._ctx)
         return pos, sizes
 
+    def af_cache(self):
+        """(ΔEs[R, N], v[R, N], z[R], trefresh[R]) of the DeltaECacheCont after the last rrrMC call on a GraphAddFields / GraphAddSubFields"""
+        dEs = np.zeros((self.R, self.X.N), np.float64)
+        v = np.zeros((self.R, self.X.N), np.float64)
+        z = np.zeros(self.R, np.float64)
+        tref = np.zeros(self.R, np.int64)
+        check(lib().rrrmc_af_cache(self._ctx, dEs.ctypes.data, v.ctypes.data, z.ctypes.data, tref.ctypes.data), self._ctx)
+        return dEs, v, z, tref
+
+    def af_build(self):
+        """the kernel build of the last rrrMC call on a GraphAddFields / GraphAddSubFields: 1 state in LDS, 2 in global memory, 0 none yet"""
+        b = C.c_int32(0)
+        check(lib().rrrmc_af_build(self._ctx, C.byref(b)), self._ctx)
+        return int(b.value)
+
     def tle_build(self):
         """the kernel build of the last rrrMC call on a GraphTopologicalLocalEntropy: 1 hot state in LDS, 2 in global memory, 0 none yet"""
         b = C.c_int32(0)

@@ -954,6 +954,52 @@ def GraphPercLinearLE(*args, seed=DEFAULT_SEED):
     return _pattern_ensemble(GraphLocalEntropy, GraphPercLinear, "N, P", args, seed=seed)
 
 
+class GraphAddFields(_DeviceGraph):
+    """``GraphAddFields(fields, g)`` — external fields added to a graph ``g`` (src/graphs/AddFields.jl:58-90): a DoubleGraph whose inner
+    graph ``GraphAF(fields)`` has energy Σ_i h_i σ_i, delta_energy −2 σ_i h_i and no neighbours, and whose residual is ``g``'s own
+    delta_energy, so that ``rrrMC`` handles the fields through its DynamicSampler at O(log N) per move whatever ``g`` is.  ``g`` is ``None``
+    (GraphEmpty), a ``GraphSK``, ``GraphSKNormal``, ``GraphPercStep``, ``GraphPercLinear``, ``GraphCommStep``, ``GraphCommReLU``,
+    ``GraphCommQu`` or ``GraphSAT`` with ``len(fields)`` spins.  ``ET = Float64``: integer energies of ``g`` enter as exact Float64s."""
+    energy_dtype = np.float64
+    K = 0
+    _sub = 0
+
+    def _create(self, ctx, R, device, replica0):
+        check(lib().rrrmc_ctx_create_af(ctx, self.slice_kind, self._sub, self.N, self.K2, R, device, replica0))
+
+    def _multi_args(self):
+        return self.model_kind, self.N, self.K2, 0
+
+    def _upload(self, ctx):
+        if self.X1 is not None:
+            self.X1._upload_couplings(ctx)
+        check(lib().rrrmc_af_set_fields(ctx, self.fields), ctx)
+
+    def __init__(self, fields, g=None):
+        fields = np.ascontiguousarray(fields, np.float64)
+        if fields.ndim != 1 or len(fields) < 1:
+            raise ValueError("fields must be a non-empty vector")
+        if g is not None and not isinstance(g, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT)):
+            raise TypeError("%s wraps GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, GraphCommStep, GraphCommReLU, "
+                            "GraphCommQu or GraphSAT; sparse graphs (GraphRRG*, GraphEA*), GraphQuant and the ensembles are not wired as g, "
+                            "given a %s" % (type(self).__name__, type(g).__name__))
+        if g is not None and g.N != len(fields):
+            raise ValueError("incompatible length, fields size=%d graph size=%d" % (len(fields), g.N))       # AddFields.jl:65
+        if not np.all(np.isfinite(fields)):
+            raise ValueError("the fields must be finite")
+        self.fields, self.N, self.X1 = fields, len(fields), g
+        self.slice_kind = _ensemble_slice_kind(g)
+        self.K2 = int(getattr(g, "K2", 0)) if isinstance(g, _GraphComm) else 0
+        self.model_kind = (57 if self._sub else 48) + (0, 1, 2, 3, 4, 5, 6, None, 7, 8)[self.slice_kind]      # RRRMC_MODEL_AF_* / RRRMC_MODEL_ASF_*
+
+
+class GraphAddSubFields(GraphAddFields):
+    """``GraphAddSubFields(fields, g)`` — the fields added and subtracted (src/graphs/AddFields.jl:94-123): energy and delta_energy are
+    ``g``'s own, the residual is ``delta_energy(g) − delta_energy(GraphAF(fields))``.  The fields only shape the proposals of ``rrrMC``;
+    the stationary law is ``g``'s."""
+    _sub = 1
+
+
 class GraphRobustEnsemble(_DeviceGraph):
     """``GraphRobustEnsemble(Nk, M, γ, β, slice_graph)`` — the Robust Ensemble (src/graphs/RE.jl:215-263): M replicas of one graph (the
     slices, which share one coupling set as ``Gconstr(args...)`` with the same ``args`` gives them) coupled by ``GraphRE{M,γ,β}`` through
