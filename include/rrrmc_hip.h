@@ -134,7 +134,14 @@ enum rrrmc_model {
     RRRMC_MODEL_ASF_COMM_STEP = 62,   /* GraphAddSubFields(h, GraphCommStep) */
     RRRMC_MODEL_ASF_COMM_RELU = 63,   /* GraphAddSubFields(h, GraphCommReLU) */
     RRRMC_MODEL_ASF_SAT = 64,         /* GraphAddSubFields(h, GraphSAT) */
-    RRRMC_MODEL_ASF_COMM_QU = 65      /* GraphAddSubFields(h, GraphCommQu) */
+    RRRMC_MODEL_ASF_COMM_QU = 65,     /* GraphAddSubFields(h, GraphCommQu) */
+    /* the cross-entropy perceptron (src/graphs/PercXEntr.jl): the model of a context made by rrrmc_ctx_create_perc_xentr (N synapses; K and
+       M ignored by rrrmc_ctx_create_multi) */
+    RRRMC_MODEL_PERC_XENTR = 66,      /* GraphPercXEntr(N, P, lambda) */
+    /* the two field wrappers over it: made by rrrmc_ctx_create_af with RRRMC_RE_SLICE_PERC_XENTR; selectors of rrrmc_ctx_create_multi.
+       67 .. 99 are unassigned: the wrappers' first eighteen ids are a closed block (48 .. 65), and so are their names */
+    RRRMC_MODEL_XENTR_AF = 100,       /* GraphAddFields(h, GraphPercXEntr) */
+    RRRMC_MODEL_XENTR_ASF = 101       /* GraphAddSubFields(h, GraphPercXEntr) */
 };
 
 /* slice families of rrrmc_ctx_create_re */
@@ -148,7 +155,11 @@ enum rrrmc_re_slice {
     RRRMC_RE_SLICE_COMM_RELU = 6,   /* GraphCommReLU (src/graphs/CommReLU.jl): patterns and labels with rrrmc_set_comm_patterns; K1, K2 even */
     /* 7 is unassigned: rrrmc_ctx_create_re / _le refuse it with RRRMC_ERR_INVALID_ARG */
     RRRMC_RE_SLICE_SAT = 8,         /* GraphSAT (src/graphs/SAT.jl): clauses with rrrmc_set_clauses */
-    RRRMC_RE_SLICE_COMM_QU = 9      /* GraphCommQu (src/graphs/CommQu.jl): patterns and labels with rrrmc_set_comm_patterns; K1, K2 even */
+    RRRMC_RE_SLICE_COMM_QU = 9,     /* GraphCommQu (src/graphs/CommQu.jl): patterns and labels with rrrmc_set_comm_patterns; K1, K2 even */
+    /* 10 is unassigned, like 7 */
+    RRRMC_RE_SLICE_PERC_XENTR = 11  /* GraphPercXEntr (src/graphs/PercXEntr.jl): patterns with rrrmc_set_patterns, the table with rrrmc_set_loss_table;
+                                       N odd.  The g of rrrmc_ctx_create_af only: rrrmc_ctx_create_re / _le / _tle / _quant_pattern refuse it
+                                       (the reference has no RE, LE or Q alias for this graph) */
 };
 
 /* Library ABI version (major*10000 + minor*100 + patch). */
@@ -381,6 +392,33 @@ RRRMC_API int32_t rrrmc_set_patterns(rrrmc_ctx *ctx, const uint64_t *xi, int64_t
  * the host from the SKBITS stream of `seed` (third counter word 1).  Needs no device. */
 RRRMC_API int32_t rrrmc_gen_patterns(int64_t N, int64_t P, uint64_t seed, uint64_t *xi_out);
 
+/* ---- The cross-entropy perceptron (src/graphs/PercXEntr.jl; RRRMC_MODEL_PERC_XENTR, RRRMC_RE_SLICE_PERC_XENTR) ------
+ * rrrmc_ctx_create_perc_xentr: R chains of GraphPercXEntr with N synapses; the argument checks of rrrmc_ctx_create_perc (N odd, N <= 32767).
+ * Then rrrmc_set_patterns (1 <= P <= 4096) and rrrmc_set_loss_table, in either order; a sampling or energy call before both is
+ * RRRMC_ERR_STATE.  energy = sum_a Hs[(Delta_a + N) / 2] and delta_energy = sum_a (Hs[new] - Hs[old]), both added in pattern order from 0.0
+ * as PercXEntr.jl:97-119 and :165-193 add them: Float64 trajectories equal the reference's bit for bit GIVEN THE SAME TABLE.  Sampler:
+ * rrrmc_standard_mc_async with rrrmc_fetch_results_f64, rrrmc_set_resume, rrrmc_set_debug_checks, rrrmc_energy_f64.  rrrMC / bklMC / wtmMC
+ * / extremal_opt answer RRRMC_ERR_UNSUPPORTED as on the other stand-alone perceptrons; rrrMC runs on GraphAddFields / GraphAddSubFields over
+ * it (rrrmc_ctx_create_af with RRRMC_RE_SLICE_PERC_XENTR).
+ *
+ * rrrmc_set_loss_table: Hs[n], n = N + 1, Hs[k] = log(1 + exp(-2 lambda Delta / sqrt(N))) for Delta = -N + 2 k (PercXEntr.jl:65), made by the
+ * caller (a Julia caller passes X.Hs itself: Julia's log / exp and this library's libm do not promise the same last bit).  Every entry
+ * must be finite (RRRMC_ERR_INVALID_ARG; the reference would carry Inf - Inf into accept).  For a context made by
+ * rrrmc_ctx_create_perc_xentr or by rrrmc_ctx_create_af over it, single or multi-device.  May be called again (GraphPercXEntr(X, lambda_new):
+ * annealing lambda on fixed patterns): a new table ends a resumed run, the next call starts from energy(X, C).
+ *
+ * rrrmc_xentr_build: the kernel build of the last standardMC call on a stand-alone GraphPercXEntr: 0 none yet, 1 one thread per chain, 2 one
+ * wavefront per chain (few chains).  RRRMC_XENTR_NO_WAVE=1 forces 1, RRRMC_XENTR_WAVE=1 forces 2; RRRMC_XENTR_NO_LDS=1 keeps the table in
+ * global memory in either.  All builds give the same bits.
+ *
+ * rrrmc_perc_step_energy: step_energy (PercXEntr.jl:205-213) of every chain's live configuration, out[R]: the number of patterns with
+ * Delta_a < 0 (the training error), computed on the device from the configuration.  Read-only: a resumed run is not disturbed.  For any
+ * stand-alone perceptron context and for rrrmc_ctx_create_af over a perceptron. */
+RRRMC_API int32_t rrrmc_ctx_create_perc_xentr(rrrmc_ctx **out, int64_t N, int64_t R, int32_t device, uint32_t replica0);
+RRRMC_API int32_t rrrmc_set_loss_table(rrrmc_ctx *ctx, const double *Hs, int64_t n);
+RRRMC_API int32_t rrrmc_xentr_build(rrrmc_ctx *ctx, int32_t *build_out);
+RRRMC_API int32_t rrrmc_perc_step_energy(rrrmc_ctx *ctx, int64_t *out);
+
 /* ---- The binary committee machines (src/graphs/CommStep.jl, CommReLU.jl; RRRMC_MODEL_COMM_*, RRRMC_RE_SLICE_COMM_*) ------
  * rrrmc_ctx_create_comm: R chains of GraphCommStep (relu = 0; K1 and K2 odd) or GraphCommReLU (relu != 0; K1 and K2 even) with K2 hidden
  * units of K1 synapses each, N = K1*K2 (unit k owns synapses k*K1 .. (k+1)*K1 - 1).  A wrong parity is RRRMC_ERR_INVALID_ARG (the
@@ -516,7 +554,8 @@ RRRMC_API int32_t rrrmc_tle_build(rrrmc_ctx *ctx, int32_t *build_out);
  *   g, by its rrrmc_re_slice kind and with that kind's own upload call and limits: GraphEmpty (nothing to upload), binary GraphSK
  *   (rrrmc_set_couplings_bits), GraphSKNormal (rrrmc_set_couplings_dense), GraphPercStep / GraphPercLinear (rrrmc_set_patterns; N odd,
  *   N <= 32 767), GraphCommStep / GraphCommReLU / GraphCommQu (rrrmc_set_comm_patterns with the creator's K2; N = K1*K2 with each kind's
- *   parities, N <= 32 767), GraphSAT (rrrmc_set_clauses; N <= 65 535).  N <= 65 535 for the first three.  N = 1 runs (a tree of no levels).
+ *   parities, N <= 32 767), GraphSAT (rrrmc_set_clauses; N <= 65 535), GraphPercXEntr (rrrmc_set_patterns and rrrmc_set_loss_table; N odd,
+ *   N <= 32 767).  N <= 65 535 for the first three.  N = 1 runs (a tree of no levels).
  *   K2 is read for the committee machines only.
  * rrrmc_ctx_create_af, then g's upload, then rrrmc_af_set_fields.  Samplers: rrrmc_rrr_mc_async (fourK ignored; staged_thr = 0.5 is the
  * reference's default for a DoubleGraph) and rrrmc_standard_mc_async / rrrmc_standard_mc_f64 (the common SITE / ACCEPT_F64 streams), with

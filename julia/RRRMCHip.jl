@@ -57,6 +57,8 @@ const QUANT_SK, QUANT_SKN, QUANT_F64 = 8, 9, 10      # selectors of rrrmc_ctx_cr
 const RE_EMPTY, RE_SK, RE_SKN = 11, 12, 13            # GraphRobustEnsemble over GraphEmpty / GraphSK / GraphSKNormal (rrrmc_ctx_create_re; multi selectors)
 const LE_EMPTY, LE_SK, LE_SKN = 14, 15, 16            # GraphLocalEntropy over GraphEmpty / GraphSK / GraphSKNormal (rrrmc_ctx_create_le; multi selectors)
 const PERC_STEP, PERC_LINEAR = 17, 18                 # GraphPercStep, GraphPercLinear (rrrmc_ctx_create_perc; multi selectors)
+const PERC_XENTR = 66                                 # GraphPercXEntr (rrrmc_ctx_create_perc_xentr; multi selector)
+const XENTR_AF, XENTR_ASF = 100, 101                  # GraphAddFields / GraphAddSubFields over GraphPercXEntr (slice kind 11; multi selectors)
 const COMM_STEP, COMM_RELU = 23, 24                   # GraphCommStep, GraphCommReLU (rrrmc_ctx_create_comm; multi selectors, N = K1 K2, K = K2)
 const COMM_QU, QUANT_COMM_QU = 36, 39                 # GraphCommQu (rrrmc_ctx_create_comm_qu), GraphQCommQuT (slice kind 9); multi selectors as their siblings
 const QUANT_PAT_MODELS = (29, 30, 31, 32)              # by slice kind 3..6: GraphQPercStepT, GraphQPercLinearT, GraphQCommStepT, GraphQCommReLUT (multi selectors)
@@ -71,6 +73,20 @@ ens_kind(G, what) = G <: RRRMC.SK.GraphSK ? 1 : G <: RRRMC.SK.GraphSKNormal ? 2 
                     G <: RRRMC.CommStep.GraphCommStep ? 5 : G <: RRRMC.CommReLU.GraphCommReLU ? 6 : G <: RRRMC.SAT.GraphSAT ? 8 :
                     G <: RRRMC.CommQu.GraphCommQu ? 9 :
                     throw(ArgumentError("the engine runs the $what over GraphEmpty, GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, GraphCommStep, GraphCommReLU, GraphCommQu and GraphSAT slices, given: $G"))
+const XEntrGraph = RRRMC.PercXEntr.GraphPercXEntr
+# the patterns of a cross-entropy perceptron, and its loss table X.Hs ITSELF (PercXEntr.jl:65): the library takes the table as an input, so
+# that the trajectory does not depend on whose log and exp made it
+function set_patterns!(ctx, X1::XEntrGraph)
+    nch = (X1.N + 63) >> 6
+    xi = Matrix{UInt64}(undef, nch, X1.P); for a = 1:X1.P; xi[:, a] = X1.ξv[a].chunks; end
+    GC.@preserve xi check(ccall((:rrrmc_set_patterns, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt64}, Int64), ctx.p, xi, X1.P), ctx.p)
+    return set_loss_table!(ctx, X1.Hs)
+end
+# a new table on fixed patterns — GraphPercXEntr(X, λnew).Hs (PercXEntr.jl:87) —: ends a resumed run, the next call starts from energy(X, C)
+function set_loss_table!(ctx, Hs::Vector{Float64})
+    GC.@preserve Hs check(ccall((:rrrmc_set_loss_table, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64), ctx.p, Hs, length(Hs)), ctx.p)
+    return ctx
+end
 # the clauses of a GraphSAT as Mc rows of K = max length 0-based variables (-1 pads) and literal bits (SAT.jl:75-115): rrrmc_set_clauses
 function set_patterns!(ctx, X1::RRRMC.SAT.GraphSAT)
     vars = fill(Int32(-1), X1.K, X1.M); lits = zeros(Int8, X1.K, X1.M)
@@ -289,13 +305,14 @@ const AF_MODELS = (48, 49, 50, 51, 52, 53, 54, 0, 55, 56)          # RRRMC_MODEL
 function Ctx(X::AddFieldsGraph, R::Integer; device = 0, replica0 = 0, devices = nothing)
     sub = X isa RRRMC.AddFields.GraphAddSubFields
     g = X.X1
-    kind = ens_kind(typeof(g), sub ? "GraphAddSubFields" : "GraphAddFields")
+    kind = g isa XEntrGraph ? 11 : ens_kind(typeof(g), sub ? "GraphAddSubFields" : "GraphAddFields")          # (no ensemble takes GraphPercXEntr)
     K2 = g isa CommGraph ? g.K2 : 0
     ref = Ref{Ptr{Cvoid}}(C_NULL)
     if devices === nothing
         check(ccall((:rrrmc_ctx_create_af, LIB), Int32, (Ref{Ptr{Cvoid}}, Int32, Int32, Int64, Int64, Int64, Int32, UInt32), ref, kind, sub ? 1 : 0, X.N, K2, R, device, replica0))
     else
-        ref[] = create(AF_MODELS[kind + 1] + (sub ? 9 : 0), X.N, K2, 0, R; replica0 = replica0, devices = devices)
+        model = kind == 11 ? (sub ? XENTR_ASF : XENTR_AF) : AF_MODELS[kind + 1] + (sub ? 9 : 0)
+        ref[] = create(model, X.N, K2, 0, R; replica0 = replica0, devices = devices)
     end
     ctx = Ctx(ref[], R, X.N, true)
     if kind == 1
@@ -335,6 +352,30 @@ function Ctx(X::PercGraph, R::Integer; device = 0, replica0 = 0, devices = nothi
         ref[] = create(lin ? PERC_LINEAR : PERC_STEP, X.N, 0, 0, R; replica0 = replica0, devices = devices)
     end
     return set_patterns!(Ctx(ref[], R, X.N, true), X)
+end
+
+# ---- GraphPercXEntr (src/graphs/PercXEntr.jl), stand-alone: standardMC only; rrrMC through GraphAddFields / GraphAddSubFields over it ----
+# (Checked statically only, as the rest of this file.)  Given X.Hs the Float64 trajectory is the reference's bit for bit.
+function Ctx(X::XEntrGraph, R::Integer; device = 0, replica0 = 0, devices = nothing)
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    if devices === nothing
+        check(ccall((:rrrmc_ctx_create_perc_xentr, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, UInt32), ref, X.N, R, device, replica0))
+    else
+        ref[] = create(PERC_XENTR, X.N, 0, 0, R; replica0 = replica0, devices = devices)
+    end
+    return set_patterns!(Ctx(ref[], R, X.N, true), X)
+end
+# which kernel ran the last standardMC call on a stand-alone GraphPercXEntr: 0 none yet, 1 one thread per chain, 2 one wavefront per chain
+function xentr_build(ctx::Ctx)
+    b = Ref{Int32}(0)
+    check(ccall((:rrrmc_xentr_build, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), ctx.p, b), ctx.p)
+    return Int(b[])
+end
+# step_energy (PercXEntr.jl:205-213) of every chain's live configuration, recomputed on the device: the misclassified patterns
+function step_energy(ctx::Ctx)
+    out = Vector{Int64}(undef, ctx.R)
+    check(ccall((:rrrmc_perc_step_energy, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}), ctx.p, out), ctx.p)
+    return out
 end
 
 # ---- GraphSAT (src/graphs/SAT.jl), stand-alone: standardMC only (rrrMC / bklMC / wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED) ----

@@ -1,6 +1,6 @@
 // gfx950 kernels for GraphAddFields / GraphAddSubFields (src/graphs/AddFields.jl:16-123): a DoubleGraph whose inner graph X0 = GraphAF(h)
 // is N independent external fields (energy Σ_i h_i σ_i, delta_energy −2 σ_i h_i, no neighbours) over one graph g of N spins — any of the
-// nine slice kinds of re_kernels.hpp, used as ONE slice (M = 1, so the ABI site order is the slice's own).
+// nine slice kinds of re_kernels.hpp, or GraphPercXEntr (xentr_kernels.hpp), used as ONE slice (M = 1, so the ABI site order is the slice's own).
 //   GraphAddFields    (sub = 0): E = energy(X0) + energy(g), ΔE = ΔE(X0) + ΔE(g), residual = ΔE(g)
 //   GraphAddSubFields (sub = 1): E = energy(g),              ΔE = ΔE(g),          residual = ΔE(g) − ΔE(X0)
 // Samplers: rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290) over DeltaECacheCont (src/DeltaE.jl:297-410) and the DynamicSampler
@@ -17,7 +17,8 @@
 // setindex! (:159-176) go one level per lane — distinct nodes, so every node receives the reference's one addition —; refresh! (:84-98)
 // gives every node to one lane, which sums the leaves of its left subtree in ascending order, and z is accumulated sequentially (as
 // cw_refresh does; the reference's sum(v) is pairwise); the perceptron and committee machine updates are one pattern per lane
-// (perc_update / comm_update<.., true>).
+// (perc_update / comm_update<.., true>), and GraphPercXEntr's residual is the wave build of xentr_kernels.hpp: one term per lane, then the
+// ordered sum by every lane (xentr_residual_wave).
 // LDS = true: tree, weights, ΔEs, the spins and g's per-chain state live in LDS for the call; LDS = false: in global memory.  Same
 // operations in the same order: the two builds give the same bits.
 #pragma once
@@ -39,6 +40,7 @@ struct AfParams {
     long long* tref;                                        // [R]      DynamicSampler.trefresh
     int32_t* status;                                        // [2]      chains that met "Unrecoverable loss of precision detected in the dynamic sampler", one of them
     int sub, levs, N2;
+    int xe_hs_lds;                                          // GraphPercXEntr in the LDS build: the loss table is staged too (it fits)
 };
 
 // bytes of LDS one chain takes in the LDS build, without g's per-chain state: tree and weights (16 N2), ΔEs, the spins
@@ -52,7 +54,7 @@ template <int SLICE>
 __device__ __forceinline__ double af_g_energy(const ReParams& P, long long n, double eskn)
 {
     if constexpr (SLICE == RE_SK) { n /= 2; return (double)n / P.sN; }
-    else if constexpr (SLICE == RE_SKN) return eskn;
+    else if constexpr (SLICE == RE_SKN || SLICE == RE_PXE) return eskn;          // (a Float64 sum made in the reference's order)
     else if constexpr (kPercSlice<SLICE>) return perc_energy_of<SLICE == RE_PLIN>(n, P.pc.sN);
     else if constexpr (kCommSlice<SLICE> || SLICE == RE_SAT) return (double)n;
     else return 0.0;
@@ -102,6 +104,10 @@ __global__ __launch_bounds__(kAfInitThreads) void af_init_kernel(AfParams A, int
         comm_init_rows<comm_kind_of_slice(SLICE)>(P.cm, comm_view<comm_kind_of_slice(SLICE)>(P.cm, r), sp, N, N, s_n);
     } else if constexpr (SLICE == RE_SAT) {
         sat_init_rows(P.sat, sp, N, 0, 1, s_n);
+    } else if constexpr (SLICE == RE_PXE) {
+        __shared__ double s_t[kPercPmax];
+        const double Eg = xentr_init_chain(P.pc, P.xe, P.pc.ds + (size_t)r * 64 * P.pc.PW, 1, sp, N, s_t);
+        if (tid == 0) s_E[0] = Eg;
     }
     __syncthreads();
     if (cache) {
@@ -187,6 +193,18 @@ __global__ __launch_bounds__(64) void af_rrr_kernel(AfParams A)
         pv.ds = reinterpret_cast<int16_t*>(pv.mm + nw);
         for (int i = lane; i < nw; i += 64) { pv.pm[i] = g_pv.pm[i]; pv.mm[i] = g_pv.mm[i]; }
         for (int i = lane; i < 64 * nw; i += 64) pv.ds[i] = g_pv.ds[i];
+        __syncthreads();
+    }
+    if constexpr (LDS && SLICE == RE_PXE) {
+        const int Pp = 64 * P.pc.PW;                                               // the term buffer (16-byte aligned), the table when it fits, Δs
+        pv.term = reinterpret_cast<double*>(af_lds + ((af_lds_bytes(N, N2, W) + 15) & ~(size_t)15));
+        double* const hs = pv.term + Pp;
+        pv.ds = reinterpret_cast<int16_t*>(hs + (A.xe_hs_lds ? N + 1 : 0));
+        if (A.xe_hs_lds) {
+            for (int i = lane; i <= N; i += 64) hs[i] = g_pv.Hs[i];
+            pv.Hs = hs;
+        }
+        for (int i = lane; i < Pp; i += 64) pv.ds[i] = g_pv.ds[i];
         __syncthreads();
     }
     if constexpr (LDS && kCommSlice<SLICE>) {
@@ -359,6 +377,9 @@ __global__ __launch_bounds__(64) void af_rrr_kernel(AfParams A)
         for (int i = lane; i < nw; i += 64) { g_pv.pm[i] = pv.pm[i]; g_pv.mm[i] = pv.mm[i]; }
         for (int i = lane; i < 64 * nw; i += 64) g_pv.ds[i] = pv.ds[i];
     }
+    if constexpr (LDS && SLICE == RE_PXE) {
+        for (int i = lane; i < 64 * P.pc.PW; i += 64) g_pv.ds[i] = pv.ds[i];
+    }
     if constexpr (LDS && kCommSlice<SLICE>) {
         const int nm = (int)comm_mk_row(P.cm.K2, P.cm.PW, comm_kind_of_slice(SLICE) == CK_QU), nd = (int)comm_ds_row(P.cm.K2, P.cm.PW, comm_kind_of_slice(SLICE) == CK_QU);
         for (int i = lane; i < nm; i += 64) g_pv.mk[i] = pv.mk[i];
@@ -431,6 +452,7 @@ __global__ __launch_bounds__(64) void af_check_kernel(AfParams A, int cache)
     }
     if constexpr (kPercSlice<SLICE>) bad = bad || perc_state_bad<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, 0, N, N);
     if constexpr (kCommSlice<SLICE>) bad = bad || comm_state_bad<comm_kind_of_slice(SLICE)>(P.cm, comm_view<comm_kind_of_slice(SLICE)>(P.cm, r), sp, 0, N, N);
+    if constexpr (SLICE == RE_PXE) bad = bad || xentr_state_bad(P.pc, P.xe, P.pc.ds + (size_t)r * 64 * P.pc.PW, 1, sp, N);
     if (cache) {
         const double* dEs = A.dEs + (size_t)r * N;
         const double* w = A.v + (size_t)r * A.N2;

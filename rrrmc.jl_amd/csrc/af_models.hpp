@@ -33,6 +33,8 @@ constexpr AfModel kAfModels[] = {
     {RRRMC_MODEL_ASF_COMM_RELU, AF_ADDSUB, RRRMC_RE_SLICE_COMM_RELU},
     {RRRMC_MODEL_ASF_SAT, AF_ADDSUB, RRRMC_RE_SLICE_SAT},
     {RRRMC_MODEL_ASF_COMM_QU, AF_ADDSUB, RRRMC_RE_SLICE_COMM_QU},
+    {RRRMC_MODEL_XENTR_AF, AF_ADD, RRRMC_RE_SLICE_PERC_XENTR},
+    {RRRMC_MODEL_XENTR_ASF, AF_ADDSUB, RRRMC_RE_SLICE_PERC_XENTR},
 };
 
 // the wrapper of a model id; AF_NONE for every other model

@@ -12,6 +12,10 @@ int32_t af_not_wired(rrrmc_ctx* ctx, const char* sampler)
 }
 int32_t af_needs_fields(rrrmc_ctx* ctx) { return fail(ctx, RRRMC_ERR_STATE, "a %s needs its fields: call rrrmc_af_set_fields first", af_graph_name(ctx)); }
 
+// g is any ensemble slice kind, or GraphPercXEntr (which no ensemble takes): the wrappers' kernels are built over this set
+using AfSlices = SliceSet<RE_EMPTY, RE_SK, RE_SKN, RE_PSTEP, RE_PLIN, RE_CSTEP, RE_CRELU, RE_SAT, RE_CQU, RE_PXE>;
+static_assert((int)RE_PXE == RRRMC_RE_SLICE_PERC_XENTR, "ReSlice is rrrmc_re_slice");
+
 constexpr int64_t kAfNmax = 65535;          // N of a wrapper over GraphEmpty / GraphSK / GraphSKNormal (the other kinds bring their own bound)
 
 // every check of rrrmc_ctx_create_af, before any device query
@@ -20,10 +24,10 @@ int32_t af_check_create(rrrmc_ctx** out, int32_t slice_kind, int32_t sub, int64_
     if (!out) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (af_model(AF_ADD, slice_kind) == kAfNoModel)
-        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "GraphAddFields: slice_kind must be RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP, _PERC_LINEAR, _COMM_STEP, _COMM_RELU, _SAT or _COMM_QU, given: %d", slice_kind);
+        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "GraphAddFields: slice_kind must be RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP, _PERC_LINEAR, _COMM_STEP, _COMM_RELU, _SAT, _COMM_QU or _PERC_XENTR, given: %d", slice_kind);
     if (sub != 0 && sub != 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "sub must be 0 (GraphAddFields) or 1 (GraphAddSubFields), given: %d", sub);
     if (N < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "GraphAddFields: N and R must be >= 1");
-    const bool perc = slice_kind == RRRMC_RE_SLICE_PERC_STEP || slice_kind == RRRMC_RE_SLICE_PERC_LINEAR;
+    const bool perc = slice_kind == RRRMC_RE_SLICE_PERC_STEP || slice_kind == RRRMC_RE_SLICE_PERC_LINEAR || slice_kind == RRRMC_RE_SLICE_PERC_XENTR;
     const bool comm = slice_kind == RRRMC_RE_SLICE_COMM_STEP || slice_kind == RRRMC_RE_SLICE_COMM_RELU || slice_kind == RRRMC_RE_SLICE_COMM_QU;
     if (perc) { const int32_t rcn = perc_check_n(N); if (rcn) return rcn; }
     if (comm) {
@@ -49,7 +53,7 @@ int32_t af_ctx_create(rrrmc_ctx** out, int32_t slice_kind, int32_t sub, int64_t 
     ctx->qNk = N; ctx->qM = 1; ctx->qW = 2 * ((N + 63) / 64); ctx->q_Wk = ctx->qW;
     ctx->replica0 = replica0;
     ctx->graph_set = slice_kind == RRRMC_RE_SLICE_EMPTY;          // GraphEmpty has nothing to upload
-    if (slice_kind >= RRRMC_RE_SLICE_COMM_STEP && slice_kind != RRRMC_RE_SLICE_SAT) ctx->cm_K2 = K2;
+    if (slice_kind == RRRMC_RE_SLICE_COMM_STEP || slice_kind == RRRMC_RE_SLICE_COMM_RELU || slice_kind == RRRMC_RE_SLICE_COMM_QU) ctx->cm_K2 = K2;
     int levs = 0;
     while (((int64_t)1 << levs) < N) ++levs;                       // DynamicSamplers.jl:36
     ctx->af_levs = levs; ctx->af_N2 = (int64_t)1 << levs;
@@ -101,6 +105,7 @@ AfParams af_params(rrrmc_ctx* ctx, double beta)
     if (slice == RE_SK) { P.Jb = ctx->q_Jb; P.Wk = (int)ctx->q_Wk; P.sN = std::sqrt((double)ctx->N); }
     if (slice == RE_SKN) { P.Jd = ctx->sk_J; P.slf = ctx->q_slf; P.smv = ctx->q_smv; P.scur = ctx->q_scur; }
     if (slice == RE_PSTEP || slice == RE_PLIN) P.pc = perc_params(ctx, 1);
+    if (slice == RE_PXE) { P.pc = perc_params(ctx, 1); P.xe = xentr_params(ctx); }
     if (slice == RE_CSTEP || slice == RE_CRELU || slice == RE_CQU) P.cm = comm_params(ctx, 1);
     if (slice == RE_SAT) P.sat = sat_table(ctx);
     P.abi = ctx->q_spins; P.sp = ctx->q_spins;          // M = 1: the ABI site order is the slice's own
@@ -118,7 +123,7 @@ int32_t af_run_init(rrrmc_ctx* ctx, double beta, bool cache)
 {
     const AfParams A = af_params(ctx, beta);
     const dim3 grid((unsigned)ctx->R), blk(kAfInitThreads);
-    if (!with_slice(AllSlices{}, af_slice(ctx->model), [&](auto s) { hipLaunchKernelGGL(af_init_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, A, cache ? 1 : 0); }))
+    if (!with_slice(AfSlices{}, af_slice(ctx->model), [&](auto s) { hipLaunchKernelGGL(af_init_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, A, cache ? 1 : 0); }))
         return ens_bad_slice(ctx);
     HIP_TRY(ctx, hipGetLastError());
     return RRRMC_OK;
@@ -132,7 +137,7 @@ int32_t af_debug_check(rrrmc_ctx* ctx, const AfParams& A0, bool cache)
     AfParams A = A0;
     A.re.flag = ctx->dbg_flag;
     const dim3 grid((unsigned)((ctx->R + 63) / 64)), blk(64);
-    if (!with_slice(AllSlices{}, af_slice(ctx->model), [&](auto s) { hipLaunchKernelGGL(af_check_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, A, cache ? 1 : 0); }))
+    if (!with_slice(AfSlices{}, af_slice(ctx->model), [&](auto s) { hipLaunchKernelGGL(af_check_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, A, cache ? 1 : 0); }))
         return ens_bad_slice(ctx);
     HIP_TRY(ctx, hipGetLastError());
     return RRRMC_OK;
@@ -143,7 +148,7 @@ typedef void (*af_kernel_fn)(AfParams);
 af_kernel_fn af_rrr_fn(int slice, bool lds)
 {
     af_kernel_fn fn = nullptr;
-    with_slice(AllSlices{}, slice, [&](auto s) { fn = lds ? af_rrr_kernel<decltype(s)::value, true> : af_rrr_kernel<decltype(s)::value, false>; });
+    with_slice(AfSlices{}, slice, [&](auto s) { fn = lds ? af_rrr_kernel<decltype(s)::value, true> : af_rrr_kernel<decltype(s)::value, false>; });
     return fn;
 }
 
@@ -164,16 +169,27 @@ int32_t af_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, i
     HIP_TRY(ctx, hipEventRecord(ctx->ev_sweep[0], st));
     if (standard) {
         const dim3 grid(rrr_blocks(ctx->R)), blk(rrr_tpb(ctx->R));
-        if (!with_slice(AllSlices{}, slice, [&](auto s) { hipLaunchKernelGGL(af_standard_kernel<decltype(s)::value>, grid, blk, 0, st, A); })) return ens_bad_slice(ctx);
+        if (!with_slice(AfSlices{}, slice, [&](auto s) { hipLaunchKernelGGL(af_standard_kernel<decltype(s)::value>, grid, blk, 0, st, A); })) return ens_bad_slice(ctx);
     } else {
         // the LDS build whenever the chain's state fits: a rule of fit, not a measured crossing (RRRMC_AF_NO_LDS=1 forces the global build:
         // the builds' parity test)
         size_t lds = (af_lds_bytes(ctx->N, ctx->af_N2, ctx->qW) + 7) & ~(size_t)7;
         if (slice == RE_SKN) lds += (size_t)16 * (size_t)ctx->N;
-        if (A.re.pc.ds) lds += perc_lds_bytes(1, A.re.pc.PW);
+        if (slice == RE_PSTEP || slice == RE_PLIN) lds += perc_lds_bytes(1, A.re.pc.PW);
         if (A.re.cm.ds) lds += comm_lds_bytes(1, A.re.cm.K2, A.re.cm.PW, slice == RE_CQU);
+        if (slice == RE_PXE) {          // Δs and the term buffer; the loss table joins them when everything still fits
+            lds = (af_lds_bytes(ctx->N, ctx->af_N2, ctx->qW) + 15) & ~(size_t)15;
+            A.xe_hs_lds = lds + xentr_lds_bytes(ctx->N, A.re.pc.PW, 0, true) <= (size_t)kLdsLimit ? 1 : 0;
+            lds += xentr_lds_bytes(ctx->N, A.re.pc.PW, 0, A.xe_hs_lds != 0);
+        }
         const char* no_lds = std::getenv("RRRMC_AF_NO_LDS");
         const bool use_lds = lds <= (size_t)kLdsLimit && !(no_lds && no_lds[0] == '1');
+        if (slice == RE_PXE && !use_lds) {          // the global build keeps the term buffer in global memory
+            const int64_t Pp = 64 * (int64_t)A.re.pc.PW;
+            if (ctx->xe_term_P != ctx->pc_P) { dev_free(ctx, ctx->xe_term); ctx->xe_term_P = 0; }
+            if (!ctx->xe_term) { HIP_TRY(ctx, dev_alloc(ctx, ctx->xe_term, (size_t)(ctx->R * Pp))); ctx->xe_term_P = ctx->pc_P; }
+            A.re.xe.term = ctx->xe_term;
+        }
         const af_kernel_fn fn = af_rrr_fn(slice, use_lds);
         if (!fn) return ens_bad_slice(ctx);
         if (use_lds) HIP_TRY(ctx, raise_lds_attr(reinterpret_cast<const void*>(fn), lds));

@@ -24,9 +24,11 @@ PercParams perc_params(const rrrmc_ctx* ctx, int64_t rows)
     return Q;
 }
 
-// rrrmc_set_patterns on one device: rows = chains' rows that carry Stabilities (1, M, or M + 1)
-int32_t perc_set_patterns(rrrmc_ctx* ctx, const uint64_t* xi, int64_t P, int64_t rows)
+// rrrmc_set_patterns on one device: rows = chains' rows that carry Stabilities (1, M, or M + 1); chains = the chains Δs is sized for where
+// that is not R (the tiles of xentr_kernels.hpp)
+int32_t perc_set_patterns(rrrmc_ctx* ctx, const uint64_t* xi, int64_t P, int64_t rows, int64_t chains = 0)
 {
+    const int64_t Rc = chains ? chains : ctx->R;
     if (!xi) return fail(ctx, RRRMC_ERR_INVALID_ARG, "xi is NULL");
     if (P < 1) return fail(ctx, RRRMC_ERR_INVALID_ARG, "P must be >= 1, given: %lld", (long long)P);
     if (P > kPercPmax) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "P = %lld: the perceptron kernels cover P <= %d", (long long)P, kPercPmax);
@@ -45,9 +47,9 @@ int32_t perc_set_patterns(rrrmc_ctx* ctx, const uint64_t* xi, int64_t P, int64_t
         ctx->pc_P = 0; ctx->graph_set = false;
         HIP_TRY(ctx, dev_alloc(ctx, ctx->pc_col, (size_t)(N * PW)));
         HIP_TRY(ctx, dev_alloc_bytes(ctx, ctx->pc_row, sizeof(uint64_t) * (size_t)(P * nch)));
-        HIP_TRY(ctx, dev_alloc(ctx, ctx->pc_ds, (size_t)(ctx->R * rows * 64 * PW)));
-        HIP_TRY(ctx, dev_alloc(ctx, ctx->pc_pm, (size_t)(ctx->R * rows * PW)));
-        HIP_TRY(ctx, dev_alloc(ctx, ctx->pc_mm, (size_t)(ctx->R * rows * PW)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->pc_ds, (size_t)(Rc * rows * 64 * PW)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->pc_pm, (size_t)(Rc * rows * PW)));
+        HIP_TRY(ctx, dev_alloc(ctx, ctx->pc_mm, (size_t)(Rc * rows * PW)));
         ctx->pc_P = P;
     }
     HIP_TRY(ctx, hipMemcpy(ctx->pc_col, col.data(), sizeof(uint64_t) * col.size(), hipMemcpyHostToDevice));

@@ -17,6 +17,7 @@
 
 #include "rrr_kernels.hpp"   // RrrView, sbit / sflip, slice_delta, skn_update, kRrrThreads, TAG_RRR, det_exp
 #include "perc_kernels.hpp"  // the binary perceptron slices (PercParams, perc_residual, perc_update, perc_init_rows)
+#include "xentr_kernels.hpp" // the cross-entropy perceptron as the g of a field wrapper (XentrParams, xentr_residual, xentr_update)
 #include "comm_kernels.hpp"  // the binary committee machine slices (CommParams, comm_residual, comm_update, comm_init_rows)
 #include "sat_kernels.hpp"   // the K-SAT slices (SatTable, sat_delta, sat_row_energy, sat_init_rows)
 
@@ -26,12 +27,13 @@ enum ReSlice { RE_EMPTY = 0, RE_SK = 1, RE_SKN = 2,          // GraphEmpty (Grap
                RE_PSTEP = 3, RE_PLIN = 4,                    // GraphPercStep (GraphPercStepRE), GraphPercLinear (GraphPercLinearRE)
                RE_CSTEP = 5, RE_CRELU = 6,                   // GraphCommStep (GraphCommStepRE), GraphCommReLU (GraphCommReLURE)
                RE_SAT = 8,                                   // GraphSAT (GraphSATRE); 7 is unassigned, as in the ABI
-               RE_CQU = 9 };                                 // GraphCommQu (GraphCommQuRE)
+               RE_CQU = 9,                                   // GraphCommQu (GraphCommQuRE)
+               RE_PXE = 11 };                                // GraphPercXEntr: the g of GraphAddFields / GraphAddSubFields only (af_kernels.hpp); 10 is unassigned
 template <int SLICE> constexpr bool kPercSlice = SLICE == RE_PSTEP || SLICE == RE_PLIN;
 template <int SLICE> constexpr bool kCommSlice = SLICE == RE_CSTEP || SLICE == RE_CRELU || SLICE == RE_CQU;
 // slices whose state is a pure function of the configuration, updated once per accepted move by the whole wavefront in the LDS builds
 // (a K-SAT slice is not one: like the binary SK slice it keeps no state, its residual is recomputed from the spins by the worker thread)
-template <int SLICE> constexpr bool kWaveSlice = kPercSlice<SLICE> || kCommSlice<SLICE>;
+template <int SLICE> constexpr bool kWaveSlice = kPercSlice<SLICE> || kCommSlice<SLICE> || SLICE == RE_PXE;
 constexpr int kReMmax = 32;                                 // replicas of the ensemble; levels L = ceil(M / 2) <= 16
 
 struct ReParams {
@@ -39,6 +41,7 @@ struct ReParams {
     const uint32_t* Jb; int Wk; double sN;                  // binary GraphSK: rows of J as 32-bit words, sqrt(Nk)
     const double* Jd;                                       // GraphSKNormal: [Nk][Nk]
     PercParams pc;                                          // perceptron slices: the shared patterns, every slice's Stabilities
+    XentrParams xe;                                         // GraphPercXEntr (with pc): the loss table, the global build's term buffer
     CommParams cm;                                          // committee machine slices: the same for GraphCommStep / GraphCommReLU / GraphCommQu
     SatTable sat;                                           // K-SAT slices: the shared occurrence program (no per-slice state)
     double* slf;                                            // [R][2][M][Nk]  every slice's lfields / lfields_last (SK.jl:212-276)
@@ -126,6 +129,20 @@ __device__ __forceinline__ void re_slice_update(const RrrView& v, const CommView
     static_assert(kCommSlice<SLICE>, "a CommView goes with a committee machine slice");
     comm_update<comm_kind_of_slice(SLICE), WAVE>(cv, k, i, sbit(v.sp, x));
 }
+// ... and with the cross-entropy perceptron (xentr_kernels.hpp), M = 1; WAVE: the wavefront forms the terms, every lane adds them in order
+template <int SLICE, bool WAVE = false>
+__device__ __forceinline__ double re_residual(const RrrView& v, const XentrView& xv, int x, int /*k*/, int i)
+{
+    static_assert(SLICE == RE_PXE, "a XentrView goes with GraphPercXEntr");
+    if constexpr (WAVE) return xentr_residual_wave(xv, i, sbit(v.sp, x));
+    else return xentr_residual(xv, i, sbit(v.sp, x));
+}
+template <int SLICE, bool WAVE>
+__device__ __forceinline__ void re_slice_update(const RrrView& v, const XentrView& xv, int x, int /*k*/, int i)
+{
+    static_assert(SLICE == RE_PXE, "a XentrView goes with GraphPercXEntr");
+    xentr_update<WAVE>(xv, i, sbit(v.sp, x));
+}
 // ... and with the K-SAT slices (sat_kernels.hpp): delta_energy from the row's spins, no update_cache!
 template <int SLICE, bool WAVE = false>
 __device__ __forceinline__ double re_residual(const RrrView& v, const SatTable& sv, int x, int /*k*/, int i)
@@ -143,6 +160,7 @@ template <int SLICE, class PP>
 __device__ __forceinline__ auto re_slice_view(const PP& P, int r)
 {
     if constexpr (SLICE == RE_SAT) return P.sat;
+    else if constexpr (SLICE == RE_PXE) return xentr_view(P.pc, P.xe, r);
     else if constexpr (kCommSlice<SLICE>) return comm_view<comm_kind_of_slice(SLICE)>(P.cm, r);
     else return perc_view(P.pc, r);
 }
@@ -184,6 +202,8 @@ __device__ inline double re_slice_energy(const ReParams& P, const RrrView& v, in
         return comm_row_energy<comm_kind_of_slice(SLICE)>(P.cm, v.sp, k * Nk, P.N);
     } else if constexpr (SLICE == RE_SAT) {
         return (double)sat_row_energy(P.sat, v.sp, k * Nk);
+    } else if constexpr (SLICE == RE_PXE) {
+        return xentr_row_energy(P.pc, P.xe, v.sp, P.N);
     } else {
         return 0.0;
     }

@@ -40,6 +40,7 @@ typedef hipError_t dev_err_t;
 #include "cont_kernels.hpp"
 #include "cont_wave_kernel.hpp"
 #include "perc_kernels.hpp"
+#include "xentr_kernels.hpp"
 #include "comm_kernels.hpp"
 #include "quant_pat_kernels.hpp"
 #include "sat_kernels.hpp"
@@ -325,6 +326,15 @@ struct rrrmc_ctx {
     uint64_t* pc_pm = nullptr;     // [R][rows][PW] the set p
     uint64_t* pc_mm = nullptr;     // [R][rows][PW] the set m
     int64_t pc_P = 0;
+    // ---- the cross-entropy perceptron (RRRMC_MODEL_PERC_XENTR, and the g of the field wrappers over it; host_xentr.hpp): patterns in pc_col /
+    //      pc_row, stabilities in pc_ds (stand-alone: tiles of 64 chains, xentr_kernels.hpp), spins in q_spins, E in sk_E, counts in q_stats ----
+    double* xe_Hs = nullptr;       // [N + 1] the loss table (rrrmc_set_loss_table)
+    int64_t* xe_nacc = nullptr;    // [R] accepted moves of the live run (the debug check's bound)
+    double* xe_term = nullptr;     // [R][64 PW] the wrappers' term buffer of the global-memory build (allocated on first use)
+    int64_t xe_term_P = 0;         // the P xe_term was sized for
+    double xe_hmax = 0.0;          // the table's largest entry
+    bool xe_table_set = false;
+    int xe_build = 0;              // the build of the last standardMC call: 1 thread per chain, 2 wavefront per chain; 0 none yet
     // ---- the binary committee machines (RRRMC_MODEL_COMM_*, and the committee slices of the ensembles; host_comm.hpp): spins
     //      in q_spins, E in sk_E, counts in q_stats ----
     uint64_t* cm_col = nullptr;    // [Nk][PW] patterns, one column per synapse
@@ -562,7 +572,7 @@ hipError_t raise_lds_attr(const void* fn, size_t bytes)
 }
 
 inline bool chunk_layout(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_QUANT_RRG || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_SPARSE_LEVELS ||
-                                                       ctx->model == RRRMC_MODEL_PERC_STEP || ctx->model == RRRMC_MODEL_PERC_LINEAR ||
+                                                       ctx->model == RRRMC_MODEL_PERC_STEP || ctx->model == RRRMC_MODEL_PERC_LINEAR || ctx->model == RRRMC_MODEL_PERC_XENTR ||
                                                        ctx->model == RRRMC_MODEL_COMM_STEP || ctx->model == RRRMC_MODEL_COMM_RELU || ctx->model == RRRMC_MODEL_COMM_QU ||
                                                        ctx->model == RRRMC_MODEL_SAT || ens_family(ctx->model) != ENS_NONE || af_family(ctx->model) != AF_NONE; }
 inline bool sparse_int_model(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_SPARSE_PM1 || ctx->model == RRRMC_MODEL_SPARSE_LEVELS; }
@@ -571,6 +581,8 @@ inline double lv_to_f64(const rrrmc_ctx* ctx, long long units) { return (double)
 int32_t ensure_state(rrrmc_ctx* ctx, bool need_spins)
 {
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!ctx->graph_set && ctx->pc_P > 0 && (ctx->model == RRRMC_MODEL_PERC_XENTR || model_slice(ctx->model) == RRRMC_RE_SLICE_PERC_XENTR))
+        return fail(ctx, RRRMC_ERR_STATE, "a GraphPercXEntr needs its loss table: call rrrmc_set_loss_table first");
     if (!ctx->graph_set) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph has not been called");
     if (need_spins && !ctx->spins_set)
         return fail(ctx, RRRMC_ERR_STATE, "no configuration: call rrrmc_init_spins_random or rrrmc_set_spins first");
@@ -708,6 +720,7 @@ inline void smp_commit(rrrmc_ctx* ctx, int kind, int64_t n) { ctx->smp_kind = ki
 #include "host_sweep.hpp"
 #include "host_spf_fast.hpp"
 #include "host_perc.hpp"
+#include "host_xentr.hpp"
 #include "host_comm.hpp"
 #include "host_quant_pat.hpp"
 #include "host_sat.hpp"
@@ -1331,6 +1344,7 @@ int32_t rrrmc_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int6
     if (ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED) return dbl_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (ctx->model == RRRMC_MODEL_SPARSE_LEVELS) return lev_standard_mc_async(ctx, beta, iters, step, false);
     if (is_perc(ctx)) return perc_mc_async(ctx, beta, iters, step);
+    if (is_xentr(ctx)) return xentr_mc_async(ctx, beta, iters, step);
     if (is_comm(ctx)) return comm_mc_async(ctx, beta, iters, step);
     if (is_sat(ctx)) return sat_mc_async(ctx, beta, iters, step);
     if (is_af(ctx)) return af_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
@@ -1370,7 +1384,7 @@ int32_t rrrmc_set_debug_checks(rrrmc_ctx* ctx, int32_t on)
 {
     RRRMC_MULTI(ctx, false, rrrmc_set_debug_checks(c, on));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_tle(ctx) && !is_af(ctx) && !is_perc(ctx) && !is_comm(ctx) && !quant_pat(ctx) && !is_sat(ctx))
+    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_tle(ctx) && !is_af(ctx) && !is_perc(ctx) && !is_xentr(ctx) && !is_comm(ctx) && !quant_pat(ctx) && !is_sat(ctx))
         return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy, the GraphTopologicalLocalEntropy, GraphAddFields / GraphAddSubFields, the perceptron, the committee machine and the K-SAT graphs, and GraphQuant over perceptrons and committee machines");
     ctx->debug_checks = on != 0;
     return RRRMC_OK;
@@ -1773,9 +1787,51 @@ int32_t rrrmc_set_patterns(rrrmc_ctx* ctx, const uint64_t* xi, int64_t P)
     RRRMC_MULTI(ctx, false, rrrmc_set_patterns(c, xi, P));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (is_xentr(ctx)) return xentr_set_patterns(ctx, xi, P);
+    if (xentr_slices(ctx)) { const int32_t rc = perc_set_patterns(ctx, xi, P, 1); if (!rc) ctx->graph_set = ctx->xe_table_set; return rc; }
     if (!is_perc(ctx) && !perc_slices(ctx) && !quant_pat_perc(ctx))
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_patterns is for contexts made by rrrmc_ctx_create_perc, or by rrrmc_ctx_create_re / _le / _quant_pattern with a perceptron slice kind");
     return perc_set_patterns(ctx, xi, P, is_perc(ctx) ? 1 : is_le(ctx) ? ctx->qM + 1 : ctx->qM);
+}
+
+// ---- the cross-entropy perceptron: exported entry points (host_xentr.hpp) ----
+int32_t rrrmc_ctx_create_perc_xentr(rrrmc_ctx** out, int64_t N, int64_t R, int32_t device, uint32_t replica0)
+{
+    return xentr_ctx_create(out, N, R, device, replica0);
+}
+
+int32_t rrrmc_set_loss_table(rrrmc_ctx* ctx, const double* Hs, int64_t n)
+{
+    RRRMC_MULTI(ctx, false, rrrmc_set_loss_table(c, Hs, n));
+    smp_drop(ctx);
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!is_xentr(ctx) && !xentr_slices(ctx))
+        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_loss_table is for contexts made by rrrmc_ctx_create_perc_xentr, or by rrrmc_ctx_create_af with RRRMC_RE_SLICE_PERC_XENTR");
+    return xentr_set_table(ctx, Hs, n);
+}
+
+int32_t rrrmc_xentr_build(rrrmc_ctx* ctx, int32_t* build_out)
+{
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (is_multi(ctx)) return rrrmc_xentr_build(ctx->kids[0], build_out);
+    if (!is_xentr(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_xentr_build is for contexts made by rrrmc_ctx_create_perc_xentr");
+    if (!build_out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "build_out is NULL");
+    *build_out = ctx->xe_build;
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_perc_step_energy(rrrmc_ctx* ctx, int64_t* out)
+{
+    RRRMC_MULTI(ctx, true, rrrmc_perc_step_energy(c, at_row(out, r0)));
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    const int32_t ms = model_slice(ctx->model);
+    const bool wrapped = is_af(ctx) && (ms == RRRMC_RE_SLICE_PERC_STEP || ms == RRRMC_RE_SLICE_PERC_LINEAR || ms == RRRMC_RE_SLICE_PERC_XENTR);
+    if (!is_perc(ctx) && !is_xentr(ctx) && !wrapped)
+        return fail(ctx, RRRMC_ERR_STATE, "rrrmc_perc_step_energy is for contexts made by rrrmc_ctx_create_perc / _perc_xentr, or by rrrmc_ctx_create_af over a perceptron");
+    if (!out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "out is NULL");
+    if (ctx->pc_P < 1) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_patterns has not been called");
+    if (!ctx->spins_set) return fail(ctx, RRRMC_ERR_STATE, "no configuration: call rrrmc_init_spins_random or rrrmc_set_spins first");
+    return perc_step_energy(ctx, out);
 }
 
 // ---- the binary committee machines: exported entry points (host_comm.hpp) ----
@@ -2105,6 +2161,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     const bool sat = model == RRRMC_MODEL_SAT;
     const bool af = af_family(model) != AF_NONE;
     const bool pc = model == RRRMC_MODEL_PERC_STEP || model == RRRMC_MODEL_PERC_LINEAR;
+    const bool xe = model == RRRMC_MODEL_PERC_XENTR;
     const bool cm = model == RRRMC_MODEL_COMM_STEP || model == RRRMC_MODEL_COMM_RELU || model == RRRMC_MODEL_COMM_QU;
     if (cm && (K < 1 || N % K != 0)) {
         delete ctx;
@@ -2113,7 +2170,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     ctx->model = quant ? RRRMC_MODEL_QUANT_RRG : model; ctx->K = K; ctx->R = R; ctx->replica0 = replica0; ctx->device = device_ids[0];
     ctx->N = quant || re ? N * M : le || tle ? N * (M + 1) : N;
     if (re || le || tle) { ctx->qNk = N; ctx->qM = M; }
-    if (pc || sat) { ctx->qNk = N; ctx->qM = 1; }
+    if (pc || xe || sat) { ctx->qNk = N; ctx->qM = 1; }
     if (cm) { ctx->qNk = N; ctx->qM = 1; ctx->cm_K2 = K; ctx->K = 0; }
     if (af) { ctx->qNk = N; ctx->qM = 1; ctx->K = 0; }
     if (quant) { ctx->qNk = N; ctx->qM = M; ctx->q_sk = model == RRRMC_MODEL_QUANT_SK; ctx->q_skn = model == RRRMC_MODEL_QUANT_SKN; ctx->q_spf = model == RRRMC_MODEL_QUANT_F64; ctx->q_pat = qpat; }
@@ -2132,6 +2189,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : le ? rrrmc_ctx_create_le(&c, N, M, ens_slice(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : tle ? rrrmc_ctx_create_tle(&c, N, M, ens_slice(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : af ? rrrmc_ctx_create_af(&c, af_slice(model), af_family(model) == AF_ADDSUB, N, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : xe ? rrrmc_ctx_create_perc_xentr(&c, N, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : pc ? rrrmc_ctx_create_perc(&c, N, model == RRRMC_MODEL_PERC_LINEAR, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : sat ? rrrmc_ctx_create_sat(&c, N, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_COMM_QU ? rrrmc_ctx_create_comm_qu(&c, N / K, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
@@ -2332,7 +2390,7 @@ int32_t rrrmc_rrr_mc_async(rrrmc_ctx* ctx, double beta, double fourK, int64_t it
     if (sparse_int_model(ctx)) return sparse_rrr_bkl_async(ctx, 0, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED) return dbl_rrr_mc_async(ctx, beta, iters, step, staged_thr, staged_thr_fact);
     if (ctx->model == RRRMC_MODEL_SPARSE_F64) return spf_cont_async(ctx, 0, beta, iters, step, 1.0, staged_thr, staged_thr_fact);
-    if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone perceptron graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
+    if (is_perc(ctx) || is_xentr(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone perceptron graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone committee machine graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone GraphSAT (a DeltaECache of max_conn + 1 levels over variable-degree neighbourhoods): standardMC is, and rrrMC on GraphSATRE / GraphSATLE");
     if (is_af(ctx)) return af_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
@@ -2350,7 +2408,7 @@ int32_t rrrmc_bkl_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t s
     if (ctx) ctx->std_cache_live = false;
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
-    if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone perceptron graphs (standardMC is)");
+    if (is_perc(ctx) || is_xentr(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone GraphSAT (standardMC is)");
     if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "bklMC");
@@ -2393,7 +2451,7 @@ int32_t rrrmc_wtm_mc_async(rrrmc_ctx* ctx, double beta, int64_t samples, double 
     if (ctx) ctx->std_cache_live = false;
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
-    if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone perceptron graphs (standardMC is)");
+    if (is_perc(ctx) || is_xentr(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone GraphSAT (standardMC is)");
     if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "wtmMC");
@@ -2424,7 +2482,7 @@ int32_t rrrmc_extremal_opt_async(rrrmc_ctx* ctx, const double* ftau, int64_t ite
     if (ctx) ctx->std_cache_live = false;
     int32_t rc = ensure_state(ctx, true);
     if (rc) return rc;
-    if (is_perc(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone perceptron graphs (standardMC is)");
+    if (is_perc(ctx) || is_xentr(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone committee machine graphs (standardMC is)");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone GraphSAT (standardMC is)");
     if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "extremal_opt");
@@ -2589,6 +2647,9 @@ int32_t rrrmc_energy_f64(rrrmc_ctx* ctx, double* E_out)
     } else if (is_perc(ctx)) {
         ctx->std_cache_live = false;
         rc = perc_run_init(ctx);
+    } else if (is_xentr(ctx)) {
+        ctx->std_cache_live = false;
+        rc = xentr_run_init(ctx);
     } else if (is_comm(ctx)) {
         ctx->std_cache_live = false;
         rc = comm_run_init(ctx);

@@ -260,6 +260,25 @@ class Engine:
         check(lib().rrrmc_af_build(self._ctx, C.byref(b)), self._ctx)
         return int(b.value)
 
+    def xentr_build(self):
+        """the kernel build of the last standardMC call on a stand-alone GraphPercXEntr: 1 one thread per chain, 2 one wavefront per chain,
+        0 none yet"""
+        b = C.c_int32(0)
+        check(lib().rrrmc_xentr_build(self._ctx, C.byref(b)), self._ctx)
+        return int(b.value)
+
+    def step_energy(self):
+        """step_energy (PercXEntr.jl:205-213) of the live configuration: the misclassified patterns of every chain, (R,) int64.  Read-only."""
+        out = np.zeros(self.R, np.int64)
+        check(lib().rrrmc_perc_step_energy(self._ctx, out), self._ctx)
+        return out
+
+    def set_loss_table(self, Hs):
+        """swap the loss table of a GraphPercXEntr (or of a field wrapper over it) on the live context — ``GraphPercXEntr(X, λnew).Hs`` anneals λ
+        on fixed patterns; the next sampler call starts from ``energy(X, C)`` with the new table"""
+        Hs = np.ascontiguousarray(Hs, np.float64)
+        check(lib().rrrmc_set_loss_table(self._ctx, Hs, len(Hs)), self._ctx)
+
     def tle_build(self):
         """the kernel build of the last rrrMC call on a GraphTopologicalLocalEntropy: 1 hot state in LDS, 2 in global memory, 0 none yet"""
         b = C.c_int32(0)

@@ -644,6 +644,92 @@ class GraphPercLinear(_GraphPerc):
     __doc__ += _GraphPerc.__doc__
 
 
+class GraphPercXEntr(_DeviceGraph):
+    """``GraphPercXEntr(N, P, λ)`` (src/graphs/PercXEntr.jl:74-85): the binary perceptron with the cross-entropy loss, energy
+    Σ_a log(1 + exp(−2λ Δ_a / √N)) over the P patterns (Δ_a = σ·ξ_a).  ``ET = Float64``.  ``GraphPercXEntr(X, λnew)`` (:87) keeps X's patterns
+    and swaps the table — annealing λ on fixed patterns.  ``from_patterns(ξ, λ)`` takes an explicit P x N 0/1 matrix.  ``xi`` holds the
+    patterns in the layout of ``GraphPercStep``; ``Hs`` is the table of the N + 1 losses for Δ = −N:2:N, built here in the reference's operator
+    order (:65) and handed to the library as it is (``rrrmc_set_loss_table``): given the same table the trajectory is the reference's.
+    Not a slice graph of the ensembles or of GraphQuant (the reference has no such alias); ``GraphAddFields`` / ``GraphAddSubFields`` wrap
+    it, which opens ``rrrMC`` on it.  See ``step_energy``."""
+    K = 0
+    model_kind = 66         # RRRMC_MODEL_PERC_XENTR
+    energy_dtype = np.float64
+    _engine = None
+
+    def _create(self, ctx, R, device, replica0):
+        check(lib().rrrmc_ctx_create_perc_xentr(ctx, self.N, R, device, replica0))
+
+    def _upload_couplings(self, ctx):
+        check(lib().rrrmc_set_patterns(ctx, self.xi.reshape(-1), self.P), ctx)
+        check(lib().rrrmc_set_loss_table(ctx, self.Hs, len(self.Hs)), ctx)
+
+    def __init__(self, N, P, lam=None, seed=DEFAULT_SEED):
+        if isinstance(N, GraphPercXEntr):                                                # GraphPercXEntr(X, λnew), PercXEntr.jl:87
+            if lam is not None:
+                raise TypeError("expected (N, P, λ) or (X, λnew)")
+            self._init(N.N, N.P, N.xi, P)
+            return
+        if lam is None:
+            raise TypeError("expected (N, P, λ) or (X, λnew)")
+        N, P = int(N), int(P)
+        if N % 2 == 0:
+            raise ValueError("N must be odd, given: %d" % N)                             # PercXEntr.jl:63
+        if P < 1:
+            raise ValueError("P must be >= 1, given: %d" % P)
+        xi = np.zeros((P, nchunks(N)), np.uint64)
+        check(lib().rrrmc_gen_patterns(N, P, seed, xi.reshape(-1)))
+        self._init(N, P, xi, lam)
+
+    def _init(self, N, P, xi, lam):
+        if not isinstance(lam, float):
+            raise TypeError("λ must be a Float64, given a %s" % type(lam).__name__)     # PercXEntr.jl:62
+        self.N, self.P, self.xi, self.lam = N, P, xi, lam
+        self.Hs = self.loss_table(N, lam)
+        if not np.isfinite(self.Hs).all():
+            raise ValueError("λ = %r at N = %d: the loss table is not finite (exp overflows)" % (lam, N))
+
+    @staticmethod
+    def loss_table(N, lam):
+        """[log(1 + exp(-2 * λ * Δ / √(N))) for Δ = -N:2:N] (PercXEntr.jl:65), operator for operator; an overflowing exp is Julia's Inf"""
+        import math
+
+        def H(d):
+            x = ((-2.0 * lam) * d) / math.sqrt(N)
+            try:
+                return math.log(1 + math.exp(x))
+            except OverflowError:
+                return math.inf
+        return np.array([H(d) for d in range(-N, N + 1, 2)], np.float64)
+
+    @classmethod
+    def from_patterns(cls, xi, lam):
+        """the graph of an explicit pattern matrix: ``xi`` is a P x N array of 0/1 (or booleans)"""
+        xi = np.asarray(xi)
+        if xi.ndim != 2 or xi.shape[0] < 1 or xi.shape[1] < 1:
+            raise ValueError("the patterns must be a P x N matrix, given an array of shape %s" % (xi.shape,))
+        if not np.isin(xi, (0, 1)).all():
+            raise ValueError("the patterns must be 0/1")
+        if xi.shape[1] % 2 == 0:
+            raise ValueError("N must be odd, given: %d" % xi.shape[1])
+        X = cls.__new__(cls)
+        X._init(int(xi.shape[1]), int(xi.shape[0]), pack_patterns(xi), lam)
+        return X
+
+    def patterns(self):
+        """the P x N matrix of 0/1"""
+        return unpack_patterns(self.xi, self.N)
+
+
+def step_energy(X, C=None):
+    """``step_energy(X)`` (PercXEntr.jl:205-213): the number of misclassified patterns (Δ_a < 0) — the training error while the cross-entropy
+    is being minimised — an int for one replica of the batch, shape (R,) otherwise (int64).  Read as ``LEenergies`` reads: the live
+    configuration of the engine that runs ``X`` (inside a hook: the sample's), or ``C``; recomputed from the configuration on the device, so
+    a hook that calls it does not change the run.  ``X`` is a ``GraphPercXEntr`` (or a field wrapper over it)."""
+    E = _le_observable(X, C, "step_energy", "step_energy")
+    return int(E[0]) if E.size == 1 else E
+
+
 class _GraphComm(_DeviceGraph):
     """A two-layer binary committee machine: ``K2`` hidden units of ``K1`` binary synapses each, N = K1 K2 (unit k owns synapses
     k K1 .. (k + 1) K1 - 1), trained on ``P`` random ±1 patterns.  ``xi`` holds the patterns as P rows of ceil(N/64) chunks (the layout of
@@ -833,6 +919,8 @@ def _ensemble_slice_kind(slice_graph):
         return 8            # RRRMC_RE_SLICE_SAT (7 is unassigned)
     if isinstance(slice_graph, GraphCommQu):
         return 9            # RRRMC_RE_SLICE_COMM_QU
+    if isinstance(slice_graph, GraphPercXEntr):
+        return 11           # RRRMC_RE_SLICE_PERC_XENTR (10 is unassigned; the g of the field wrappers only)
     return (0 if slice_graph is None else 1 if isinstance(slice_graph, GraphSK) else 2 if isinstance(slice_graph, GraphSKNormal)
             else 3 if isinstance(slice_graph, GraphPercStep) else 4 if isinstance(slice_graph, GraphPercLinear)
             else 5 if isinstance(slice_graph, GraphCommStep) else 6)
@@ -959,10 +1047,12 @@ class GraphAddFields(_DeviceGraph):
     graph ``GraphAF(fields)`` has energy Σ_i h_i σ_i, delta_energy −2 σ_i h_i and no neighbours, and whose residual is ``g``'s own
     delta_energy, so that ``rrrMC`` handles the fields through its DynamicSampler at O(log N) per move whatever ``g`` is.  ``g`` is ``None``
     (GraphEmpty), a ``GraphSK``, ``GraphSKNormal``, ``GraphPercStep``, ``GraphPercLinear``, ``GraphCommStep``, ``GraphCommReLU``,
-    ``GraphCommQu`` or ``GraphSAT`` with ``len(fields)`` spins.  ``ET = Float64``: integer energies of ``g`` enter as exact Float64s."""
+    ``GraphCommQu``, ``GraphSAT`` or ``GraphPercXEntr`` with ``len(fields)`` spins.  ``ET = Float64``: integer energies of ``g`` enter as
+    exact Float64s."""
     energy_dtype = np.float64
     K = 0
     _sub = 0
+    _engine = None          # step_energy over a perceptron reads the live engine
 
     def _create(self, ctx, R, device, replica0):
         check(lib().rrrmc_ctx_create_af(ctx, self.slice_kind, self._sub, self.N, self.K2, R, device, replica0))
@@ -979,9 +1069,9 @@ class GraphAddFields(_DeviceGraph):
         fields = np.ascontiguousarray(fields, np.float64)
         if fields.ndim != 1 or len(fields) < 1:
             raise ValueError("fields must be a non-empty vector")
-        if g is not None and not isinstance(g, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT)):
+        if g is not None and not isinstance(g, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT, GraphPercXEntr)):
             raise TypeError("%s wraps GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, GraphCommStep, GraphCommReLU, "
-                            "GraphCommQu or GraphSAT; sparse graphs (GraphRRG*, GraphEA*), GraphQuant and the ensembles are not wired as g, "
+                            "GraphCommQu, GraphSAT or GraphPercXEntr; sparse graphs (GraphRRG*, GraphEA*), GraphQuant and the ensembles are not wired as g, "
                             "given a %s" % (type(self).__name__, type(g).__name__))
         if g is not None and g.N != len(fields):
             raise ValueError("incompatible length, fields size=%d graph size=%d" % (len(fields), g.N))       # AddFields.jl:65
@@ -990,7 +1080,10 @@ class GraphAddFields(_DeviceGraph):
         self.fields, self.N, self.X1 = fields, len(fields), g
         self.slice_kind = _ensemble_slice_kind(g)
         self.K2 = int(getattr(g, "K2", 0)) if isinstance(g, _GraphComm) else 0
-        self.model_kind = (57 if self._sub else 48) + (0, 1, 2, 3, 4, 5, 6, None, 7, 8)[self.slice_kind]      # RRRMC_MODEL_AF_* / RRRMC_MODEL_ASF_*
+        if self.slice_kind == 11:
+            self.model_kind = 101 if self._sub else 100                                                       # RRRMC_MODEL_XENTR_ASF / _AF
+        else:
+            self.model_kind = (57 if self._sub else 48) + (0, 1, 2, 3, 4, 5, 6, None, 7, 8)[self.slice_kind]  # RRRMC_MODEL_AF_* / RRRMC_MODEL_ASF_*
 
 
 class GraphAddSubFields(GraphAddFields):

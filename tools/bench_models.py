@@ -9,6 +9,8 @@
   python tools/bench_models.py sat [R ...]  GraphSAT(1000, 3, 4.2), β = 2: standardMC through the wave and the thread build
   python tools/bench_models.py tle [R ...]  GraphSATTLE(1000, 3, 4.2, 3) and GraphSKTLE(201, 3) beside LE: rrrMC (both builds) and standardMC
   python tools/bench_models.py satre [R ...] GraphSATRE(1001, 3, 4.2, 5) beside GraphPercStepRE(1001, 400, 5): rrrMC, both builds
+  python tools/bench_models.py xentr [R ...] GraphPercXEntr(1001, 400, 1.0), β = 1: standardMC through the wave and the thread build, the table in
+                                            LDS and in global memory, beside GraphPercLinear(1001, 400)
 """
 import json
 import os
@@ -403,6 +405,8 @@ def _timed_legs(pkg, X, R, legs, envs, beta, it, step, seed, reps):
                      "acceptance": float(res[1].mean()) / it, "energy_per_spin": float(res[0][:, -1].mean()) / X.N}
         if not rrr and hasattr(X, "max_conn"):
             out[name]["build"] = eng.sat_build()
+        if not rrr and type(X).__name__ == "GraphPercXEntr":
+            out[name]["build"] = eng.xentr_build()
         eng.close()
     for k in envs:
         os.environ.pop(k, None)
@@ -438,6 +442,27 @@ def bench_satre(Nk=1001, K=3, alpha=4.2, P=400, M=5, gamma=2.0, beta=0.4, iters=
             print(json.dumps(out), flush=True)
 
 
+def bench_xentr(N=1001, P=400, lam=1.0, beta=1.0, iters=1 << 14, step=1 << 8, seed=0x5EED, reps=3):
+    """GraphPercXEntr(1001, 400, λ = 1) under standardMC at β = 1 through both builds (one wavefront per chain, one thread per chain), each with
+    the loss table in LDS and in global memory, and the build the library picks by itself; GraphPercLinear(1001, 400) under the same call beside
+    it for scale.  Kernel iterations/s per chain count: python tools/bench_models.py xentr 8 512 4096 32768"""
+    pkg = entry.load_package()
+    X = pkg.GraphPercXEntr(N, P, lam, seed=seed)
+    XL = pkg.GraphPercLinear(N, P, seed=seed)
+    envs = ("RRRMC_XENTR_NO_WAVE", "RRRMC_XENTR_WAVE", "RRRMC_XENTR_NO_LDS")
+    legs = (("wave", {"RRRMC_XENTR_WAVE": "1"}, False), ("thread", {"RRRMC_XENTR_NO_WAVE": "1"}, False),
+            ("wave_global_table", {"RRRMC_XENTR_WAVE": "1", "RRRMC_XENTR_NO_LDS": "1"}, False),
+            ("thread_global_table", {"RRRMC_XENTR_NO_WAVE": "1", "RRRMC_XENTR_NO_LDS": "1"}, False), ("default", {}, False))
+    for R in ([int(a) for a in sys.argv[2:]] or [8, 512, 4096, 32768]):
+        it = max(step, iters * 1024 // max(R, 1024))
+        out = {"model": "GraphPercXEntr", "N": N, "P": P, "lambda": lam, "beta": beta, "replicas": R, "iters": it}
+        out.update(_timed_legs(pkg, X, R, legs, envs, beta, it, step, seed, reps))
+        print(json.dumps(out), flush=True)
+        out = {"model": "GraphPercLinear", "N": N, "P": P, "beta": beta, "replicas": R, "iters": it}
+        out.update(_timed_legs(pkg, XL, R, (("standard", {}, False),), envs, beta, it, step, seed, reps))
+        print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "sk"
-    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm, "sat": bench_sat, "satre": bench_satre, "tle": bench_tle}[which]()
+    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm, "sat": bench_sat, "satre": bench_satre, "tle": bench_tle, "xentr": bench_xentr}[which]()
