@@ -138,8 +138,14 @@ enum rrrmc_model {
     /* the cross-entropy perceptron (src/graphs/PercXEntr.jl): the model of a context made by rrrmc_ctx_create_perc_xentr (N synapses; K and
        M ignored by rrrmc_ctx_create_multi) */
     RRRMC_MODEL_PERC_XENTR = 66,      /* GraphPercXEntr(N, P, lambda) */
-    /* the two field wrappers over it: made by rrrmc_ctx_create_af with RRRMC_RE_SLICE_PERC_XENTR; selectors of rrrmc_ctx_create_multi.
-       67 .. 99 are unassigned: the wrappers' first eighteen ids are a closed block (48 .. 65), and so are their names */
+    /* the three ensembles over sparse Float64 slices (GraphEANormal: GraphEARE, GraphEALE, GraphEATLE of src/REAliases.jl:43-75,
+       src/LEAliases.jl:43-75, src/TLEAliases.jl:36-68; GraphRRGNormal alike): made by rrrmc_ctx_create_re_f64 / _le_f64 / _tle_f64;
+       selectors of rrrmc_ctx_create_multi (N = Nk, K, M) */
+    RRRMC_MODEL_RE_SPARSE_F64 = 67,   /* GraphRobustEnsemble over (A, J) Float64 slices */
+    RRRMC_MODEL_LE_SPARSE_F64 = 68,   /* GraphLocalEntropy over them */
+    RRRMC_MODEL_TLE_SPARSE_F64 = 69,  /* GraphTopologicalLocalEntropy over them */
+    /* the two field wrappers over GraphPercXEntr: made by rrrmc_ctx_create_af with RRRMC_RE_SLICE_PERC_XENTR; selectors of rrrmc_ctx_create_multi.
+       70 .. 99 are unassigned: the wrappers' first eighteen ids are a closed block (48 .. 65), and so are their names */
     RRRMC_MODEL_XENTR_AF = 100,       /* GraphAddFields(h, GraphPercXEntr) */
     RRRMC_MODEL_XENTR_ASF = 101       /* GraphAddSubFields(h, GraphPercXEntr) */
 };
@@ -157,9 +163,12 @@ enum rrrmc_re_slice {
     RRRMC_RE_SLICE_SAT = 8,         /* GraphSAT (src/graphs/SAT.jl): clauses with rrrmc_set_clauses */
     RRRMC_RE_SLICE_COMM_QU = 9,     /* GraphCommQu (src/graphs/CommQu.jl): patterns and labels with rrrmc_set_comm_patterns; K1, K2 even */
     /* 10 is unassigned, like 7 */
-    RRRMC_RE_SLICE_PERC_XENTR = 11  /* GraphPercXEntr (src/graphs/PercXEntr.jl): patterns with rrrmc_set_patterns, the table with rrrmc_set_loss_table;
+    RRRMC_RE_SLICE_PERC_XENTR = 11, /* GraphPercXEntr (src/graphs/PercXEntr.jl): patterns with rrrmc_set_patterns, the table with rrrmc_set_loss_table;
                                        N odd.  The g of rrrmc_ctx_create_af only: rrrmc_ctx_create_re / _le / _tle / _quant_pattern refuse it
                                        (the reference has no RE, LE or Q alias for this graph) */
+    RRRMC_RE_SLICE_SPARSE_F64 = 12  /* GraphEANormal / GraphRRGNormal (src/graphs/EA.jl:534-680, RRG.jl:503-617): (A, J) with rrrmc_set_graph_f64.
+                                       The slice graph has a K of its own, so these contexts are made by rrrmc_ctx_create_re_f64 / _le_f64 /
+                                       _tle_f64; rrrmc_ctx_create_re / _le / _tle refuse the kind and name that creator */
 };
 
 /* Library ABI version (major*10000 + minor*100 + patch). */
@@ -700,6 +709,27 @@ RRRMC_API int64_t rrrmc_iterations_done(const rrrmc_ctx *ctx);
 RRRMC_API int32_t rrrmc_set_graph_f64(rrrmc_ctx *ctx, const int32_t *A, const double *J);
 /* gen_J(Float64, N, A) do randn() end (RRG.jl:71-96, EA.jl:45-71): one GAUSS-stream normal per bond. J_out[N*K]. */
 RRRMC_API int32_t rrrmc_gen_couplings_gauss(int64_t N, int64_t K, const int32_t *A, uint64_t seed, double *J_out);
+/* gen_J(Float64, N, A) do lo + (hi - lo) * rand() end — the aliases over GraphEANormal draw 4 * rand() - 2 (src/QAliases.jl:60-62,
+ * src/REAliases.jl:53-55): the bond visiting order of rrrmc_gen_couplings_gauss (x < y in table order, mirrored into the first free slot of
+ * row y), draw n = the 53-bit uniform of Philox block n of the UNIFORM stream (the reference's rand is unpinned: the stream is ours).
+ * lo, hi finite, lo < hi.  J_out[N*K].  Needs no device. */
+RRRMC_API int32_t rrrmc_gen_couplings_uniform(int64_t N, int64_t K, const int32_t *A, uint64_t seed, double lo, double hi, double *J_out);
+
+/* ---- The three ensembles over sparse Float64 slices (RRRMC_MODEL_RE_SPARSE_F64 / _LE_ / _TLE_; RRRMC_RE_SLICE_SPARSE_F64) ------
+ * GraphEARE / GraphEALE / GraphEATLE (src/REAliases.jl:43-75, src/LEAliases.jl:43-75, src/TLEAliases.jl:36-68) and the generic constructors
+ * over a GraphEANormal or GraphRRGNormal: every slice (and the centre of the two Local Entropy ensembles) is the one graph (A, J) of Nk sites
+ * with K table entries per site.  A slice keeps its graph's LocalFields{Float64} cache (EA.jl:584-653): the residual of a move is
+ * delta_energy(X1[k], C1[k], i) = -lfields[i], not divided by M; update_cache! follows every flip, and the immediate undo of a rejected
+ * rrrMC move takes its move_last path, which restores the fields bit for bit.  The centre's cache is never updated.
+ *   The creators are rrrmc_ctx_create_re / _le / _tle with a K: 1 <= K <= 8 as rrrmc_ctx_create_quant_f64, and the ensembles' own limits
+ *   (3 <= M <= 32 for the Robust Ensemble, <= 31 for the other two, N <= 65 535).  Then rrrmc_set_graph_f64(ctx, A[Nk x K], J[Nk x K])
+ *   with the checks it applies to a GraphQEAT (ascending rows, no self-loop, finite J, every bond from both ends; a neighbour may repeat:
+ *   L = 2); new couplings end a resumed run.  Then rrrmc_re_set_params / rrrmc_le_set_params, or rrrmc_tle_set_topology and
+ *   rrrmc_tle_set_params in that order: the topology of a GraphEATLE is neighbors(g0, i) = the distinct entries of row A[i], ascending
+ *   (EA.jl:680, TLE.jl:394), which the caller computes.  Samplers and every other entry point as for the other slice kinds. */
+RRRMC_API int32_t rrrmc_ctx_create_re_f64(rrrmc_ctx **out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0);
+RRRMC_API int32_t rrrmc_ctx_create_le_f64(rrrmc_ctx **out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0);
+RRRMC_API int32_t rrrmc_ctx_create_tle_f64(rrrmc_ctx **out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0);
 
 /* ---- DoubleGraphs with discretised Gaussian couplings (RRRMC_MODEL_SPARSE_DISCRETIZED) --------
  * GraphRRGNormalDiscretized{Int,LEV,K} / GraphEANormalDiscretized{Int,LEV,2D}: couplings cJ ~ Normal(0,1) split by

@@ -73,6 +73,17 @@ ens_kind(G, what) = G <: RRRMC.SK.GraphSK ? 1 : G <: RRRMC.SK.GraphSKNormal ? 2 
                     G <: RRRMC.CommStep.GraphCommStep ? 5 : G <: RRRMC.CommReLU.GraphCommReLU ? 6 : G <: RRRMC.SAT.GraphSAT ? 8 :
                     G <: RRRMC.CommQu.GraphCommQu ? 9 :
                     throw(ArgumentError("the engine runs the $what over GraphEmpty, GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, GraphCommStep, GraphCommReLU, GraphCommQu and GraphSAT slices, given: $G"))
+# ... of the three ensembles, which also run over sparse Float64 slices (kind 12: GraphEANormal — the reference's GraphEARE, GraphEALE,
+# GraphEATLE, src/REAliases.jl:43-75, src/LEAliases.jl:43-75, src/TLEAliases.jl:36-68 — and GraphRRGNormal through the generic constructors)
+const ENS_SPARSE_F64 = 12
+const RE_SPARSE_F64, LE_SPARSE_F64, TLE_SPARSE_F64 = 67, 68, 69          # rrrmc_ctx_create_re_f64 / _le_f64 / _tle_f64; multi selectors (N = Nk, K, M)
+ens_kind_f64(G, what) = G <: Union{RRRMC.RRG.GraphRRGNormal,RRRMC.EA.GraphEANormal} ? ENS_SPARSE_F64 : ens_kind(G, what)
+# the shared (A, J) of such slices: K entries per site, 0-based rows as the reference keeps them (ascending)
+function set_graph_f64!(ctx, X1)
+    A = flatA(X1); J = collect(reinterpret(Float64, X1.J))
+    GC.@preserve A J check(ccall((:rrrmc_set_graph_f64, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}), ctx.p, A, J), ctx.p)
+    return ctx
+end
 const XEntrGraph = RRRMC.PercXEntr.GraphPercXEntr
 # the patterns of a cross-entropy perceptron, and its loss table X.Hs ITSELF (PercXEntr.jl:65): the library takes the table as an input, so
 # that the trajectory does not depend on whose log and exp made it
@@ -274,9 +285,16 @@ end
 # spins in the reference's order (site (i-1)M + k = spin i of replica k), so C.s.chunks passes as is; the M slices share one coupling set
 function Ctx(X::RRRMC.RE.GraphRobustEnsemble{M,γ,β,G}, R::Integer; device = 0, replica0 = 0, devices = nothing) where {M,γ,β,G}
     Nk = X.Nk
-    kind = ens_kind(G, "Robust Ensemble")
+    kind = ens_kind_f64(G, "Robust Ensemble")
     ref = Ref{Ptr{Cvoid}}(C_NULL)
-    if devices === nothing
+    if kind == ENS_SPARSE_F64          # GraphEARE: the creator that carries the slice graph's K
+        K = length(X.X1[1].A[1])
+        if devices === nothing
+            check(ccall((:rrrmc_ctx_create_re_f64, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Int64, Int32, UInt32), ref, Nk, K, M, R, device, replica0))
+        else
+            ref[] = create(RE_SPARSE_F64, Nk, K, M, R; replica0 = replica0, devices = devices)
+        end
+    elseif devices === nothing
         check(ccall((:rrrmc_ctx_create_re, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, Int64, Int32, UInt32), ref, Nk, M, kind, R, device, replica0))
     else
         ref[] = create(RE_MODELS[kind + 1], Nk, 0, M, R; replica0 = replica0, devices = devices)
@@ -290,7 +308,8 @@ function Ctx(X::RRRMC.RE.GraphRobustEnsemble{M,γ,β,G}, R::Integer; device = 0,
         Jm = Matrix{Float64}(undef, Nk, Nk); for i = 1:Nk; Jm[:, i] = X1.J[i]; end
         GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
     end
-    kind >= 3 && set_patterns!(ctx, X1)
+    kind == ENS_SPARSE_F64 && set_graph_f64!(ctx, X1)
+    3 <= kind <= 9 && set_patterns!(ctx, X1)
     check(ccall((:rrrmc_re_set_params, LIB), Int32, (Ptr{Cvoid}, Float64, Float64), ctx.p, γ, β), ctx.p)
     return ctx
 end
@@ -460,9 +479,16 @@ re_hook(X::RRRMC.RE.GraphRobustEnsemble, hook) = (it, X_, C, a, b) -> (re_slices
 # γT / 1 is γT exactly
 function Ctx(X::RRRMC.LE.GraphLocalEntropy{M,γT,G}, R::Integer; device = 0, replica0 = 0, devices = nothing) where {M,γT,G}
     Nk = X.Nk
-    kind = ens_kind(G, "Local Entropy ensemble")
+    kind = ens_kind_f64(G, "Local Entropy ensemble")
     ref = Ref{Ptr{Cvoid}}(C_NULL)
-    if devices === nothing
+    if kind == ENS_SPARSE_F64          # GraphEALE
+        K = length(X.X1[1].A[1])
+        if devices === nothing
+            check(ccall((:rrrmc_ctx_create_le_f64, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Int64, Int32, UInt32), ref, Nk, K, M, R, device, replica0))
+        else
+            ref[] = create(LE_SPARSE_F64, Nk, K, M, R; replica0 = replica0, devices = devices)
+        end
+    elseif devices === nothing
         check(ccall((:rrrmc_ctx_create_le, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, Int64, Int32, UInt32), ref, Nk, M, kind, R, device, replica0))
     else
         ref[] = create(LE_MODELS[kind + 1], Nk, 0, M, R; replica0 = replica0, devices = devices)
@@ -476,7 +502,8 @@ function Ctx(X::RRRMC.LE.GraphLocalEntropy{M,γT,G}, R::Integer; device = 0, rep
         Jm = Matrix{Float64}(undef, Nk, Nk); for i = 1:Nk; Jm[:, i] = X1.J[i]; end
         GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
     end
-    kind >= 3 && set_patterns!(ctx, X1)
+    kind == ENS_SPARSE_F64 && set_graph_f64!(ctx, X1)
+    3 <= kind <= 9 && set_patterns!(ctx, X1)
     check(ccall((:rrrmc_le_set_params, LIB), Int32, (Ptr{Cvoid}, Float64, Float64), ctx.p, γT, 1.0), ctx.p)
     return ctx
 end
@@ -519,17 +546,25 @@ re_hook(X::RRRMC.LE.GraphLocalEntropy, hook::Nothing) = hook
 re_hook(X::RRRMC.LE.GraphLocalEntropy, hook) = (it, X_, C, a, b) -> (le_slices!(X, C); hook(it, X_, C, a, b))
 
 # ---- GraphTopologicalLocalEntropy (src/graphs/TLE.jl:351-502): GraphLocalEntropy's layout with the inner graph GraphTLE{M,γT,λT} ---------
-# Graph0TLE, GraphSKTLE and GraphSATTLE (src/TLEAliases.jl) arrive here as GraphTopologicalLocalEntropy{M,γT,λT,G} with G = GraphEmpty,
-# GraphSK, GraphSAT; GraphEATLE (GraphEANormal slices) and the pattern machines are refused by the library (RRRMC_ERR_UNSUPPORTED).  The
-# neighbour lists are X.X0.neighb, 1-based in the reference and 0-based across the ABI, in list order.  γT and λT are type parameters:
+# Graph0TLE, GraphSKTLE, GraphSATTLE and GraphEATLE (src/TLEAliases.jl) arrive here as GraphTopologicalLocalEntropy{M,γT,λT,G} with
+# G = GraphEmpty, GraphSK, GraphSAT, GraphEANormal; the pattern machines are refused by the library (RRRMC_ERR_UNSUPPORTED).  The
+# neighbour lists are X.X0.neighb (for a GraphEATLE: uA, each lattice neighbour once), 1-based in the reference and 0-based across the ABI,
+# in list order.  γT and λT are type parameters:
 # rrrmc_tle_set_params takes (γ, λ, β) = (γT, λT, 1).  The observables go through le_energies / le_cenergy / le_distances.
 const TLE_EMPTY, TLE_SK, TLE_SKN, TLE_SAT = 44, 45, 46, 47       # rrrmc_ctx_create_tle; multi selectors
 const TLE_MODELS = (TLE_EMPTY, TLE_SK, TLE_SKN, 0, 0, 0, 0, 0, TLE_SAT, 0)   # by slice kind 0..9
 function Ctx(X::RRRMC.TLE.GraphTopologicalLocalEntropy{M,γT,λT,G}, R::Integer; device = 0, replica0 = 0, devices = nothing) where {M,γT,λT,G}
     Nk = X.Nk
-    kind = ens_kind(G, "Topological Local Entropy ensemble")
+    kind = ens_kind_f64(G, "Topological Local Entropy ensemble")
     ref = Ref{Ptr{Cvoid}}(C_NULL)
-    if devices === nothing || TLE_MODELS[kind + 1] == 0           # (a slice kind without a selector: the single-device call names the refusal)
+    if kind == ENS_SPARSE_F64          # GraphEATLE
+        K = length(X.X1[1].A[1])
+        if devices === nothing
+            check(ccall((:rrrmc_ctx_create_tle_f64, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Int64, Int32, UInt32), ref, Nk, K, M, R, device, replica0))
+        else
+            ref[] = create(TLE_SPARSE_F64, Nk, K, M, R; replica0 = replica0, devices = devices)
+        end
+    elseif devices === nothing || TLE_MODELS[kind + 1] == 0           # (a slice kind without a selector: the single-device call names the refusal)
         check(ccall((:rrrmc_ctx_create_tle, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, Int64, Int32, UInt32), ref, Nk, M, kind, R, device, replica0))
     else
         ref[] = create(TLE_MODELS[kind + 1], Nk, 0, M, R; replica0 = replica0, devices = devices)
@@ -543,7 +578,8 @@ function Ctx(X::RRRMC.TLE.GraphTopologicalLocalEntropy{M,γT,λT,G}, R::Integer;
         Jm = Matrix{Float64}(undef, Nk, Nk); for i = 1:Nk; Jm[:, i] = X1.J[i]; end
         GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
     end
-    kind >= 3 && set_patterns!(ctx, X1)
+    kind == ENS_SPARSE_F64 && set_graph_f64!(ctx, X1)          # the graph, then the topology, then the parameters
+    3 <= kind <= 9 && set_patterns!(ctx, X1)
     neighb = X.X0.neighb
     rowptr = Int32[0; cumsum(length.(neighb))]
     cols = Int32[i1 - 1 for ni in neighb for i1 in ni]

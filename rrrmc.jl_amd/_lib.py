@@ -43,6 +43,7 @@ SYMBOLS = [
     "rrrmc_ctx_create_tle", "rrrmc_tle_set_topology", "rrrmc_tle_check_topology", "rrrmc_tle_set_params", "rrrmc_tle_tables", "rrrmc_tle_cache", "rrrmc_tle_build",
     "rrrmc_ctx_create_af", "rrrmc_af_set_fields", "rrrmc_af_build", "rrrmc_af_cache",
     "rrrmc_ctx_create_perc_xentr", "rrrmc_set_loss_table", "rrrmc_xentr_build", "rrrmc_perc_step_energy",
+    "rrrmc_ctx_create_re_f64", "rrrmc_ctx_create_le_f64", "rrrmc_ctx_create_tle_f64", "rrrmc_gen_couplings_uniform",
 ]
 
 
@@ -211,6 +212,12 @@ def lib():
     L.rrrmc_set_graph_f64.argtypes = [vp, i32p, f64p]
     L.rrrmc_gen_couplings_gauss.restype = C.c_int32
     L.rrrmc_gen_couplings_gauss.argtypes = [C.c_int64, C.c_int64, i32p, C.c_uint64, f64p]
+    L.rrrmc_gen_couplings_uniform.restype = C.c_int32
+    L.rrrmc_gen_couplings_uniform.argtypes = [C.c_int64, C.c_int64, i32p, C.c_uint64, C.c_double, C.c_double, f64p]
+    for fam in ("re", "le", "tle"):          # the three ensembles over sparse Float64 slices: (out, Nk, K, M, R, device, replica0)
+        fn = getattr(L, "rrrmc_ctx_create_%s_f64" % fam)
+        fn.restype = C.c_int32
+        fn.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_uint32]
     L.rrrmc_set_graph_discretized.restype = C.c_int32
     L.rrrmc_set_graph_discretized.argtypes = [vp, i32p, i8p, f64p, i32p, C.c_int32, C.c_int32]
     L.rrrmc_discretize.restype = C.c_int32

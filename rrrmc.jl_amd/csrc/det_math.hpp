@@ -10,6 +10,7 @@ namespace rrrmc {
 
 constexpr uint32_t TAG_ACCEPT_F64 = 9;
 constexpr uint32_t TAG_GAUSS = 6;
+constexpr uint32_t TAG_UNIFORM = 12;          // host-side uniform couplings (rrrmc_gen_couplings_uniform): block n, 53 bits of words 0 and 1
 
 // rand() of replica `replica` at global iteration g: 53-bit uniform of the ACCEPT_F64 stream
 RRRMC_HD double rand53(uint32_t k0, uint32_t k1, uint64_t g, uint32_t replica)

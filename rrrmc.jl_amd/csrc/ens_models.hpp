@@ -34,10 +34,13 @@ constexpr EnsModel kEnsModels[] = {
     {RRRMC_MODEL_LE_COMM_RELU, ENS_LE, RRRMC_RE_SLICE_COMM_RELU},
     {RRRMC_MODEL_LE_SAT, ENS_LE, RRRMC_RE_SLICE_SAT},
     {RRRMC_MODEL_LE_COMM_QU, ENS_LE, RRRMC_RE_SLICE_COMM_QU},
-    {RRRMC_MODEL_TLE_EMPTY, ENS_TLE, RRRMC_RE_SLICE_EMPTY},          // (the TLE kernels cover these four slice kinds)
+    {RRRMC_MODEL_TLE_EMPTY, ENS_TLE, RRRMC_RE_SLICE_EMPTY},          // (the TLE kernels cover these four slice kinds and the sparse Float64 one below)
     {RRRMC_MODEL_TLE_SK, ENS_TLE, RRRMC_RE_SLICE_SK},
     {RRRMC_MODEL_TLE_SKN, ENS_TLE, RRRMC_RE_SLICE_SKN},
     {RRRMC_MODEL_TLE_SAT, ENS_TLE, RRRMC_RE_SLICE_SAT},
+    {RRRMC_MODEL_RE_SPARSE_F64, ENS_RE, RRRMC_RE_SLICE_SPARSE_F64},          // sparse Float64 slices (GraphEARE, GraphEALE, GraphEATLE)
+    {RRRMC_MODEL_LE_SPARSE_F64, ENS_LE, RRRMC_RE_SLICE_SPARSE_F64},
+    {RRRMC_MODEL_TLE_SPARSE_F64, ENS_TLE, RRRMC_RE_SLICE_SPARSE_F64},
 };
 
 // the ensemble of a model id; ENS_NONE for every model that is not an ensemble

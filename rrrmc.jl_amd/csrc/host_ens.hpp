@@ -8,14 +8,14 @@
 static_assert((int)RE_EMPTY == RRRMC_RE_SLICE_EMPTY && (int)RE_SK == RRRMC_RE_SLICE_SK && (int)RE_SKN == RRRMC_RE_SLICE_SKN, "ReSlice is rrrmc_re_slice");
 static_assert((int)RE_PSTEP == RRRMC_RE_SLICE_PERC_STEP && (int)RE_PLIN == RRRMC_RE_SLICE_PERC_LINEAR, "ReSlice is rrrmc_re_slice");
 static_assert((int)RE_CSTEP == RRRMC_RE_SLICE_COMM_STEP && (int)RE_CRELU == RRRMC_RE_SLICE_COMM_RELU && (int)RE_CQU == RRRMC_RE_SLICE_COMM_QU, "ReSlice is rrrmc_re_slice");
-static_assert((int)RE_SAT == RRRMC_RE_SLICE_SAT, "ReSlice is rrrmc_re_slice");
+static_assert((int)RE_SAT == RRRMC_RE_SLICE_SAT && (int)RE_SPF == RRRMC_RE_SLICE_SPARSE_F64, "ReSlice is rrrmc_re_slice");
 
 // with_slice(Set{}, slice, f) calls f(std::integral_constant<int, S>{}) for the S of the set that equals `slice`, so that a generic lambda can
 // launch kernel<decltype(s)::value>; false when the set has no such S (the table makes that unreachable: callers fail with ens_bad_slice).
 // A kernel template is built once per member of the set it is dispatched over: the TLE kernels over TleSlices, all others over AllSlices.
 template <int... S> struct SliceSet {};
-using AllSlices = SliceSet<RE_EMPTY, RE_SK, RE_SKN, RE_PSTEP, RE_PLIN, RE_CSTEP, RE_CRELU, RE_SAT, RE_CQU>;
-using TleSlices = SliceSet<RE_EMPTY, RE_SK, RE_SKN, RE_SAT>;
+using AllSlices = SliceSet<RE_EMPTY, RE_SK, RE_SKN, RE_PSTEP, RE_PLIN, RE_CSTEP, RE_CRELU, RE_SAT, RE_CQU, RE_SPF>;
+using TleSlices = SliceSet<RE_EMPTY, RE_SK, RE_SKN, RE_SAT, RE_SPF>;
 template <int... S, typename F> bool with_slice(SliceSet<S...>, int slice, F&& f)
 {
     return ((slice == S && (f(std::integral_constant<int, S>{}), true)) || ...);
@@ -124,8 +124,25 @@ template <typename Check> int32_t ens_call_end(rrrmc_ctx* ctx, const ReParams& P
 
 // ---- context creation: a Robust Ensemble has M rows of Nk spins, a Local Entropy ensemble M + 1 (row 0 the centre); a TLE context starts
 //      as a Local Entropy one (tle_ctx_create) ----
-int32_t ens_ctx_create(EnsFamily family, rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0)
+// the table width K of a sparse Float64 slice graph: given by rrrmc_ctx_create_re_f64 / _le_f64 / _tle_f64, not by the creators that carry no K
+struct SliceK { bool given = false; int64_t K = 0; };
+// the sparse Float64 slices of the call's parameters, and whether the LDS build with `base` bytes of its own can stage their state too
+inline void ens_spf_params(const rrrmc_ctx* ctx, ReParams* P)
 {
+    P->A = ctx->d_A; P->Jf = ctx->q_Jf; P->K = (int)ctx->K; P->flf = ctx->q_flf; P->fundo = ctx->q_fundo; P->fml = ctx->q_fml;
+}
+inline size_t ens_spf_lds(const rrrmc_ctx* ctx, size_t base, int64_t rows, ReParams* P)
+{
+    const size_t tot = ((base + 7) & ~(size_t)7) + spf_ens_lds_bytes(rows, ctx->qNk, ctx->K);
+    P->spf_lds = base <= (size_t)kLdsLimit && tot <= (size_t)kLdsLimit ? 1 : 0;          // else the slice state stays in global memory, as RE_SKN's does
+    return P->spf_lds ? tot : base;
+}
+// `creator`: the ensemble whose exported creator was called, where it is not `family` (tle_ctx_create builds on a Local Entropy context)
+int32_t ens_ctx_create(EnsFamily family, rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0, SliceK k = {},
+                       EnsFamily creator = ENS_NONE)
+{
+    const int64_t K = k.K;
+    if (creator == ENS_NONE) creator = family;
     const bool re = family == ENS_RE;
     const char* name = re ? "Robust Ensemble" : "Local Entropy";
     const int Mmax = re ? kReMmax : kLeMmax;
@@ -135,7 +152,13 @@ int32_t ens_ctx_create(EnsFamily family, rrrmc_ctx** out, int64_t Nk, int64_t M,
     const bool comm = slice_kind == RRRMC_RE_SLICE_COMM_STEP || slice_kind == RRRMC_RE_SLICE_COMM_RELU || slice_kind == RRRMC_RE_SLICE_COMM_QU;
     if (ens_model(family, slice_kind) == kEnsNoModel)
         return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind must be RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP, _PERC_LINEAR, _COMM_STEP, _COMM_RELU, _SAT or _COMM_QU, given: %d", slice_kind);
+    const bool spf = slice_kind == RRRMC_RE_SLICE_SPARSE_F64;
+    if (spf && !k.given)
+        return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind RRRMC_RE_SLICE_SPARSE_F64 needs the K of the slice graph: use rrrmc_ctx_create_%s_f64",
+                    creator == ENS_RE ? "re" : creator == ENS_LE ? "le" : "tle");
     if (Nk < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "Nk and R must be >= 1");
+    if (spf && K < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "Nk, K, R must be >= 1");
+    if (spf && K > kContKmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "K=%lld: the Float64 sparse slice kernels cover K <= %d", (long long)K, kContKmax);
     if (perc) { const int32_t rcn = perc_check_n(Nk); if (rcn) return rcn; }
     if (comm) { const int32_t rcn = comm_check_nk(Nk, slice_kind != RRRMC_RE_SLICE_COMM_STEP); if (rcn) return rcn; }
     if (M <= 2) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "M must be greater than 2, given: %lld", (long long)M);      // RE.jl:37, LE.jl:24
@@ -147,7 +170,7 @@ int32_t ens_ctx_create(EnsFamily family, rrrmc_ctx** out, int64_t Nk, int64_t M,
     rrrmc_ctx* ctx = nullptr;
     { const int32_t rcb = ctx_create_begin(&ctx, device, false); if (rcb) return rcb; }
     ctx->model = ens_model(family, slice_kind);
-    ctx->N = N; ctx->K = 0; ctx->R = R; ctx->Rpad = R;
+    ctx->N = N; ctx->K = spf ? K : 0; ctx->R = R; ctx->Rpad = R;
     ctx->qNk = Nk; ctx->qM = M; ctx->qW = 2 * ((N + 63) / 64); ctx->q_Wk = 2 * ((Nk + 63) / 64);
     ctx->replica0 = replica0;
     ctx->graph_set = slice_kind == RRRMC_RE_SLICE_EMPTY;          // Graph0RE / Graph0LE has no couplings to give
@@ -164,6 +187,14 @@ int32_t ens_ctx_create(EnsFamily family, rrrmc_ctx** out, int64_t Nk, int64_t M,
         CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_scur, (size_t)R * (size_t)rows));
     } else if (slice_kind == RRRMC_RE_SLICE_SK) {
         CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_Jb, Nk * ctx->q_Wk));
+    } else if (spf) {
+        // the shared graph, and per chain every row's LocalFields{Float64}: lfields, the K + 1 values of the undo record, move_last
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->d_A, Nk * K));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_Jf, Nk * K));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_flf, (size_t)R * (size_t)rows * (size_t)Nk));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_fundo, (size_t)R * (size_t)rows * (size_t)(K + 1)));
+        CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_fml, (size_t)R * (size_t)rows));
+        CTX_CREATE_TRY(ctx, false, hipMemset(ctx->q_flf, 0, sizeof(double) * (size_t)R * (size_t)rows * (size_t)Nk));          // (a centre row is never built)
     }
     CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->re_tab, (size_t)ntab_d));
     CTX_CREATE_TRY(ctx, false, dev_alloc(ctx, ctx->q_spins, R * ctx->qW));

@@ -31,6 +31,7 @@ ReParams re_params(rrrmc_ctx* ctx, double beta)
     if (slice == RE_PSTEP || slice == RE_PLIN) P.pc = perc_params(ctx, M);
     if (slice == RE_CSTEP || slice == RE_CRELU || slice == RE_CQU) P.cm = comm_params(ctx, M);
     if (slice == RE_SAT) P.sat = sat_table(ctx);
+    if (slice == RE_SPF) ens_spf_params(ctx, &P);
     P.tab = ctx->re_tab; P.etab = ctx->re_tab + M; P.ft = ctx->re_tab + 2 * M + 1;
     P.abi = ctx->q_spins; P.sp = ctx->re_sp; P.mu = ctx->re_mu; P.cls = ctx->q_cls; P.sv = ctx->q_sv; P.spos = ctx->q_spos; P.st = ctx->q_st;
     P.T = ctx->q_T; P.zz = ctx->q_z; P.E_cur = ctx->sk_E; P.acc_rate = ctx->q_accrate; P.stats = ctx->q_stats; P.Es = ctx->sk_Es;
@@ -111,6 +112,7 @@ int32_t re_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, i
         size_t lds = re_rrr_lds_bytes(ctx->N, ctx->qW, ctx->qNk);
         if (P.pc.ds) lds = ((lds + 7) & ~(size_t)7) + perc_lds_bytes(P.pc.rows, P.pc.PW);
         if (P.cm.ds) lds = ((lds + 7) & ~(size_t)7) + comm_lds_bytes(P.cm.rows, P.cm.K2, P.cm.PW, slice == RE_CQU);          // the slices' Stabilities
+        if (slice == RE_SPF) lds = ens_spf_lds(ctx, lds, ctx->qM, &P);          // the slices' LocalFields, when they fit too
         const char* no_lds = std::getenv("RRRMC_RE_NO_LDS");
         const char* want_lds = std::getenv("RRRMC_RE_LDS");
         // perceptron slices: the LDS build at every replica count (its update_cache! is spread over the wavefront; the thread build's is a

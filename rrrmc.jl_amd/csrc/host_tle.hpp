@@ -1,9 +1,9 @@
 // Host side of the Topological Local Entropy ensemble (GraphTopologicalLocalEntropy over GraphEmpty / binary GraphSK / GraphSKNormal /
-// GraphSAT slices, tle_kernels.hpp).  Included by rrrmc_hip.hip inside its anonymous namespace, after host_le.hpp; not a stand-alone
+// GraphSAT / sparse Float64 slices, tle_kernels.hpp).  Included by rrrmc_hip.hip inside its anonymous namespace, after host_le.hpp; not a stand-alone
 // translation unit.  A TLE context is a Local Entropy context (the same spins, μ, slice state, scalars, observables) whose level tables and
 // DeltaECache arrays are sized by rrrmc_tle_set_params — the number of levels depends on the topology and on (γT, λT) — and which adds the
 // neighbour lists, the class-code table, lfields2 and 16-bit class ids.  What the three ensembles share is in host_ens.hpp; the TLE kernels
-// are dispatched over TleSlices, the four slice kinds they are built for.
+// are dispatched over TleSlices, the five slice kinds they are built for.
 
 // Device-memory rule: the sets are dense, [2L][N] 16-bit members per replica, as in the other ensembles; a context whose sets would take
 // more than kTleSetBytesMax in all is refused.
@@ -83,12 +83,13 @@ int32_t tle_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, 
         // (the builds' parity test, timing experiments).
         const char* no_lds = std::getenv("RRRMC_TLE_NO_LDS");
         const char* want_lds = std::getenv("RRRMC_TLE_LDS");
-        const size_t state = tle_rrr_lds_bytes(true, ctx->N, ctx->qW, ctx->qNk, 2 * ctx->tle_L);
+        size_t state = tle_rrr_lds_bytes(true, ctx->N, ctx->qW, ctx->qNk, 2 * ctx->tle_L);
+        if (ens_slice(ctx->model) == RE_SPF) state = ens_spf_lds(ctx, state, ctx->qM + 1, &P);          // with the rows' LocalFields, when they fit too
         int cus = 0;
         HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
         const bool resident = state <= (size_t)kLdsLimit && (size_t)ctx->R <= (size_t)cus * ((size_t)kLdsLimit / state);
         const bool use_lds = state <= (size_t)kLdsLimit && !(no_lds && no_lds[0] == '1') && (resident || (want_lds && want_lds[0] == '1'));
-        const size_t lds = tle_rrr_lds_bytes(use_lds, ctx->N, ctx->qW, ctx->qNk, 2 * ctx->tle_L);
+        const size_t lds = use_lds ? state : tle_rrr_lds_bytes(false, ctx->N, ctx->qW, ctx->qNk, 2 * ctx->tle_L);
         const tle_kernel_fn fn = tle_rrr_fn(ens_slice(ctx->model), use_lds);
         if (!fn) return ens_bad_slice(ctx);
         HIP_TRY(ctx, raise_lds_attr(reinterpret_cast<const void*>(fn), lds));
@@ -99,12 +100,13 @@ int32_t tle_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, 
     return ens_call_end(ctx, P, C, standard, iters, [&] { return tle_debug_check(ctx, P, !standard); });
 }
 
-int32_t tle_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0)
+int32_t tle_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0, SliceK k = {})
 {
     if (!out) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (ens_model(ENS_LE, slice_kind) == kEnsNoModel)          // (the Local Entropy ensemble has every slice kind there is)
         return fail(nullptr, RRRMC_ERR_INVALID_ARG, "slice_kind must be one of rrrmc_re_slice, given: %d", slice_kind);
+    // (the kernels cover sparse Float64 slices too; the text is kept as tests/golden/ens_refusals.json records it, byte for byte)
     if (ens_model(ENS_TLE, slice_kind) == kEnsNoModel)
         return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "slice kind %d: the Topological Local Entropy kernels cover GraphEmpty, GraphSK, GraphSKNormal and GraphSAT slices", slice_kind);
     if (Nk < 1 || R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "Nk and R must be >= 1");
@@ -112,7 +114,7 @@ int32_t tle_ctx_create(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kin
     if (M > kTleMmax) return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "M = %lld: the Topological Local Entropy kernels cover M <= %d", (long long)M, kTleMmax);
     if (Nk * (M + 1) > kTleNmax)
         return fail(nullptr, RRRMC_ERR_UNSUPPORTED, "N = Nk*(M+1) = %lld is beyond the Topological Local Entropy kernels (16-bit set members: N <= 65535)", (long long)(Nk * (M + 1)));
-    const int32_t rc = ens_ctx_create(ENS_LE, out, Nk, M, slice_kind, R, device, replica0);
+    const int32_t rc = ens_ctx_create(ENS_LE, out, Nk, M, slice_kind, R, device, replica0, k, ENS_TLE);
     if (rc) return rc;
     rrrmc_ctx* ctx = *out;
     ctx->model = ens_model(ENS_TLE, slice_kind);

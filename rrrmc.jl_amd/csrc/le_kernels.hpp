@@ -1,6 +1,6 @@
 // gfx950 kernels for the Local Entropy ensemble (src/graphs/LE.jl): GraphLocalEntropy{M,γT,G} = the inner graph GraphLE{M,γT}, which couples
 // each of M replicas of spin i to an explicit reference ("centre") spin, plus a centre graph Xc and M slice graphs X1[k] of one graph G —
-// GraphEmpty (Graph0LE), binary GraphSK (GraphSKLE), GraphSKNormal (src/LEAliases.jl).  Samplers: rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290)
+// GraphEmpty (Graph0LE), binary GraphSK (GraphSKLE), GraphSKNormal, GraphEANormal (GraphEALE) (src/LEAliases.jl).  Samplers: rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290)
 // over the DeltaECache{Float64,L} (src/DeltaE.jl:63-295), standardMC (src/RRRMC.jl:81-127), and the observables LEenergies / cenergy /
 // distances (LE.jl:259-274, 309-318).
 //
@@ -101,6 +101,8 @@ __global__ __launch_bounds__(kReInitThreads) void le_init_kernel(LeParams P, int
         for (int k = tid; k < rows; k += kReInitThreads) { v.smv[k] = -1; v.scur[k] = 0; }
         __syncthreads();
         for (int x = Nk + tid; x < N; x += kReInitThreads) v.slf[(size_t)rows * Nk + x] = 0.0;
+    } else if constexpr (SLICE == RE_SPF) {
+        spf_init_rows(P, v, sp, 1, rows, s_E);                                                // (row 0, the centre: its cache is never used)
     } else if constexpr (kPercSlice<SLICE>) {
         perc_init_rows<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, Nk, N, s_n);          // (row 0, the centre: built, never used)
     } else if constexpr (kCommSlice<SLICE>) {
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(kReInitThreads) void le_init_kernel(LeParams P, int
         double E = (double)s_n0 * P.gT;
         for (int k = 1; k < rows; ++k) {
             if constexpr (SLICE == RE_SK) { long long n = s_n[k]; n /= 2; E += (double)n / P.sN; }
-            else if constexpr (SLICE == RE_SKN) E += s_E[k];
+            else if constexpr (SLICE == RE_SKN || SLICE == RE_SPF) E += s_E[k];
             else if constexpr (kPercSlice<SLICE>) E += perc_energy_of<SLICE == RE_PLIN>(s_n[k], P.pc.sN);
             else if constexpr (kCommSlice<SLICE> || SLICE == RE_SAT) E += (double)s_n[k];
             else E += 0.0;
@@ -209,7 +211,11 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
         __syncthreads();
         sp = l_sp; spos = l_spos; cls = l_cls; mu = l_mu; t = l_t;
     }
-    const RrrView v = re_view(P, sp, r);
+    const RrrView g_v = re_view(P, sp, r);
+    RrrView v = g_v;
+    if constexpr (LDS && SLICE == RE_SPF) {                                        // the rows' LocalFields behind the chain's own arrays, as in re_rrr_kernel
+        if (P.spf_lds) spf_ens_attach(v, reinterpret_cast<char*>(le_lds) + ((le_rrr_lds_bytes(N, P.W, Nk) + 7) & ~(size_t)7), rows);
+    }
     const auto g_pv = re_slice_view<SLICE>(P, r);                                  // PercView, or CommView for committee slices
     auto pv = g_pv;
     if constexpr (LDS && kPercSlice<SLICE>) {
@@ -432,6 +438,9 @@ __global__ __launch_bounds__(kRrrThreads) void le_rrr_kernel(LeParams P)
         for (int i = (int)threadIdx.x; i < nm; i += (int)blockDim.x) g_pv.mk[i] = pv.mk[i];
         for (int i = (int)threadIdx.x; i < nd; i += (int)blockDim.x) g_pv.ds[i] = pv.ds[i];
     }
+    if constexpr (LDS && SLICE == RE_SPF) {
+        if (P.spf_lds) spf_ens_detach(v, g_v, rows);
+    }
     if constexpr (LDS) {
         __syncthreads();
         const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
@@ -545,6 +554,7 @@ __global__ __launch_bounds__(64) void le_check_kernel(LeParams P, int cache)
                 bad = bad || !(dd <= 1e-10 * Nk && dd >= -1e-10 * Nk);
             }
     }
+    if constexpr (SLICE == RE_SPF) bad = bad || spf_state_bad(P, v, sp, 1, rows);
     if constexpr (kPercSlice<SLICE>) bad = bad || perc_state_bad<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, 1, Nk, N);
     if constexpr (kCommSlice<SLICE>) bad = bad || comm_state_bad<comm_kind_of_slice(SLICE)>(P.cm, comm_view<comm_kind_of_slice(SLICE)>(P.cm, r), sp, 1, Nk, N);
     if (cache) {

@@ -1,6 +1,6 @@
 // gfx950 kernels for the Robust Ensemble (src/graphs/RE.jl): GraphRobustEnsemble{M,γ,β,G} = the inner graph GraphRE{M,γ,β}, which couples
 // the M replicas of every spin through μ_i = Σ_k σ_(i,k), plus M slices of one graph G — GraphEmpty (Graph0RE), binary GraphSK (GraphSKRE),
-// GraphSKNormal (src/REAliases.jl:20-38).  Samplers: rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290) with the DeltaECache{Float64,L} over
+// GraphSKNormal (src/REAliases.jl:20-38), GraphEANormal (GraphEARE, :43-75), the pattern machines and GraphSAT.  Samplers: rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290) with the DeltaECache{Float64,L} over
 // ArraySets (src/DeltaE.jl:63-295, src/ArraySets.jl), standardMC (src/RRRMC.jl:81-127), and REenergies (RE.jl:285-301).
 //
 // Layout.  Spins cross the ABI in the reference's order j = i M + k (spin i of replica k, RE.jl:76-95); the kernels work on a
@@ -28,7 +28,8 @@ enum ReSlice { RE_EMPTY = 0, RE_SK = 1, RE_SKN = 2,          // GraphEmpty (Grap
                RE_CSTEP = 5, RE_CRELU = 6,                   // GraphCommStep (GraphCommStepRE), GraphCommReLU (GraphCommReLURE)
                RE_SAT = 8,                                   // GraphSAT (GraphSATRE); 7 is unassigned, as in the ABI
                RE_CQU = 9,                                   // GraphCommQu (GraphCommQuRE)
-               RE_PXE = 11 };                                // GraphPercXEntr: the g of GraphAddFields / GraphAddSubFields only (af_kernels.hpp); 10 is unassigned
+               RE_PXE = 11,                                  // GraphPercXEntr: the g of GraphAddFields / GraphAddSubFields only (af_kernels.hpp); 10 is unassigned
+               RE_SPF = 12 };                                // GraphEANormal / GraphRRGNormal: sparse Float64 couplings (GraphEARE, GraphEALE, GraphEATLE)
 template <int SLICE> constexpr bool kPercSlice = SLICE == RE_PSTEP || SLICE == RE_PLIN;
 template <int SLICE> constexpr bool kCommSlice = SLICE == RE_CSTEP || SLICE == RE_CRELU || SLICE == RE_CQU;
 // slices whose state is a pure function of the configuration, updated once per accepted move by the whole wavefront in the LDS builds
@@ -47,6 +48,12 @@ struct ReParams {
     double* slf;                                            // [R][2][M][Nk]  every slice's lfields / lfields_last (SK.jl:212-276)
     int32_t* smv;                                           // [R][M]         move_last of every slice (-1 = none)
     uint8_t* scur;                                          // [R][M]         which of the two arrays is `lfields`
+    // sparse Float64 slices (GraphEANormal, GraphRRGNormal): the shared graph and every slice's LocalFields{Float64} (EA.jl:584-653)
+    const int32_t* A; const double* Jf; int K;              // [Nk][K] neighbour table (ascending rows, a neighbour may repeat) and couplings
+    double* flf;                                            // [R][M][Nk]     lfields of every slice
+    double* fundo;                                          // [R][M][K+1]    the part of lfields_last the undo path reads
+    int32_t* fml;                                           // [R][M]         move_last of every slice (-1 = none)
+    int spf_lds;                                            // the LDS builds stage flf / fundo / fml in LDS (they fit behind the chain's arrays)
     // tables: host libm (rrrmc_re_tables) and the sampler's class weights
     const double* tab;                                      // [M]    ΔElist(GraphRE): fk(mū) for mū = -(M-1), -(M-3), ..., M-1 (RE.jl:53-56)
     const double* etab;                                     // [M+1]  log(2 cosh(γ μ)) / β for μ = -M, -M+2, ..., M (RE.jl:90-93)
@@ -83,24 +90,60 @@ __device__ __forceinline__ RrrView re_view(const ReParams& P, uint32_t* sp, int 
     v.slf = P.slf ? P.slf + (size_t)r * 2 * P.M * P.Nk : nullptr;
     v.smv = P.smv ? P.smv + (size_t)r * P.M : nullptr;
     v.scur = P.scur ? P.scur + (size_t)r * P.M : nullptr;
+    if (P.Jf) {
+        v.A = P.A; v.K = P.K; v.Jf = P.Jf;
+        v.flf = P.flf + (size_t)r * P.M * P.Nk;
+        v.fundo = P.fundo + (size_t)r * P.M * (P.K + 1);
+        v.fml = P.fml + (size_t)r * P.M;
+    }
     v.nk_magic = (uint32_t)((0x100000000ull + (uint32_t)P.Nk - 1u) / (uint32_t)P.Nk);
     return v;
 }
 
 // delta_energy_residual (RE.jl:303-310) = delta_energy(X1[k], C1[k], i), NOT divided by M: 0 (GraphEmpty), lfields[i] / sqrt(Nk) (GraphSK,
-// SK.jl:137-140, the integer field by popcounts), lfields[i] (GraphSKNormal, SK.jl:278-284)
+// SK.jl:137-140, the integer field by popcounts), lfields[i] (GraphSKNormal, SK.jl:278-284), -lfields[i] (sparse Float64 slices, EA.jl:655-663)
 template <int SLICE>
 __device__ __forceinline__ double re_residual(const RrrView& v, int x, int k, int i)
 {
     if constexpr (SLICE == RE_EMPTY) return 0.0;
     else if constexpr (SLICE == RE_SK) return (double)slice_delta(v, x) / v.sN;
+    else if constexpr (SLICE == RE_SPF) return -v.flf[(size_t)k * v.Nk + i];
     else return v.slf[((size_t)v.scur[k] * v.M + k) * v.Nk + i];
 }
-// the slice graph's update_cache! after the bit flip (spinflip!(X1[k], C1[k], i), RE.jl:246-253); the binary SK field is recomputed
+// the slice graph's update_cache! after the bit flip (spinflip!(X1[k], C1[k], i), RE.jl:246-253); the binary SK field is recomputed.
+// Sparse Float64 slices: GraphQuant's helper (rrr_kernels.hpp) on the same RrrView members, so that the move_last path and the order in
+// which a repeated neighbour receives its bonds are written once.
 template <int SLICE>
 __device__ __forceinline__ void re_slice_update(const RrrView& v, int x)
 {
     if constexpr (SLICE == RE_SKN) skn_update(v, x);
+    else if constexpr (SLICE == RE_SPF) spf_slice_update(v, x);
+}
+// sparse Float64 slices in the LDS builds: bytes of one chain's flf / fundo / fml (rows = M, or M + 1 with a centre), their staging behind
+// `lds` (8-byte aligned) and the copy back at the end of the call.  Called by the whole workgroup.
+__host__ __device__ inline size_t spf_ens_lds_bytes(int64_t rows, int64_t Nk, int64_t K)
+{
+    return (size_t)8 * (size_t)rows * (size_t)(Nk + K + 1) + (size_t)4 * (size_t)rows;
+}
+__device__ inline void spf_ens_attach(RrrView& v, char* lds, int rows)
+{
+    const int nf = rows * v.Nk, nu = rows * (v.K + 1), tid = (int)threadIdx.x, nt = (int)blockDim.x;
+    double* l_lf = reinterpret_cast<double*>(lds);
+    double* l_undo = l_lf + nf;
+    int32_t* l_ml = reinterpret_cast<int32_t*>(l_undo + nu);
+    for (int q = tid; q < nf; q += nt) l_lf[q] = v.flf[q];
+    for (int q = tid; q < nu; q += nt) l_undo[q] = v.fundo[q];
+    for (int q = tid; q < rows; q += nt) l_ml[q] = v.fml[q];
+    __syncthreads();
+    v.flf = l_lf; v.fundo = l_undo; v.fml = l_ml;
+}
+__device__ inline void spf_ens_detach(const RrrView& v, const RrrView& g, int rows)
+{
+    const int nf = rows * v.Nk, nu = rows * (v.K + 1), tid = (int)threadIdx.x, nt = (int)blockDim.x;
+    __syncthreads();
+    for (int q = tid; q < nf; q += nt) g.flf[q] = v.flf[q];
+    for (int q = tid; q < nu; q += nt) g.fundo[q] = v.fundo[q];
+    for (int q = tid; q < rows; q += nt) g.fml[q] = v.fml[q];
 }
 // the same two with the perceptron slices (perc_kernels.hpp), whose state is not part of the RrrView; WAVE: the wavefront-wide update
 template <int SLICE, bool WAVE = false>
@@ -174,6 +217,51 @@ __device__ __forceinline__ int re_class(const double* tab, int M, int L, int mub
 }
 __device__ __forceinline__ double re_class_f(const double* ft, int L, int k) { return k >= L ? ft[k - L] : 1.0; }     // get_class_f
 
+// sparse Float64 slices: lf_x = the sum over row x of the table, in order, of -J σx σy for the slice whose spins start at bit `off` (EA.jl:590-600)
+__device__ __forceinline__ double spf_site_lf(const ReParams& P, const uint32_t* sp, int off, int x)
+{
+    const int K = P.K, sx = 2 * sbit(sp, off + x) - 1;
+    double fl = 0.0;
+    for (int q = 0; q < K; ++q) {
+        const int sy = 2 * sbit(sp, off + P.A[(size_t)x * K + q]) - 1;
+        fl = fl - P.Jf[(size_t)x * K + q] * (double)sx * (double)sy;
+    }
+    return fl;
+}
+// ... their caches rebuilt as energy(X1[k], C1[k]) does (EA.jl:584-611) for rows k0 .. rows - 1, by a whole workgroup: lfields = 2 lf,
+// E1 = (Σ_x lf_x) / 2 summed in site order into s_E[k], the undo record cleared, move_last = none (every row's, an unused centre row included)
+__device__ inline void spf_init_rows(const ReParams& P, const RrrView& v, const uint32_t* sp, int k0, int rows, double* s_E)
+{
+    const int Nk = P.Nk, K = P.K, tid = (int)threadIdx.x, nt = (int)blockDim.x;
+    for (int x = k0 * Nk + tid; x < rows * Nk; x += nt) {
+        const int k = x / Nk;
+        v.flf[x] = spf_site_lf(P, sp, k * Nk, x - k * Nk);
+    }
+    __syncthreads();
+    for (int k = tid; k < rows; k += nt) {
+        if (k >= k0) {
+            double* lf = v.flf + (size_t)k * Nk;
+            double E1 = 0.0;
+            for (int x = 0; x < Nk; ++x) { const double fl = lf[x]; E1 = E1 + fl; lf[x] = 2.0 * fl; }
+            s_E[k] = E1 / 2;
+        }
+        v.fml[k] = -1;
+        for (int q = 0; q <= K; ++q) v.fundo[(size_t)k * (K + 1) + q] = 0.0;
+    }
+    __syncthreads();
+}
+// ... debug mode: the cached fields of rows k0 .. rows - 1 within 1e-10 K of recomputed ones
+__device__ inline bool spf_state_bad(const ReParams& P, const RrrView& v, const uint32_t* sp, int k0, int rows)
+{
+    bool bad = false;
+    for (int k = k0; k < rows; ++k)
+        for (int x = 0; x < P.Nk; ++x) {
+            const double dd = v.flf[(size_t)k * P.Nk + x] - 2 * spf_site_lf(P, sp, k * P.Nk, x);
+            bad = bad || !(dd <= 1e-10 * P.K && dd >= -1e-10 * P.K);
+        }
+    return bad;
+}
+
 // energy(X1[k], C1[k]) of one slice from the slice-major spins: GraphSK n / sqrt(Nk) (SK.jl:62-96), GraphSKNormal recomputed in the
 // reference's order (SK.jl:212-237); 0 for GraphEmpty.  Sequential (REenergies, debug checks).
 template <int SLICE>
@@ -196,6 +284,10 @@ __device__ inline double re_slice_energy(const ReParams& P, const RrrView& v, in
         }
         n /= 2;
         return n;
+    } else if constexpr (SLICE == RE_SPF) {
+        double E1 = 0.0;                                                  // EA.jl:584-611: lf_x in table order, summed in site order, halved
+        for (int x = 0; x < Nk; ++x) E1 = E1 + spf_site_lf(P, v.sp, k * Nk, x);
+        return E1 / 2;
     } else if constexpr (kPercSlice<SLICE>) {
         return perc_row_energy<SLICE == RE_PLIN>(P.pc, v.sp, k * Nk, Nk, P.N);
     } else if constexpr (kCommSlice<SLICE>) {
@@ -286,6 +378,8 @@ __global__ __launch_bounds__(kReInitThreads) void re_init_kernel(ReParams P, int
         }
         __syncthreads();
         for (int x = tid; x < N; x += kReInitThreads) v.slf[(size_t)M * Nk + x] = 0.0;
+    } else if constexpr (SLICE == RE_SPF) {
+        spf_init_rows(P, v, sp, 0, M, s_E);
     } else if constexpr (kPercSlice<SLICE>) {
         perc_init_rows<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, Nk, N, s_n);
     } else if constexpr (kCommSlice<SLICE>) {
@@ -327,7 +421,7 @@ __global__ __launch_bounds__(kReInitThreads) void re_init_kernel(ReParams P, int
         for (int i = 0; i < Nk; ++i) E -= P.etab[(mu[i] + M) >> 1];
         for (int k = 0; k < M; ++k) {
             if constexpr (SLICE == RE_SK) { long long n = s_n[k]; n /= 2; E += (double)n / P.sN; }
-            else if constexpr (SLICE == RE_SKN) E += s_E[k];
+            else if constexpr (SLICE == RE_SKN || SLICE == RE_SPF) E += s_E[k];
             else if constexpr (kPercSlice<SLICE>) E += perc_energy_of<SLICE == RE_PLIN>(s_n[k], P.pc.sN);
             else if constexpr (kCommSlice<SLICE> || SLICE == RE_SAT) E += (double)s_n[k];
             else E += 0.0;
@@ -365,6 +459,8 @@ __host__ __device__ inline size_t re_rrr_lds_bytes(int64_t N, int64_t W, int64_t
 //   Perceptron slices: the Stabilities of the M slices are staged in LDS too, and ALL 64 lanes run the chain with identical values, so
 //   that the O(P) update_cache! of an accepted move is one pattern per lane (perc_update<.., true>); stores name one address wave-wide.
 //   Committee machine slices (comm_kernels.hpp) the same way: their Δ1 / Δ2 and masks in LDS, comm_update<.., true>.
+//   Sparse Float64 slices: lfields, the undo record and move_last of the M slices are staged in LDS when they fit (ReParams::spf_lds) and
+//   written back at the end of the call; lane 0 runs update_cache! there (K + 1 LDS reads and writes instead of scattered HBM/L2 ones).
 template <bool LDS, int LM, int SLICE>
 __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
 {
@@ -400,7 +496,11 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
         __syncthreads();
         sp = l_sp; spos = l_spos; cls = l_cls; mu = l_mu; t = l_t;
     }
-    const RrrView v = re_view(P, sp, r);
+    const RrrView g_v = re_view(P, sp, r);
+    RrrView v = g_v;
+    if constexpr (LDS && SLICE == RE_SPF) {                                        // the slices' LocalFields behind the chain's own arrays
+        if (P.spf_lds) spf_ens_attach(v, reinterpret_cast<char*>(re_lds) + ((re_rrr_lds_bytes(N, P.W, Nk) + 7) & ~(size_t)7), M);
+    }
     const auto g_pv = re_slice_view<SLICE>(P, r);                                  // PercView, or CommView for committee slices
     auto pv = g_pv;
     if constexpr (LDS && kPercSlice<SLICE>) {
@@ -632,6 +732,9 @@ __global__ __launch_bounds__(kRrrThreads) void re_rrr_kernel(ReParams P)
         for (int i = (int)threadIdx.x; i < nm; i += (int)blockDim.x) g_pv.mk[i] = pv.mk[i];
         for (int i = (int)threadIdx.x; i < nd; i += (int)blockDim.x) g_pv.ds[i] = pv.ds[i];
     }
+    if constexpr (LDS && SLICE == RE_SPF) {
+        if (P.spf_lds) spf_ens_detach(v, g_v, M);
+    }
     if constexpr (LDS) {
         __syncthreads();
         const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
@@ -693,7 +796,8 @@ __global__ __launch_bounds__(64) void re_energies_kernel(ReParams P)
 
 // debug mode (rrrmc_set_debug_checks): after a sampler call every replica's energy(X, C) is re-evaluated from its configuration and compared
 // with the tracked E (|ΔE| <= 1e-10, the bound of the reference's check, RRRMC.jl:250); μ, and after rrrMC every site's class and the set
-// sizes, must equal what the configuration gives; GraphSKNormal slices: the cached fields within 1e-10 Nk of recomputed ones.
+// sizes, must equal what the configuration gives; GraphSKNormal slices: the cached fields within 1e-10 Nk of recomputed ones (sparse Float64
+// slices: within 1e-10 K).
 template <int SLICE>
 __global__ __launch_bounds__(64) void re_check_kernel(ReParams P, int cache)
 {
@@ -725,6 +829,7 @@ __global__ __launch_bounds__(64) void re_check_kernel(ReParams P, int cache)
                 bad = bad || !(dd <= 1e-10 * Nk && dd >= -1e-10 * Nk);
             }
     }
+    if constexpr (SLICE == RE_SPF) bad = bad || spf_state_bad(P, v, sp, 0, M);
     if constexpr (kPercSlice<SLICE>) bad = bad || perc_state_bad<SLICE == RE_PLIN>(P.pc, perc_view(P.pc, r), sp, 0, Nk, N);
     if constexpr (kCommSlice<SLICE>) bad = bad || comm_state_bad<comm_kind_of_slice(SLICE)>(P.cm, comm_view<comm_kind_of_slice(SLICE)>(P.cm, r), sp, 0, Nk, N);
     if (cache) {

@@ -1725,6 +1725,12 @@ int32_t rrrmc_ctx_create_re(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slic
     return ens_ctx_create(ENS_RE, out, Nk, M, slice_kind, R, device, replica0);
 }
 
+// ... over sparse Float64 slices (GraphEARE; a GraphRRGNormal alike): the slice graph's K rides along
+int32_t rrrmc_ctx_create_re_f64(rrrmc_ctx** out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0)
+{
+    return ens_ctx_create(ENS_RE, out, Nk, M, RRRMC_RE_SLICE_SPARSE_F64, R, device, replica0, SliceK{true, K});
+}
+
 int32_t rrrmc_re_tables(int64_t M, double gamma, double beta, double* dElist, double* e0)
 {
     if (!dElist || !e0) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "dElist and e0 must not be NULL");
@@ -1942,6 +1948,11 @@ int32_t rrrmc_ctx_create_le(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slic
     return ens_ctx_create(ENS_LE, out, Nk, M, slice_kind, R, device, replica0);
 }
 
+int32_t rrrmc_ctx_create_le_f64(rrrmc_ctx** out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0)
+{
+    return ens_ctx_create(ENS_LE, out, Nk, M, RRRMC_RE_SLICE_SPARSE_F64, R, device, replica0, SliceK{true, K});
+}
+
 int32_t rrrmc_le_tables(int64_t M, double gamma, double beta, double* dElist)
 {
     if (!dElist) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "dElist must not be NULL");
@@ -2027,6 +2038,11 @@ int32_t rrrmc_le_distances(rrrmc_ctx* ctx, int64_t* out)
 int32_t rrrmc_ctx_create_tle(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0)
 {
     return tle_ctx_create(out, Nk, M, slice_kind, R, device, replica0);
+}
+
+int32_t rrrmc_ctx_create_tle_f64(rrrmc_ctx** out, int64_t Nk, int64_t K, int64_t M, int64_t R, int32_t device, uint32_t replica0)
+{
+    return tle_ctx_create(out, Nk, M, RRRMC_RE_SLICE_SPARSE_F64, R, device, replica0, SliceK{true, K});
 }
 
 int32_t rrrmc_tle_check_topology(int64_t Nk, const int32_t* rowptr, const int32_t* cols, int64_t* maxdeg_out)
@@ -2185,6 +2201,9 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : model == RRRMC_MODEL_QUANT_SKN ? rrrmc_ctx_create_quant_skn(&c, N, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_QUANT_F64 ? rrrmc_ctx_create_quant_f64(&c, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : qpat ? rrrmc_ctx_create_quant_pattern(&c, qpat, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : model == RRRMC_MODEL_RE_SPARSE_F64 ? rrrmc_ctx_create_re_f64(&c, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : model == RRRMC_MODEL_LE_SPARSE_F64 ? rrrmc_ctx_create_le_f64(&c, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : model == RRRMC_MODEL_TLE_SPARSE_F64 ? rrrmc_ctx_create_tle_f64(&c, N, K, M, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : re ? rrrmc_ctx_create_re(&c, N, M, ens_slice(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : le ? rrrmc_ctx_create_le(&c, N, M, ens_slice(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : tle ? rrrmc_ctx_create_tle(&c, N, M, ens_slice(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
@@ -3139,8 +3158,10 @@ int32_t rrrmc_set_graph_f64(rrrmc_ctx* ctx, const int32_t* A, const double* J)
     RRRMC_MULTI(ctx, false, rrrmc_set_graph_f64(c, A, J));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qspf = ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_spf;          // the slice graph of a GraphQEAT: (A, J) is Nk x K
-    if (ctx->model != RRRMC_MODEL_SPARSE_F64 && !qspf) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph_f64 is for RRRMC_MODEL_SPARSE_F64 (or a context made by rrrmc_ctx_create_quant_f64)");
+    // the slice graph of a GraphQEAT, or of an ensemble over sparse Float64 slices (GraphEARE, GraphEALE, GraphEATLE): (A, J) is Nk x K
+    const bool espf = ens_slice(ctx->model) == RRRMC_RE_SLICE_SPARSE_F64;
+    const bool qspf = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_spf) || espf;
+    if (ctx->model != RRRMC_MODEL_SPARSE_F64 && !qspf) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph_f64 is for RRRMC_MODEL_SPARSE_F64 (or a context made by rrrmc_ctx_create_quant_f64 / _re_f64 / _le_f64 / _tle_f64)");
     if (!A || !J) return fail(ctx, RRRMC_ERR_INVALID_ARG, "A and J must not be NULL");
     const int64_t N = qspf ? ctx->qNk : ctx->N, K = ctx->K;
     for (int64_t q = 0; q < N * K; ++q) {
@@ -3165,6 +3186,7 @@ int32_t rrrmc_set_graph_f64(rrrmc_ctx* ctx, const int32_t* A, const double* J)
     if (qspf) {
         HIP_TRY(ctx, hipMemcpy(ctx->q_Jf, J, sizeof(double) * N * K, hipMemcpyHostToDevice));
         ctx->q_cache_valid = false;
+        if (espf) ctx->std_cache_live = false;
         ctx->graph_set = true;
         return RRRMC_OK;
     }
@@ -3199,6 +3221,34 @@ int32_t rrrmc_gen_couplings_gauss(int64_t N, int64_t K, const int32_t* A, uint64
                 J_out[x * K + k] = Jxy; filled[x * K + k] = 1;
                 int64_t l = 0;
                 while (l < K && filled[y * K + l]) ++l;          // findfirst(==(m), J[y]): RRG.jl:84
+                if (l == K) return RRRMC_ERR_INVALID_ARG;
+                J_out[y * K + l] = Jxy; filled[y * K + l] = 1;
+            }
+        }
+    for (int64_t q = 0; q < N * K; ++q) if (!filled[q]) return RRRMC_ERR_INVALID_ARG;
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_gen_couplings_uniform(int64_t N, int64_t K, const int32_t* A, uint64_t seed, double lo, double hi, double* J_out)
+{
+    // the bond order of rrrmc_gen_couplings_gauss; draw n is lo + (hi - lo) u with u the 53-bit uniform of block n of the UNIFORM stream
+    if (N < 1 || K < 1 || !A || !J_out || !std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return RRRMC_ERR_INVALID_ARG;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    std::vector<uint8_t> filled((size_t)(N * K), 0);
+    uint64_t ndraw = 0;
+    for (int64_t x = 0; x < N; ++x)
+        for (int64_t k = 0; k < K; ++k) {
+            const int64_t y = A[x * K + k];
+            if (y < 0 || y >= N) return RRRMC_ERR_INVALID_ARG;
+            if (x < y) {
+                const Philox4 o = philox4x32_10((uint32_t)ndraw, (uint32_t)(ndraw >> 32), 0u, TAG_UNIFORM, k0, k1);
+                ++ndraw;
+                const double u = (double)((((uint64_t)o.w[0] << 32) | o.w[1]) >> 11) * 0x1.0p-53;
+                const double Jxy = lo + (hi - lo) * u;
+                if (filled[x * K + k]) return RRRMC_ERR_INVALID_ARG;
+                J_out[x * K + k] = Jxy; filled[x * K + k] = 1;
+                int64_t l = 0;
+                while (l < K && filled[y * K + l]) ++l;          // findfirst(==(m), J[y]): EA.jl:64
                 if (l == K) return RRRMC_ERR_INVALID_ARG;
                 J_out[y * K + l] = Jxy; filled[y * K + l] = 1;
             }

@@ -1,6 +1,6 @@
 // gfx950 kernels for the Topological Local Entropy ensemble (src/graphs/TLE.jl): GraphTopologicalLocalEntropy{M,γT,λT,G} = the inner graph
 // GraphTLE{M,γT,λT} plus a centre graph and M slice graphs of one graph G — GraphEmpty (Graph0TLE), binary GraphSK (GraphSKTLE), GraphSKNormal,
-// GraphSAT (GraphSATTLE, src/TLEAliases.jl).  Samplers: rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290) over the DeltaECache{Float64,L}
+// GraphSAT (GraphSATTLE, src/TLEAliases.jl), GraphEANormal (GraphEATLE; its ∂i is uA[i], each lattice neighbour once).  Samplers: rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290) over the DeltaECache{Float64,L}
 // (src/DeltaE.jl:63-295) and standardMC (src/RRRMC.jl:81-127); the observables are LE's kernel (TLEenergies / cenergy / distances read the
 // slices only, TLE.jl:437-502).
 //
@@ -112,6 +112,8 @@ __global__ __launch_bounds__(kReInitThreads) void tle_init_kernel(TleParams P, i
         for (int k = tid; k < rows; k += kReInitThreads) { v.smv[k] = -1; v.scur[k] = 0; }
         __syncthreads();
         for (int x = Nk + tid; x < N; x += kReInitThreads) v.slf[(size_t)rows * Nk + x] = 0.0;
+    } else if constexpr (SLICE == RE_SPF) {
+        spf_init_rows(P, v, sp, 1, rows, s_E);
     } else if constexpr (SLICE == RE_SAT) {
         sat_init_rows(P.sat, sp, Nk, 1, rows, s_n);
     }
@@ -146,7 +148,7 @@ __global__ __launch_bounds__(kReInitThreads) void tle_init_kernel(TleParams P, i
         double E = (double)s_n0 * P.gT + (double)rr * P.lT;
         for (int k = 1; k < rows; ++k) {
             if constexpr (SLICE == RE_SK) { long long n = s_n[k]; n /= 2; E += (double)n / P.sN; }
-            else if constexpr (SLICE == RE_SKN) E += s_E[k];
+            else if constexpr (SLICE == RE_SKN || SLICE == RE_SPF) E += s_E[k];
             else if constexpr (SLICE == RE_SAT) E += (double)s_n[k];
             else E += 0.0;
         }
@@ -231,7 +233,11 @@ __global__ __launch_bounds__(kTleWave) void tle_rrr_kernel(TleParams P)
         __syncthreads();
         sp = l_sp; mu = l_mu; lf2 = l_lf2; cls = l_cls; spos = l_spos; t = l_t; T = l_T;
     }
-    const RrrView v = re_view(P, sp, r);
+    const RrrView g_v = re_view(P, sp, r);
+    RrrView v = g_v;
+    if constexpr (LDS && SLICE == RE_SPF) {                                        // the rows' LocalFields behind the chain's own arrays, as in re_rrr_kernel
+        if (P.spf_lds) spf_ens_attach(v, reinterpret_cast<char*>(tle_lds) + ((tle_rrr_lds_bytes(true, N, P.W, Nk, L2) + 7) & ~(size_t)7), rows);
+    }
     const auto pv = re_slice_view<SLICE>(P, r);
     const uint32_t rep = P.replica0 + (uint32_t)r;
     const double* tab = P.tab;
@@ -415,6 +421,9 @@ __global__ __launch_bounds__(kTleWave) void tle_rrr_kernel(TleParams P)
         P.zz[r] = z; P.E_cur[r] = E; P.acc_rate[r] = acc_rate;
         P.stats[(size_t)r * 2] = accepted; P.stats[(size_t)r * 2 + 1] = staged_its;
     }
+    if constexpr (LDS && SLICE == RE_SPF) {
+        if (P.spf_lds) spf_ens_detach(v, g_v, rows);
+    }
     if constexpr (LDS) {
         for (int i = lane; i < L2; i += kTleWave) { g_T[i] = T[i]; g_t[i] = t[i]; }
         for (int i = lane; i < N; i += kTleWave) { g_lf2[i] = lf2[i]; g_spos[i] = spos[i]; g_cls[i] = cls[i]; }
@@ -521,6 +530,7 @@ __global__ __launch_bounds__(64) void tle_check_kernel(TleParams P, int cache)
                 bad = bad || !(dd <= 1e-10 * Nk && dd >= -1e-10 * Nk);
             }
     }
+    if constexpr (SLICE == RE_SPF) bad = bad || spf_state_bad(P, v, sp, 1, rows);
     if (cache) {
         long long tot = 0;
         for (int k = 0; k < 2 * L; ++k) { const int c = P.st[(size_t)r * 2 * L + k]; bad = bad || c < 0 || c > N; tot += c; }

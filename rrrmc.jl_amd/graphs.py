@@ -921,9 +921,79 @@ def _ensemble_slice_kind(slice_graph):
         return 9            # RRRMC_RE_SLICE_COMM_QU
     if isinstance(slice_graph, GraphPercXEntr):
         return 11           # RRRMC_RE_SLICE_PERC_XENTR (10 is unassigned; the g of the field wrappers only)
+    if isinstance(slice_graph, _SparseF64Graph):
+        return 12           # RRRMC_RE_SLICE_SPARSE_F64: GraphEANormal / GraphRRGNormal slices (GraphEARE, GraphEALE, GraphEATLE)
     return (0 if slice_graph is None else 1 if isinstance(slice_graph, GraphSK) else 2 if isinstance(slice_graph, GraphSKNormal)
             else 3 if isinstance(slice_graph, GraphPercStep) else 4 if isinstance(slice_graph, GraphPercLinear)
             else 5 if isinstance(slice_graph, GraphCommStep) else 6)
+
+
+def _check_sparse_slice(X1):
+    """What the ensembles ask of a sparse Float64 slice graph before any device call: the rows of ``A`` ascending, in range and without
+    self-loops (EA.jl:46, RRG.jl:64; ``rrrmc_set_graph_f64`` checks the same, and the symmetry of ``(A, J)``, at upload), finite couplings,
+    and an even row length for a ``GraphEANormal`` (EA.jl:541-542).  Returns ``neighbors(g0, i)`` of every site: the distinct entries of
+    row ``A[i]``, ascending (EA.jl:680) — D entries, not 2D, when L = 2."""
+    A, J = X1.A, X1.J
+    N, K = A.shape
+    if isinstance(X1, GraphEANormal) and K % 2:
+        raise ValueError("twoD must be even, given: %d" % K)                            # EA.jl:542
+    if K < 1 or K > 8:
+        raise ValueError("K = %d: the sparse Float64 slices of an ensemble take 1 <= K <= 8" % K)
+    if ((A < 0) | (A >= N)).any():
+        raise ValueError("invalid A, all elements must be between 1 and %d" % N)
+    if (np.diff(A, axis=1) < 0).any():
+        raise ValueError("invalid A, row %d is not sorted" % (int(np.nonzero((np.diff(A, axis=1) < 0).any(axis=1))[0][0]) + 1))
+    if (A == np.arange(N)[:, None]).any():
+        raise ValueError("invalid A, site %d neighbours itself" % (int(np.nonzero((A == np.arange(N)[:, None]).any(axis=1))[0][0]) + 1))
+    if not np.isfinite(J).all():
+        raise ValueError("J must be finite")
+    return [[int(j) for j in np.unique(A[i])] for i in range(N)]
+
+
+def _ea_slice_graph(alias, args, n_params, seed):
+    """the slice graph of GraphEARE / GraphEALE / GraphEATLE and the remaining arguments: (L, D, ...) draws J = 4 rand() - 2 per bond
+    (``rrrmc_gen_couplings_uniform``; src/REAliases.jl:50-59), (fname, ...) reads ``gen_AJ``'s text format, (X::GraphEANormal, ...) keeps
+    ``X.A``, ``X.J`` (:61-75)"""
+    if isinstance(args[0], (str, GraphEANormal)):
+        if len(args) != 1 + n_params:
+            raise TypeError("%s: expected (X | fname, M, ...) with %d parameters" % (alias, n_params))
+        X1 = GraphEANormal(args[0]) if isinstance(args[0], str) else args[0]
+        return X1, args[1:]
+    if len(args) != 2 + n_params:
+        raise TypeError("%s: expected (L, D, M, ...) with %d parameters" % (alias, n_params))
+    L, D = args[:2]
+    if D < 1:
+        raise ValueError("D must be ≥ 0, given: %d" % D)                                # REAliases.jl:51 (the reference's message)
+    N, K = int(L) ** int(D), 2 * int(D)
+    A = np.zeros((N, K), np.int32)
+    check(lib().rrrmc_gen_ea(L, D, A))
+    J = np.zeros((N, K), np.float64)
+    check(lib().rrrmc_gen_couplings_uniform(N, K, A, seed, -2.0, 2.0, J.reshape(-1)))
+    X1 = GraphEANormal.from_AJ(A, J)
+    X1.L, X1.D = int(L), int(D)
+    return X1, args[2:]
+
+
+def GraphEARE(*args, seed=DEFAULT_SEED):
+    """``GraphEARE(L, D, M, γ, β)`` / ``GraphEARE(fname, M, γ, β)`` / ``GraphEARE(X::GraphEANormal, M, γ, β)`` (src/REAliases.jl:43-75): a
+    Robust Ensemble of M replicas of one Edwards-Anderson lattice with Float64 couplings, uniform in [-2, 2) in the first form."""
+    X1, (M, gamma, beta) = _ea_slice_graph("GraphEARE", args, 3, seed)
+    return GraphRobustEnsemble(X1.N, M, gamma, beta, X1)
+
+
+def GraphEALE(*args, seed=DEFAULT_SEED):
+    """``GraphEALE(L, D, M, γ, β)`` / ``GraphEALE(fname, M, γ, β)`` / ``GraphEALE(X::GraphEANormal, M, γ, β)`` (src/LEAliases.jl:43-75): the
+    Local Entropy ensemble over the same lattice; the centre and the M replicas share ``(A, J)``."""
+    X1, (M, gamma, beta) = _ea_slice_graph("GraphEALE", args, 3, seed)
+    return GraphLocalEntropy(X1.N, M, gamma, beta, X1)
+
+
+def GraphEATLE(*args, seed=DEFAULT_SEED):
+    """``GraphEATLE(L, D, M, γ, λ, β)`` / ``GraphEATLE(fname, M, γ, λ, β)`` / ``GraphEATLE(X::GraphEANormal, M, γ, λ, β)``
+    (src/TLEAliases.jl:36-68): the Topological Local Entropy ensemble over the lattice; ∂i is the lattice neighbourhood of i (each
+    neighbour once: D entries at L = 2)."""
+    X1, (M, gamma, lam, beta) = _ea_slice_graph("GraphEATLE", args, 4, seed)
+    return GraphTopologicalLocalEntropy(X1.N, M, gamma, lam, beta, X1)
 
 
 def _pattern_ensemble(ens, G, sig, args, family=None, **kw):
@@ -1104,7 +1174,10 @@ class GraphRobustEnsemble(_DeviceGraph):
     _rrr_classes = property(lambda self: 2 * ((self.M + 1) // 2))
 
     def _create(self, ctx, R, device, replica0):
-        check(lib().rrrmc_ctx_create_re(ctx, self.Nk, self.M, self.slice_kind, R, device, replica0))
+        if self.slice_kind == 12:          # sparse Float64 slices: the creator that carries K
+            check(lib().rrrmc_ctx_create_re_f64(ctx, self.Nk, self.K, self.M, R, device, replica0))
+        else:
+            check(lib().rrrmc_ctx_create_re(ctx, self.Nk, self.M, self.slice_kind, R, device, replica0))
 
     def _multi_args(self):
         return self.model_kind, self.Nk, self.K, self.M
@@ -1117,16 +1190,19 @@ class GraphRobustEnsemble(_DeviceGraph):
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
             raise ValueError("M must be greater than 2, given: %d" % M)                  # RE.jl:37
-        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT)):
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT, _SparseF64Graph)):
             raise TypeError("the slices of a GraphRobustEnsemble are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, "
-                            "GraphCommStep, GraphCommReLU, GraphCommQu or GraphSAT")
+                            "GraphCommStep, GraphCommReLU, GraphCommQu, GraphSAT, GraphEANormal or GraphRRGNormal")
         if slice_graph is not None and slice_graph.N != int(Nk):
             raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
         self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
         self.N = self.Nk * self.M
         self.X1 = slice_graph
         self.slice_kind = _ensemble_slice_kind(slice_graph)
-        self.model_kind = (11, 12, 13, 19, 20, 25, 26, None, 34, 37)[self.slice_kind]  # RRRMC_MODEL_RE_EMPTY / _SK / _SKN / _PERC_* / _COMM_* / _SAT / _COMM_QU
+        self.model_kind = (11, 12, 13, 19, 20, 25, 26, None, 34, 37, None, None, 67)[self.slice_kind]  # RRRMC_MODEL_RE_EMPTY / _SK / _SKN / _PERC_* / _COMM_* / _SAT / _COMM_QU / _SPARSE_F64
+        if self.slice_kind == 12:
+            _check_sparse_slice(slice_graph)
+            self.K = slice_graph.K                      # rrrmc_ctx_create_re_f64 and rrrmc_ctx_create_multi carry the slice graph's K
         self.J = getattr(slice_graph, "J", None)
         self._engine = None                             # the Engine running this graph: REenergies reads the live configuration there
 
@@ -1169,7 +1245,10 @@ class GraphLocalEntropy(_DeviceGraph):
     _rrr_classes = property(lambda self: 2 * (self.M // 2 + 2 if self.M % 2 == 0 else (self.M + 1) // 2))
 
     def _create(self, ctx, R, device, replica0):
-        check(lib().rrrmc_ctx_create_le(ctx, self.Nk, self.M, self.slice_kind, R, device, replica0))
+        if self.slice_kind == 12:          # sparse Float64 slices: the creator that carries K
+            check(lib().rrrmc_ctx_create_le_f64(ctx, self.Nk, self.K, self.M, R, device, replica0))
+        else:
+            check(lib().rrrmc_ctx_create_le(ctx, self.Nk, self.M, self.slice_kind, R, device, replica0))
 
     def _multi_args(self):
         return self.model_kind, self.Nk, self.K, self.M
@@ -1182,9 +1261,9 @@ class GraphLocalEntropy(_DeviceGraph):
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
             raise ValueError("M must be greater than 2, given: %d" % M)                  # LE.jl:24
-        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT)):
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT, _SparseF64Graph)):
             raise TypeError("the slices of a GraphLocalEntropy are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, "
-                            "GraphCommStep, GraphCommReLU, GraphCommQu or GraphSAT")
+                            "GraphCommStep, GraphCommReLU, GraphCommQu, GraphSAT, GraphEANormal or GraphRRGNormal")
         if slice_graph is not None and slice_graph.N != int(Nk):
             raise ValueError("the slice graph has %d spins, expected Nk = %d" % (slice_graph.N, Nk))
         self.Nk, self.M, self.gamma, self.beta = int(Nk), int(M), float(gamma), float(beta)
@@ -1192,7 +1271,10 @@ class GraphLocalEntropy(_DeviceGraph):
         self.N = self.Nk * (self.M + 1)
         self.X1 = slice_graph
         self.slice_kind = _ensemble_slice_kind(slice_graph)
-        self.model_kind = (14, 15, 16, 21, 22, 27, 28, None, 35, 38)[self.slice_kind]  # RRRMC_MODEL_LE_EMPTY / _SK / _SKN / _PERC_* / _COMM_* / _SAT / _COMM_QU
+        self.model_kind = (14, 15, 16, 21, 22, 27, 28, None, 35, 38, None, None, 68)[self.slice_kind]  # RRRMC_MODEL_LE_EMPTY / _SK / _SKN / _PERC_* / _COMM_* / _SAT / _COMM_QU / _SPARSE_F64
+        if self.slice_kind == 12:
+            _check_sparse_slice(slice_graph)
+            self.K = slice_graph.K                      # rrrmc_ctx_create_le_f64 and rrrmc_ctx_create_multi carry the slice graph's K
         self.J = getattr(slice_graph, "J", None)
         self._engine = None                             # the Engine running this graph: the observables read the live configuration there
 
@@ -1248,7 +1330,10 @@ class GraphTopologicalLocalEntropy(_DeviceGraph):
     K = 0
 
     def _create(self, ctx, R, device, replica0):
-        check(lib().rrrmc_ctx_create_tle(ctx, self.Nk, self.M, self.slice_kind, R, device, replica0))
+        if self.slice_kind == 12:          # sparse Float64 slices: the creator that carries K
+            check(lib().rrrmc_ctx_create_tle_f64(ctx, self.Nk, self.K, self.M, R, device, replica0))
+        else:
+            check(lib().rrrmc_ctx_create_tle(ctx, self.Nk, self.M, self.slice_kind, R, device, replica0))
 
     def _multi_args(self):
         return self.model_kind, self.Nk, self.K, self.M
@@ -1260,8 +1345,8 @@ class GraphTopologicalLocalEntropy(_DeviceGraph):
         check(lib().rrrmc_tle_set_params(ctx, self.gamma, self.lam, self.beta), ctx)
 
     def __init__(self, Nk, M, gamma, lam, beta, slice_graph=None):
-        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, GraphSAT)):
-            raise TypeError("the slices of a GraphTopologicalLocalEntropy are GraphEmpty (None), GraphSK, GraphSKNormal or GraphSAT")
+        if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, GraphSAT, _SparseF64Graph)):
+            raise TypeError("the slices of a GraphTopologicalLocalEntropy are GraphEmpty (None), GraphSK, GraphSKNormal, GraphSAT, GraphEANormal or GraphRRGNormal")
         if slice_graph is not None and slice_graph.N != int(Nk):
             raise ValueError("expected %d spins, got %d" % (Nk, slice_graph.N))           # TLE.jl:392
         self.Nk, self.M, self.gamma, self.lam, self.beta = int(Nk), int(M), float(gamma), float(lam), float(beta)
@@ -1269,6 +1354,9 @@ class GraphTopologicalLocalEntropy(_DeviceGraph):
             neighb = [[] for _ in range(self.Nk)]
         elif isinstance(slice_graph, GraphSAT):
             neighb = [list(ni) for ni in slice_graph.neighb]
+        elif isinstance(slice_graph, _SparseF64Graph):
+            neighb = _check_sparse_slice(slice_graph)                                     # uA[i]: neighbors(g0, i), EA.jl:680, TLE.jl:394
+            self.K = slice_graph.K
         else:
             neighb = [[j for j in range(self.Nk) if j != i] for i in range(self.Nk)]      # AllButOne
         _tle_check_neighb(self.Nk, self.M, neighb)
@@ -1277,7 +1365,7 @@ class GraphTopologicalLocalEntropy(_DeviceGraph):
         self.N = self.Nk * (self.M + 1)
         self.X1 = slice_graph
         self.slice_kind = _ensemble_slice_kind(slice_graph)
-        self.model_kind = {0: 44, 1: 45, 2: 46, 8: 47}[self.slice_kind]                   # RRRMC_MODEL_TLE_EMPTY / _SK / _SKN / _SAT
+        self.model_kind = {0: 44, 1: 45, 2: 46, 8: 47, 12: 69}[self.slice_kind]           # RRRMC_MODEL_TLE_EMPTY / _SK / _SKN / _SAT / _SPARSE_F64
         self.J = getattr(slice_graph, "J", None)
         self.max_deg = max(len(ni) for ni in neighb)
         self._rowptr = np.zeros(self.Nk + 1, np.int32)

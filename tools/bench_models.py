@@ -11,6 +11,8 @@
   python tools/bench_models.py satre [R ...] GraphSATRE(1001, 3, 4.2, 5) beside GraphPercStepRE(1001, 400, 5): rrrMC, both builds
   python tools/bench_models.py xentr [R ...] GraphPercXEntr(1001, 400, 1.0), β = 1: standardMC through the wave and the thread build, the table in
                                             LDS and in global memory, beside GraphPercLinear(1001, 400)
+  python tools/bench_models.py eare [R ...] GraphEARE / GraphEATLE(10, 3, 5) at β = 0.8 and 0.2 beside GraphSKRE(1024, 5): rrrMC (both builds)
+                                            and standardMC
 """
 import json
 import os
@@ -463,6 +465,24 @@ def bench_xentr(N=1001, P=400, lam=1.0, beta=1.0, iters=1 << 14, step=1 << 8, se
         print(json.dumps(out), flush=True)
 
 
+def bench_eare(L=10, D=3, M=5, gamma=1.5, lam=0.2, betas=(0.8, 0.2), iters=1 << 14, step=1 << 12, seed=0x5EED, reps=3):
+    """GraphEARE(10, 3, 5) and GraphEATLE(10, 3, 5) (Nk = 1000, K = 6; γ = 1.5, λ = 0.2, graph β = sampler β = 0.8 and 0.2) under rrrMC through
+    the global and the LDS build and under standardMC, beside GraphSKRE(1024, 5) at bench_re's point (γ = 2, β = 0.4) from the same build in
+    the same job: kernel iterations/s per chain count (python tools/bench_models.py eare 8 512 4096; profiles/r18/sparse_ens.md)."""
+    pkg = entry.load_package()
+    models = [("GraphSKRE", pkg.GraphSKRE(1024, M, 2.0, 0.4, seed=seed), ("RRRMC_RE_NO_LDS", "RRRMC_RE_LDS"), 0.4)]
+    for beta in betas:
+        models.append(("GraphEARE", pkg.GraphEARE(L, D, M, gamma, beta, seed=seed), ("RRRMC_RE_NO_LDS", "RRRMC_RE_LDS"), beta))
+        models.append(("GraphEATLE", pkg.GraphEATLE(L, D, M, gamma, lam, beta, seed=seed), ("RRRMC_TLE_NO_LDS", "RRRMC_TLE_LDS"), beta))
+    for R in ([int(a) for a in sys.argv[2:]] or [8, 512, 4096]):
+        it = max(step, iters * 1024 // max(R, 1024))
+        for model, X, envs, b in models:
+            legs = (("rrr_global", {envs[0]: "1"}, True), ("rrr_lds", {envs[1]: "1"}, True), ("rrr_default", {}, True), ("standard", {}, False))
+            out = {"model": model, "Nk": X.Nk, "M": M, "beta": b, "replicas": R, "iters": it}
+            out.update(_timed_legs(pkg, X, R, legs, envs, b, it, step, seed, reps))
+            print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "sk"
-    {"sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm, "sat": bench_sat, "satre": bench_satre, "tle": bench_tle, "xentr": bench_xentr}[which]()
+    {"eare": bench_eare, "sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm, "sat": bench_sat, "satre": bench_satre, "tle": bench_tle, "xentr": bench_xentr}[which]()
