@@ -147,7 +147,12 @@ enum rrrmc_model {
     /* the two field wrappers over GraphPercXEntr: made by rrrmc_ctx_create_af with RRRMC_RE_SLICE_PERC_XENTR; selectors of rrrmc_ctx_create_multi.
        70 .. 99 are unassigned: the wrappers' first eighteen ids are a closed block (48 .. 65), and so are their names */
     RRRMC_MODEL_XENTR_AF = 100,       /* GraphAddFields(h, GraphPercXEntr) */
-    RRRMC_MODEL_XENTR_ASF = 101       /* GraphAddSubFields(h, GraphPercXEntr) */
+    RRRMC_MODEL_XENTR_ASF = 101,      /* GraphAddSubFields(h, GraphPercXEntr) */
+    /* GraphMixed (src/graphs/Mixed.jl) and the two field wrappers over it: the models of contexts made by rrrmc_ctx_create_mixed /
+       rrrmc_ctx_create_mixed_multi (rrrmc_ctx_create_multi cannot carry a component list and refuses them) */
+    RRRMC_MODEL_MIXED = 102,          /* GraphMixed(graphs...) */
+    RRRMC_MODEL_MIXED_AF = 103,       /* GraphAddFields(h, GraphMixed(graphs...)) */
+    RRRMC_MODEL_MIXED_ASF = 104       /* GraphAddSubFields(h, GraphMixed(graphs...)) */
 };
 
 /* slice families of rrrmc_ctx_create_re */
@@ -166,9 +171,11 @@ enum rrrmc_re_slice {
     RRRMC_RE_SLICE_PERC_XENTR = 11, /* GraphPercXEntr (src/graphs/PercXEntr.jl): patterns with rrrmc_set_patterns, the table with rrrmc_set_loss_table;
                                        N odd.  The g of rrrmc_ctx_create_af only: rrrmc_ctx_create_re / _le / _tle / _quant_pattern refuse it
                                        (the reference has no RE, LE or Q alias for this graph) */
-    RRRMC_RE_SLICE_SPARSE_F64 = 12  /* GraphEANormal / GraphRRGNormal (src/graphs/EA.jl:534-680, RRG.jl:503-617): (A, J) with rrrmc_set_graph_f64.
+    RRRMC_RE_SLICE_SPARSE_F64 = 12, /* GraphEANormal / GraphRRGNormal (src/graphs/EA.jl:534-680, RRG.jl:503-617): (A, J) with rrrmc_set_graph_f64.
                                        The slice graph has a K of its own, so these contexts are made by rrrmc_ctx_create_re_f64 / _le_f64 /
                                        _tle_f64; rrrmc_ctx_create_re / _le / _tle refuse the kind and name that creator */
+    RRRMC_RE_SLICE_MIXED = 13       /* GraphMixed: the g of the field wrappers made by rrrmc_ctx_create_mixed only.  rrrmc_ctx_create_af, _re, _le,
+                                       _tle and _quant_pattern refuse it, and so does a component list (a mix does not nest) */
 };
 
 /* Library ABI version (major*10000 + minor*100 + patch). */
@@ -583,6 +590,34 @@ RRRMC_API int32_t rrrmc_af_build(rrrmc_ctx *ctx, int32_t *build_out);
 /* The DeltaECacheCont after the last rrrMC call: dEs_out[R * N] = DeltaEs, v_out[R * N] the sampler's weights, z_out[R], trefresh_out[R]
  * (any may be NULL). */
 RRRMC_API int32_t rrrmc_af_cache(rrrmc_ctx *ctx, double *dEs_out, double *v_out, double *z_out, int64_t *trefresh_out);
+
+/* ---- GraphMixed (src/graphs/Mixed.jl; RRRMC_MODEL_MIXED, RRRMC_MODEL_MIXED_AF, RRRMC_MODEL_MIXED_ASF) ------
+ * rrrmc_ctx_create_mixed: R chains of GraphMixed(graphs...) on N spins, or of a field wrapper over it.  kinds[nkinds] lists the 2 .. 7
+ * components in order, each RRRMC_RE_SLICE_EMPTY, _SK, _SKN, _PERC_STEP, _PERC_LINEAR, _PERC_XENTR, _COMM_STEP, _COMM_RELU, _COMM_QU, _SAT
+ * or _SPARSE_F64.  wrap: 0 GraphMixed itself, 1 GraphAddFields(h, mixed), 2 GraphAddSubFields(h, mixed).  K is read for a _SPARSE_F64
+ * component (1 <= K <= 8), K2 for a committee machine.  A context holds one upload of each storage group -- {SK}, {SKN}, {PERC_STEP,
+ * PERC_LINEAR, PERC_XENTR}, {COMM_STEP, COMM_RELU, COMM_QU}, {SAT}, {SPARSE_F64} -- so a second component of one group is
+ * RRRMC_ERR_UNSUPPORTED (the message names the group); _EMPTY may repeat.  N <= 65535, and every component's own limits (perceptrons and
+ * committee machines N <= 32767 and their parities, whose message names the component).  Then each component's upload call, in any order
+ * (rrrmc_set_couplings_bits, _dense, rrrmc_set_patterns and rrrmc_set_loss_table, rrrmc_set_comm_patterns, rrrmc_set_clauses,
+ * rrrmc_set_graph_f64), and rrrmc_af_set_fields for wrap 1 or 2; a sampling or energy call before that answers RRRMC_ERR_STATE and names the
+ * missing call.  energy = the left-to-right Float64 sum of the components' energies, delta_energy the left-to-right sum of theirs
+ * (Mixed.jl:33-40): the order of the list is part of the model.  Results through the Float64 entry points (integers as exact doubles).
+ * Samplers: rrrmc_standard_mc_async on all three models; rrrmc_rrr_mc_async on wrap 1 and 2 (RRRMC_ERR_UNSUPPORTED on wrap 0, as on the
+ * other stand-alone dense graphs); bklMC / wtmMC / extremal_opt RRRMC_ERR_UNSUPPORTED.  rrrmc_set_resume, rrrmc_set_debug_checks, timing,
+ * rrrmc_energy_f64 / rrrmc_tracked_energy_f64, spins, snapshots and overlaps as for rrrmc_ctx_create_af; rrrmc_af_cache / rrrmc_af_build
+ * on wrap 1 and 2.  rrrmc_ctx_create_mixed_multi makes the same context over several devices (shards as rrrmc_ctx_create_multi's). */
+RRRMC_API int32_t rrrmc_ctx_create_mixed(rrrmc_ctx **out, const int32_t *kinds, int32_t nkinds, int32_t wrap, int64_t N, int64_t K, int64_t K2,
+                                         int64_t R, int32_t device, uint32_t replica0);
+RRRMC_API int32_t rrrmc_ctx_create_mixed_multi(rrrmc_ctx **out, const int32_t *kinds, int32_t nkinds, int32_t wrap, int64_t N, int64_t K, int64_t K2,
+                                               int64_t R, const int32_t *device_ids, int32_t ndev, uint32_t replica0);
+/* E_out[R * nkinds]: energy(graphs[c], C) of every component of the live configuration of every chain, recomputed from the configuration
+ * (read-only: a run the context continues is not disturbed).  Their left-to-right sum is energy(GraphMixed, C). */
+RRRMC_API int32_t rrrmc_mixed_energies(rrrmc_ctx *ctx, double *E_out);
+/* Which build the last rrrmc_standard_mc_async call on a mixed context ran (the first shard of a multi-device context): 0 none yet, 1 one
+ * thread per chain, 2 one wavefront per chain.  Up to 16384 chains run the wave build; RRRMC_MIXED_NO_WAVE=1 / RRRMC_MIXED_WAVE=1 force a
+ * build; the builds give the same bits. */
+RRRMC_API int32_t rrrmc_mixed_build(rrrmc_ctx *ctx, int32_t *build_out);
 
 /* rrrMC(X::DoubleGraph, beta, iters; step, staged_thr, staged_thr_fact) (src/RRRMC.jl:221-290) for all R replicas.
  *   fourK = round(2/beta * log(coth(beta * Gamma / M)), digits = 8)  (QT.jl:165) is computed by the caller.

@@ -314,6 +314,67 @@ function Ctx(X::RRRMC.RE.GraphRobustEnsemble{M,γ,β,G}, R::Integer; device = 0,
     return ctx
 end
 
+# ---- GraphMixed (src/graphs/Mixed.jl): two to seven graphs on one set of spins; the order of X.graphs is part of the model ------------------
+# standardMC on the mix itself (wrap 0), rrrMC and standardMC on GraphAddFields / GraphAddSubFields over it (wrap 1 / 2).  A component is
+# any graph the field wrappers take, GraphPercXEntr, a GraphRRGNormal / GraphEANormal (K <= 8), or a +-J GraphRRG / GraphEA with levels
+# (-1, 1), whose couplings go up as +-1.0; at most one component of each storage group (the library refuses a second one and names the
+# group).  (Checked statically only, as the rest of this file.)
+const MIXED, MIXED_AF, MIXED_ASF = 102, 103, 104       # rrrmc_ctx_create_mixed / rrrmc_ctx_create_mixed_multi with wrap 0, 1, 2
+const MixedGraph = RRRMC.Mixed.GraphMixed
+mixed_kind(g) = g isa XEntrGraph ? 11 : (g isa F64Graph || g isa PM1Graph) ? ENS_SPARSE_F64 : ens_kind(typeof(g), "GraphMixed")
+function mixed_upload!(ctx, X::MixedGraph)
+    for g in X.graphs          # every component's own upload call, in the order of the list (any order is accepted)
+        kind = mixed_kind(g)
+        if kind == 1
+            Jc = sk_bits(g.J)
+            GC.@preserve Jc check(ccall((:rrrmc_set_couplings_bits, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt64}), ctx.p, Jc), ctx.p)
+        elseif kind == 2
+            Jm = Matrix{Float64}(undef, X.N, X.N); for i = 1:X.N; Jm[:, i] = g.J[i]; end
+            GC.@preserve Jm check(ccall((:rrrmc_set_couplings_dense, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, Jm), ctx.p)
+        elseif kind == ENS_SPARSE_F64 && g isa PM1Graph
+            A = flatA(g); J = Float64.(collect(reinterpret(Int, g.J)))
+            GC.@preserve A J check(ccall((:rrrmc_set_graph_f64, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}), ctx.p, A, J), ctx.p)
+        elseif kind == ENS_SPARSE_F64
+            set_graph_f64!(ctx, g)
+        elseif kind >= 3
+            set_patterns!(ctx, g)
+        end
+    end
+    return ctx
+end
+function mixed_ctx(X::MixedGraph, wrap::Integer, R::Integer; device = 0, replica0 = 0, devices = nothing)
+    kinds = Int32[mixed_kind(g) for g in X.graphs]
+    K = 0; K2 = 0
+    for g in X.graphs
+        (g isa F64Graph || g isa PM1Graph) && (K = length(g.A[1]))
+        g isa CommGraph && (K2 = g.K2)
+    end
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    if devices === nothing
+        GC.@preserve kinds check(ccall((:rrrmc_ctx_create_mixed, LIB), Int32, (Ref{Ptr{Cvoid}}, Ptr{Int32}, Int32, Int32, Int64, Int64, Int64, Int64, Int32, UInt32),
+                                       ref, kinds, length(kinds), wrap, X.N, K, K2, R, device, replica0))
+    else
+        ids = Int32.(collect(devices))
+        GC.@preserve kinds ids check(ccall((:rrrmc_ctx_create_mixed_multi, LIB), Int32,
+                                           (Ref{Ptr{Cvoid}}, Ptr{Int32}, Int32, Int32, Int64, Int64, Int64, Int64, Ptr{Int32}, Int32, UInt32),
+                                           ref, kinds, length(kinds), wrap, X.N, K, K2, R, ids, length(ids), replica0))
+    end
+    return mixed_upload!(Ctx(ref[], R, X.N, true), X)
+end
+Ctx(X::MixedGraph, R::Integer; kw...) = mixed_ctx(X, 0, R; kw...)
+# energy(graphs[c], C) of every component for the live configurations: a length(X.graphs) x R matrix; column r = replica r
+function mixed_energies(ctx::Ctx, n::Integer)
+    E = Matrix{Float64}(undef, n, ctx.R)
+    check(ccall((:rrrmc_mixed_energies, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, E), ctx.p)
+    return E
+end
+# which kernel ran the last standardMC call on a mixed context: 0 none yet, 1 one thread per chain, 2 one wavefront per chain
+function mixed_build(ctx::Ctx)
+    b = Ref{Int32}(0)
+    check(ccall((:rrrmc_mixed_build, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), ctx.p, b), ctx.p)
+    return Int(b[])
+end
+
 # ---- GraphAddFields / GraphAddSubFields (src/graphs/AddFields.jl:58-123): external fields over one graph g ------------------------------
 # rrrMC(X::DoubleGraph) through the DynamicSampler of the inner GraphAF (one setindex! per move, whatever g is) and standardMC; bklMC /
 # wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED.  g is any graph the ensembles take as a slice; sparse graphs, GraphQuant and the
@@ -324,6 +385,12 @@ const AF_MODELS = (48, 49, 50, 51, 52, 53, 54, 0, 55, 56)          # RRRMC_MODEL
 function Ctx(X::AddFieldsGraph, R::Integer; device = 0, replica0 = 0, devices = nothing)
     sub = X isa RRRMC.AddFields.GraphAddSubFields
     g = X.X1
+    if g isa MixedGraph          # a wrapper over a GraphMixed: rrrmc_ctx_create_mixed with wrap 1 / 2, the components' uploads, then the fields
+        ctx = mixed_ctx(g, sub ? 2 : 1, R; device = device, replica0 = replica0, devices = devices)
+        h = Vector{Float64}(X.X0.fields)
+        GC.@preserve h check(ccall((:rrrmc_af_set_fields, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, h), ctx.p)
+        return ctx
+    end
     kind = g isa XEntrGraph ? 11 : ens_kind(typeof(g), sub ? "GraphAddSubFields" : "GraphAddFields")          # (no ensemble takes GraphPercXEntr)
     K2 = g isa CommGraph ? g.K2 : 0
     ref = Ref{Ptr{Cvoid}}(C_NULL)

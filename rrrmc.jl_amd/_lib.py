@@ -42,6 +42,7 @@ SYMBOLS = [
     "rrrmc_ctx_create_sat", "rrrmc_set_clauses", "rrrmc_sat_build", "rrrmc_sweep_build", "rrrmc_gen_ksat", "rrrmc_check_clauses",
     "rrrmc_ctx_create_tle", "rrrmc_tle_set_topology", "rrrmc_tle_check_topology", "rrrmc_tle_set_params", "rrrmc_tle_tables", "rrrmc_tle_cache", "rrrmc_tle_build",
     "rrrmc_ctx_create_af", "rrrmc_af_set_fields", "rrrmc_af_build", "rrrmc_af_cache",
+    "rrrmc_ctx_create_mixed", "rrrmc_ctx_create_mixed_multi", "rrrmc_mixed_energies", "rrrmc_mixed_build",
     "rrrmc_ctx_create_perc_xentr", "rrrmc_set_loss_table", "rrrmc_xentr_build", "rrrmc_perc_step_energy",
     "rrrmc_ctx_create_re_f64", "rrrmc_ctx_create_le_f64", "rrrmc_ctx_create_tle_f64", "rrrmc_gen_couplings_uniform",
 ]
@@ -310,6 +311,14 @@ def lib():
     L.rrrmc_af_build.argtypes = [vp, C.POINTER(C.c_int32)]
     L.rrrmc_af_cache.restype = C.c_int32
     L.rrrmc_af_cache.argtypes = [vp, vp, vp, vp, vp]
+    L.rrrmc_ctx_create_mixed.restype = C.c_int32
+    L.rrrmc_ctx_create_mixed.argtypes = [C.POINTER(vp), i32p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_uint32]
+    L.rrrmc_ctx_create_mixed_multi.restype = C.c_int32
+    L.rrrmc_ctx_create_mixed_multi.argtypes = [C.POINTER(vp), i32p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32p, C.c_int32, C.c_uint32]
+    L.rrrmc_mixed_energies.restype = C.c_int32
+    L.rrrmc_mixed_energies.argtypes = [vp, f64p]
+    L.rrrmc_mixed_build.restype = C.c_int32
+    L.rrrmc_mixed_build.argtypes = [vp, C.POINTER(C.c_int32)]
     L.rrrmc_ctx_create_perc_xentr.restype = C.c_int32
     L.rrrmc_ctx_create_perc_xentr.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int32, C.c_uint32]
     L.rrrmc_set_loss_table.restype = C.c_int32

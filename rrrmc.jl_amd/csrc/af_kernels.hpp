@@ -27,6 +27,7 @@
 
 #include "re_kernels.hpp"         // ReParams, re_view, re_residual / re_slice_update / re_slice_view / re_slice_energy, the slice kinds
 #include "sk_block_kernel.hpp"    // sk_readlane_f64
+#include "mixed_models.hpp"       // MixedList: g = GraphMixed (SLICE = RE_MIXED; the device functions are mixed_kernels.hpp's)
 
 namespace rrrmc {
 
@@ -41,6 +42,7 @@ struct AfParams {
     int32_t* status;                                        // [2]      chains that met "Unrecoverable loss of precision detected in the dynamic sampler", one of them
     int sub, levs, N2;
     int xe_hs_lds;                                          // GraphPercXEntr in the LDS build: the loss table is staged too (it fits)
+    MixedList mx;                                           // g = GraphMixed: the component list (n = 0 otherwise)
 };
 
 // bytes of LDS one chain takes in the LDS build, without g's per-chain state: tree and weights (16 N2), ΔEs, the spins
@@ -63,6 +65,9 @@ __device__ __forceinline__ double af_g_energy(const ReParams& P, long long n, do
 // The start of a reference call (src/RRRMC.jl:237-240): E = energy(X, C) and g's own cache; with `cache`, DeltaECacheCont(X0, C, β) — ΔEs,
 // the weights prior(β ΔE) and refresh! —, acc_rate = 0.5.  One workgroup per chain.
 constexpr int kAfInitThreads = 256;
+}  // namespace rrrmc
+#include "mixed_kernels.hpp"      // g = GraphMixed: the hooks of af_rrr_kernel<RE_MIXED, LDS> and the mix's own kernels (they take AfParams)
+namespace rrrmc {
 template <int SLICE>
 __global__ __launch_bounds__(kAfInitThreads) void af_init_kernel(AfParams A, int cache)
 {
@@ -179,6 +184,8 @@ __global__ __launch_bounds__(64) void af_rrr_kernel(AfParams A)
     RrrView v = re_view(P, sp, r);
     const auto g_pv = re_slice_view<SLICE>(P, r);                                  // PercView, CommView or SatTable
     auto pv = g_pv;
+    [[maybe_unused]] MixedViews mv{};                                              // g = GraphMixed: the components' state stays in global memory
+    if constexpr (SLICE == RE_MIXED) mv = mixed_views(P, A.mx, r);
     double* const g_slf = v.slf;
     [[maybe_unused]] unsigned char* const l_slice = af_lds + ((af_lds_bytes(N, N2, W) + 7) & ~(size_t)7);
     if constexpr (LDS && SLICE == RE_SKN) {
@@ -280,11 +287,16 @@ __global__ __launch_bounds__(64) void af_rrr_kernel(AfParams A)
     // the slice graph's update_cache!: the kinds whose update is written for one thread run it on lane 0
     auto g_update = [&](int move) {
         if constexpr (kWaveSlice<SLICE>) re_slice_update<SLICE, true>(v, pv, move, 0, move);
+        else if constexpr (SLICE == RE_MIXED) mixed_update_follow<true>(A.mx, v, move);          // (the pure components: g_update_pure)
         else if constexpr (SLICE == RE_SKN) {
             __syncthreads();
             if (lane == 0) skn_update(v, move);
             __syncthreads();
         }
+    };
+    // GraphMixed: the components that are pure functions of the configuration, once per accepted move
+    auto g_update_pure = [&]([[maybe_unused]] int move) {
+        if constexpr (SLICE == RE_MIXED) mixed_update_pure<true>(A.mx, v, mv, move);
     };
     auto flip = [&](int move) {
         __syncthreads();                                                           // (every lane has read the old bit)
@@ -305,7 +317,9 @@ __global__ __launch_bounds__(64) void af_rrr_kernel(AfParams A)
     };
     // delta_energy_residual at the current configuration (AddFields.jl:83, :119)
     auto residual = [&](int move) -> double {
-        const double dg = re_residual<SLICE, true>(v, pv, move, 0, move);
+        double dg;
+        if constexpr (SLICE == RE_MIXED) dg = mixed_residual<true>(A.mx, v, mv, move);
+        else dg = re_residual<SLICE, true>(v, pv, move, 0, move);
         return A.sub ? dg - af_delta0(A.h, move, sbit(sp, move)) : dg;
     };
 
@@ -329,6 +343,7 @@ __global__ __launch_bounds__(64) void af_rrr_kernel(AfParams A)
             if (accept_c(c, -beta * dE1, g)) {
                 flip(move);                                                        // spinflip!(X, C, move)
                 g_update(move);
+                g_update_pure(move);
                 __syncthreads();
                 if (lane == 0) dEs[move] = dEp;                                    // apply_staged!
                 setel(move, pp);
@@ -354,6 +369,7 @@ __global__ __launch_bounds__(64) void af_rrr_kernel(AfParams A)
                 if (accept_c(cc, -beta * dE1, g)) { E += dE0 + dE1; accepted += 1; acc = true; break; }
             }
             if constexpr (kWaveSlice<SLICE>) { if (acc) g_update(move); }
+            if (acc) g_update_pure(move);
         }
         acc_rate = acc_rate * (1 - P.lambda) + (acc ? 1.0 : 0.0) * P.lambda;       // RRRMC.jl:281
     }

@@ -3,8 +3,15 @@
 // uploads are the ensembles' (rrrmc_set_couplings_bits / _dense, rrrmc_set_patterns, rrrmc_set_comm_patterns, rrrmc_set_clauses) and the
 // frame of a sampler call is theirs (host_ens.hpp).  The model <-> (wrapper, kind of g) relation is the table of af_models.hpp.
 // Included by rrrmc_hip.hip inside its anonymous namespace, after host_ens.hpp; not a stand-alone translation unit.
-inline bool is_af(const rrrmc_ctx* ctx) { return af_family(ctx->model) != AF_NONE; }
-inline const char* af_graph_name(const rrrmc_ctx* ctx) { return af_family(ctx->model) == AF_ADDSUB ? "GraphAddSubFields" : "GraphAddFields"; }
+// (a mixed context, host_mixed.hpp, is one of the family: the stand-alone GraphMixed runs as a GraphAddSubFields whose fields are never read)
+inline bool is_af(const rrrmc_ctx* ctx) { return af_family(ctx->model) != AF_NONE || is_mixed(ctx); }
+inline const char* af_graph_name(const rrrmc_ctx* ctx)
+{
+    if (is_mixed(ctx)) return mixed_wrap(ctx->model) == 0 ? "GraphMixed" : mixed_wrap(ctx->model) == 2 ? "GraphAddSubFields over a GraphMixed" : "GraphAddFields over a GraphMixed";
+    return af_family(ctx->model) == AF_ADDSUB ? "GraphAddSubFields" : "GraphAddFields";
+}
+int32_t mixed_run_init(rrrmc_ctx* ctx, double beta, bool cache);          // host_mixed.hpp
+int32_t mixed_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact);
 // bklMC, wtmMC and extremal_opt on the family
 int32_t af_not_wired(rrrmc_ctx* ctx, const char* sampler)
 {
@@ -121,6 +128,7 @@ AfParams af_params(rrrmc_ctx* ctx, double beta)
 // energy(X, C), g's cache and, for rrrMC, a fresh DeltaECacheCont over X0: the start of a reference call (src/RRRMC.jl:237-240)
 int32_t af_run_init(rrrmc_ctx* ctx, double beta, bool cache)
 {
+    if (is_mixed(ctx)) return mixed_run_init(ctx, beta, cache);
     const AfParams A = af_params(ctx, beta);
     const dim3 grid((unsigned)ctx->R), blk(kAfInitThreads);
     if (!with_slice(AfSlices{}, af_slice(ctx->model), [&](auto s) { hipLaunchKernelGGL(af_init_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, A, cache ? 1 : 0); }))
@@ -156,6 +164,7 @@ af_kernel_fn af_rrr_fn(int slice, bool lds)
 int32_t af_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact)
 {
     if (!ctx->af_fields_set) return af_needs_fields(ctx);
+    if (is_mixed(ctx)) return mixed_mc_async(ctx, standard, beta, iters, step, staged_thr, staged_thr_fact);
     if (standard && std::isnan(beta)) return fail(ctx, RRRMC_ERR_INVALID_ARG, "beta is NaN");
     EnsCall C;
     int32_t rc = ens_call_begin(ctx, standard, beta, iters, step, staged_thr, staged_thr_fact, &C, false);

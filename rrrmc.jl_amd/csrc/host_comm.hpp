@@ -11,12 +11,12 @@ inline bool comm_slices(const rrrmc_ctx* ctx)          // an ensemble over commi
 inline bool comm_relu(const rrrmc_ctx* ctx)
 {
     return ctx->model == RRRMC_MODEL_COMM_RELU || model_slice(ctx->model) == RRRMC_RE_SLICE_COMM_RELU ||
-           (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_pat == RRRMC_RE_SLICE_COMM_RELU);
+           (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_pat == RRRMC_RE_SLICE_COMM_RELU) || mixed_has(ctx, RRRMC_RE_SLICE_COMM_RELU);
 }
 inline bool comm_qu(const rrrmc_ctx* ctx)
 {
     return ctx->model == RRRMC_MODEL_COMM_QU || model_slice(ctx->model) == RRRMC_RE_SLICE_COMM_QU ||
-           (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_pat == RRRMC_RE_SLICE_COMM_QU);
+           (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_pat == RRRMC_RE_SLICE_COMM_QU) || mixed_has(ctx, RRRMC_RE_SLICE_COMM_QU);
 }
 // GraphCommReLU and GraphCommQu: K1, K2 even, labelled patterns
 inline bool comm_labelled(const rrrmc_ctx* ctx) { return comm_relu(ctx) || comm_qu(ctx); }
@@ -62,7 +62,7 @@ int32_t comm_set_patterns(rrrmc_ctx* ctx, int64_t K2, const uint64_t* xi, const 
     if (relu && !y) return fail(ctx, RRRMC_ERR_INVALID_ARG, "a %s needs the labels y", qu ? "GraphCommQu" : "GraphCommReLU");
     if (!relu && y) return fail(ctx, RRRMC_ERR_INVALID_ARG, "a GraphCommStep has no labels: y must be NULL");
     if (K2 < 1 || N % K2 != 0) return fail(ctx, RRRMC_ERR_INVALID_ARG, "N = %lld is not a multiple of K2 = %lld", (long long)N, (long long)K2);
-    if ((is_comm(ctx) || ctx->model == RRRMC_MODEL_QUANT_RRG || af_family(ctx->model) != AF_NONE) && K2 != ctx->cm_K2)
+    if ((is_comm(ctx) || ctx->model == RRRMC_MODEL_QUANT_RRG || af_family(ctx->model) != AF_NONE || is_mixed(ctx)) && K2 != ctx->cm_K2)
         return fail(ctx, RRRMC_ERR_INVALID_ARG, "K2 = %lld, but the context was made with K2 = %lld", (long long)K2, (long long)ctx->cm_K2);
     { const int32_t rck = comm_check_k(ctx, N / K2, K2, relu); if (rck) return rck; }
     if (P < 1) return fail(ctx, RRRMC_ERR_INVALID_ARG, "P must be >= 1, given: %lld", (long long)P);

@@ -29,7 +29,8 @@ enum ReSlice { RE_EMPTY = 0, RE_SK = 1, RE_SKN = 2,          // GraphEmpty (Grap
                RE_SAT = 8,                                   // GraphSAT (GraphSATRE); 7 is unassigned, as in the ABI
                RE_CQU = 9,                                   // GraphCommQu (GraphCommQuRE)
                RE_PXE = 11,                                  // GraphPercXEntr: the g of GraphAddFields / GraphAddSubFields only (af_kernels.hpp); 10 is unassigned
-               RE_SPF = 12 };                                // GraphEANormal / GraphRRGNormal: sparse Float64 couplings (GraphEARE, GraphEALE, GraphEATLE)
+               RE_SPF = 12,                                  // GraphEANormal / GraphRRGNormal: sparse Float64 couplings (GraphEARE, GraphEALE, GraphEATLE)
+               RE_MIXED = 13 };                              // GraphMixed: the g of the field wrappers over a mix only (mixed_kernels.hpp)
 template <int SLICE> constexpr bool kPercSlice = SLICE == RE_PSTEP || SLICE == RE_PLIN;
 template <int SLICE> constexpr bool kCommSlice = SLICE == RE_CSTEP || SLICE == RE_CRELU || SLICE == RE_CQU;
 // slices whose state is a pure function of the configuration, updated once per accepted move by the whole wavefront in the LDS builds

@@ -23,6 +23,7 @@ typedef hipError_t dev_err_t;
 #include "dev_mem.hpp"
 #include "ens_models.hpp"
 #include "af_models.hpp"
+#include "mixed_models.hpp"
 #include "sk_kernels.hpp"
 #include "sk_block_kernel.hpp"
 #include "sk_hblock_kernel.hpp"
@@ -318,6 +319,11 @@ struct rrrmc_ctx {
     int64_t af_N2 = 0;
     bool af_fields_set = false;
     int af_build = 0;              // the build of the last rrrMC call: 1 LDS, 2 global memory; 0 none yet
+    // ---- GraphMixed and the field wrappers over it (mixed_models.hpp; host_mixed.hpp): the wrappers' buffers above, and every component in
+    //      the buffers its kind has (q_Jb; sk_J / q_slf / q_smv / q_scur; pc_* / xe_*; cm_*; sat_*; d_A / q_Jf / q_flf / q_fundo / q_fml) ----
+    MixedList mx{};                // the component list (n = 0: no mixed context)
+    uint32_t mx_need = 0, mx_have = 0;   // the uploads the list waits for and those made: one bit per storage group, kMixedTableBit for the loss table
+    int mx_build = 0;              // the build of the last standardMC call: 1 thread per chain, 2 wavefront per chain; 0 none yet
     // ---- the binary perceptron (RRRMC_MODEL_PERC_*, and the perceptron slices of the ensembles; host_perc.hpp): spins in q_spins,
     //      E in sk_E, counts in q_stats ----
     uint64_t* pc_col = nullptr;    // [Nk][PW] patterns, one column per synapse
@@ -571,7 +577,18 @@ hipError_t raise_lds_attr(const void* fn, size_t bytes)
     return e;
 }
 
-inline bool chunk_layout(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_QUANT_RRG || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_SPARSE_LEVELS ||
+inline bool is_mixed(const rrrmc_ctx* ctx) { return mixed_wrap(ctx->model) >= 0; }
+inline bool mixed_has(const rrrmc_ctx* ctx, int32_t kind) { return is_mixed(ctx) && mixed_list_has(ctx->mx, kind); }
+inline bool mixed_has_group(const rrrmc_ctx* ctx, int group) { return is_mixed(ctx) && mixed_list_has_group(ctx->mx, group); }
+// behind an upload call on a mixed context (rc = what the call answered): the context is ready once every group of its list is filled
+inline int32_t mixed_uploaded(rrrmc_ctx* ctx, int32_t rc, int bit)
+{
+    if (!ctx || !is_mixed(ctx) || !ctx->kids.empty()) return rc;
+    if (rc) ctx->mx_have &= ~(1u << bit); else ctx->mx_have |= 1u << bit;
+    ctx->graph_set = (ctx->mx_have & ctx->mx_need) == ctx->mx_need;
+    return rc;
+}
+inline bool chunk_layout(const rrrmc_ctx* ctx) { return is_mixed(ctx) || ctx->model == RRRMC_MODEL_QUANT_RRG || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_SPARSE_LEVELS ||
                                                        ctx->model == RRRMC_MODEL_PERC_STEP || ctx->model == RRRMC_MODEL_PERC_LINEAR || ctx->model == RRRMC_MODEL_PERC_XENTR ||
                                                        ctx->model == RRRMC_MODEL_COMM_STEP || ctx->model == RRRMC_MODEL_COMM_RELU || ctx->model == RRRMC_MODEL_COMM_QU ||
                                                        ctx->model == RRRMC_MODEL_SAT || ens_family(ctx->model) != ENS_NONE || af_family(ctx->model) != AF_NONE; }
@@ -583,6 +600,11 @@ int32_t ensure_state(rrrmc_ctx* ctx, bool need_spins)
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
     if (!ctx->graph_set && ctx->pc_P > 0 && (ctx->model == RRRMC_MODEL_PERC_XENTR || model_slice(ctx->model) == RRRMC_RE_SLICE_PERC_XENTR))
         return fail(ctx, RRRMC_ERR_STATE, "a GraphPercXEntr needs its loss table: call rrrmc_set_loss_table first");
+    if (!ctx->graph_set && is_mixed(ctx)) {
+        int bit = 0;
+        while (bit < kMixedTableBit && !((ctx->mx_need & ~ctx->mx_have) & (1u << bit))) ++bit;
+        return fail(ctx, RRRMC_ERR_STATE, "a GraphMixed needs every component's upload: %s has not been called", mixed_upload_name(bit));
+    }
     if (!ctx->graph_set) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph has not been called");
     if (need_spins && !ctx->spins_set)
         return fail(ctx, RRRMC_ERR_STATE, "no configuration: call rrrmc_init_spins_random or rrrmc_set_spins first");
@@ -729,6 +751,7 @@ inline void smp_commit(rrrmc_ctx* ctx, int kind, int64_t n) { ctx->smp_kind = ki
 #include "host_le.hpp"
 #include "host_tle.hpp"
 #include "host_af.hpp"
+#include "host_mixed.hpp"
 int32_t quant_mc_async(rrrmc_ctx* ctx, bool standard, double beta, double fourK, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact);
 
 }  // namespace
@@ -1795,6 +1818,7 @@ int32_t rrrmc_set_patterns(rrrmc_ctx* ctx, const uint64_t* xi, int64_t P)
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
     if (is_xentr(ctx)) return xentr_set_patterns(ctx, xi, P);
     if (xentr_slices(ctx)) { const int32_t rc = perc_set_patterns(ctx, xi, P, 1); if (!rc) ctx->graph_set = ctx->xe_table_set; return rc; }
+    if (mixed_has_group(ctx, MG_PERC)) return mixed_uploaded(ctx, perc_set_patterns(ctx, xi, P, 1), MG_PERC);
     if (!is_perc(ctx) && !perc_slices(ctx) && !quant_pat_perc(ctx))
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_patterns is for contexts made by rrrmc_ctx_create_perc, or by rrrmc_ctx_create_re / _le / _quant_pattern with a perceptron slice kind");
     return perc_set_patterns(ctx, xi, P, is_perc(ctx) ? 1 : is_le(ctx) ? ctx->qM + 1 : ctx->qM);
@@ -1811,6 +1835,7 @@ int32_t rrrmc_set_loss_table(rrrmc_ctx* ctx, const double* Hs, int64_t n)
     RRRMC_MULTI(ctx, false, rrrmc_set_loss_table(c, Hs, n));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (mixed_has(ctx, RRRMC_RE_SLICE_PERC_XENTR)) return mixed_uploaded(ctx, xentr_set_table(ctx, Hs, n), kMixedTableBit);
     if (!is_xentr(ctx) && !xentr_slices(ctx))
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_loss_table is for contexts made by rrrmc_ctx_create_perc_xentr, or by rrrmc_ctx_create_af with RRRMC_RE_SLICE_PERC_XENTR");
     return xentr_set_table(ctx, Hs, n);
@@ -1831,7 +1856,7 @@ int32_t rrrmc_perc_step_energy(rrrmc_ctx* ctx, int64_t* out)
     RRRMC_MULTI(ctx, true, rrrmc_perc_step_energy(c, at_row(out, r0)));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
     const int32_t ms = model_slice(ctx->model);
-    const bool wrapped = is_af(ctx) && (ms == RRRMC_RE_SLICE_PERC_STEP || ms == RRRMC_RE_SLICE_PERC_LINEAR || ms == RRRMC_RE_SLICE_PERC_XENTR);
+    const bool wrapped = (is_af(ctx) && (ms == RRRMC_RE_SLICE_PERC_STEP || ms == RRRMC_RE_SLICE_PERC_LINEAR || ms == RRRMC_RE_SLICE_PERC_XENTR)) || mixed_has_group(ctx, MG_PERC);
     if (!is_perc(ctx) && !is_xentr(ctx) && !wrapped)
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_perc_step_energy is for contexts made by rrrmc_ctx_create_perc / _perc_xentr, or by rrrmc_ctx_create_af over a perceptron");
     if (!out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "out is NULL");
@@ -1855,6 +1880,7 @@ int32_t rrrmc_set_comm_patterns(rrrmc_ctx* ctx, int64_t K2, const uint64_t* xi, 
     RRRMC_MULTI(ctx, false, rrrmc_set_comm_patterns(c, K2, xi, y, P));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (mixed_has_group(ctx, MG_COMM)) return mixed_uploaded(ctx, comm_set_patterns(ctx, K2, xi, y, P, 1), MG_COMM);
     if (!is_comm(ctx) && !comm_slices(ctx) && !quant_pat_comm(ctx))
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_comm_patterns is for contexts made by rrrmc_ctx_create_comm / _comm_qu, or by rrrmc_ctx_create_re / _le / _quant_pattern with a committee machine slice kind");
     return comm_set_patterns(ctx, K2, xi, y, P, is_comm(ctx) ? 1 : is_le(ctx) ? ctx->qM + 1 : ctx->qM);
@@ -1871,6 +1897,7 @@ int32_t rrrmc_set_clauses(rrrmc_ctx* ctx, int64_t Mc, int64_t Kmax, const int32_
     RRRMC_MULTI(ctx, false, rrrmc_set_clauses(c, Mc, Kmax, vars, lits));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (mixed_has(ctx, RRRMC_RE_SLICE_SAT)) return mixed_uploaded(ctx, sat_set_clauses(ctx, Mc, Kmax, vars, lits), MG_SAT);
     if (!is_sat(ctx) && !sat_slices(ctx))
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_clauses is for contexts made by rrrmc_ctx_create_sat, or by rrrmc_ctx_create_re / _le with RRRMC_RE_SLICE_SAT");
     return sat_set_clauses(ctx, Mc, Kmax, vars, lits);
@@ -2119,7 +2146,7 @@ int32_t rrrmc_af_set_fields(rrrmc_ctx* ctx, const double* h)
     RRRMC_MULTI(ctx, false, rrrmc_af_set_fields(c, h));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (!is_af(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_af_set_fields is for contexts made by rrrmc_ctx_create_af (GraphAddFields, GraphAddSubFields)");
+    if (!is_af(ctx) || mixed_wrap(ctx->model) == 0) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_af_set_fields is for contexts made by rrrmc_ctx_create_af (GraphAddFields, GraphAddSubFields), or by rrrmc_ctx_create_mixed with wrap 1 or 2");
     return af_set_fields(ctx, h);
 }
 
@@ -2127,7 +2154,7 @@ int32_t rrrmc_af_build(rrrmc_ctx* ctx, int32_t* build_out)
 {
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
     if (is_multi(ctx)) return rrrmc_af_build(ctx->kids[0], build_out);
-    if (!is_af(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_af_build is for contexts made by rrrmc_ctx_create_af (GraphAddFields, GraphAddSubFields)");
+    if (!is_af(ctx) || mixed_wrap(ctx->model) == 0) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_af_build is for contexts made by rrrmc_ctx_create_af (GraphAddFields, GraphAddSubFields), or by rrrmc_ctx_create_mixed with wrap 1 or 2");
     if (!build_out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "build_out is NULL");
     *build_out = ctx->af_build;
     return RRRMC_OK;
@@ -2137,7 +2164,7 @@ int32_t rrrmc_af_cache(rrrmc_ctx* ctx, double* dEs_out, double* v_out, double* z
 {
     RRRMC_MULTI(ctx, true, rrrmc_af_cache(c, at_row(dEs_out, r0 * ctx->N), at_row(v_out, r0 * ctx->N), at_row(z_out, r0), at_row(trefresh_out, r0)));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (!is_af(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_af_cache is for contexts made by rrrmc_ctx_create_af (GraphAddFields, GraphAddSubFields)");
+    if (!is_af(ctx) || mixed_wrap(ctx->model) == 0) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_af_cache is for contexts made by rrrmc_ctx_create_af (GraphAddFields, GraphAddSubFields), or by rrrmc_ctx_create_mixed with wrap 1 or 2");
     if (!ctx->results_valid || !ctx->last_call_rrr || !ctx->q_cache_valid) return fail(ctx, RRRMC_ERR_STATE, "no rrrMC call has been made");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2150,6 +2177,38 @@ int32_t rrrmc_af_cache(rrrmc_ctx* ctx, double* dEs_out, double* v_out, double* z
         HIP_TRY(ctx, hipMemcpy(t.data(), ctx->af_tref, sizeof(long long) * R, hipMemcpyDeviceToHost));
         for (size_t r = 0; r < R; ++r) trefresh_out[r] = (int64_t)t[r];
     }
+    return RRRMC_OK;
+}
+
+// ---- GraphMixed and the field wrappers over it: exported entry points (host_mixed.hpp) ----
+int32_t rrrmc_ctx_create_mixed(rrrmc_ctx** out, const int32_t* kinds, int32_t nkinds, int32_t wrap, int64_t N, int64_t K, int64_t K2, int64_t R, int32_t device, uint32_t replica0)
+{
+    return mixed_ctx_create(out, kinds, nkinds, wrap, N, K, K2, R, device, replica0);
+}
+int32_t rrrmc_ctx_create_mixed_multi(rrrmc_ctx** out, const int32_t* kinds, int32_t nkinds, int32_t wrap, int64_t N, int64_t K, int64_t K2, int64_t R,
+                                     const int32_t* device_ids, int32_t ndev, uint32_t replica0)
+{
+    return mixed_ctx_create_multi(out, kinds, nkinds, wrap, N, K, K2, R, device_ids, ndev, replica0);
+}
+
+int32_t rrrmc_mixed_energies(rrrmc_ctx* ctx, double* E_out)
+{
+    RRRMC_MULTI(ctx, true, rrrmc_mixed_energies(c, at_row(E_out, r0 * ctx->mx.n)));
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (!is_mixed(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_mixed_energies is for contexts made by rrrmc_ctx_create_mixed");
+    const int32_t rc = ensure_state(ctx, true);
+    if (rc) return rc;
+    if (!E_out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "E_out is NULL");
+    return mixed_energies(ctx, E_out);
+}
+
+int32_t rrrmc_mixed_build(rrrmc_ctx* ctx, int32_t* build_out)
+{
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (is_multi(ctx)) return rrrmc_mixed_build(ctx->kids[0], build_out);
+    if (!is_mixed(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_mixed_build is for contexts made by rrrmc_ctx_create_mixed");
+    if (!build_out) return fail(ctx, RRRMC_ERR_INVALID_ARG, "build_out is NULL");
+    *build_out = ctx->mx_build;
     return RRRMC_OK;
 }
 
@@ -2167,6 +2226,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     if (ndev > 64) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "ndev = %d: at most 64 devices", ndev);
     if (R < 1) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "R must be >= 1 (given %lld)", (long long)R);
     if (replica0 % 32) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "replica0 must be a multiple of 32 (given %u)", replica0);
+    if (mixed_wrap(model) >= 0) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "a GraphMixed needs its component list: use rrrmc_ctx_create_mixed_multi");
     rrrmc_ctx* ctx = new (std::nothrow) rrrmc_ctx();
     if (!ctx) return fail(nullptr, RRRMC_ERR_NOMEM, "out of host memory");
     const int32_t qpat = model == RRRMC_MODEL_QUANT_PERC_STEP ? RRRMC_RE_SLICE_PERC_STEP : model == RRRMC_MODEL_QUANT_PERC_LINEAR ? RRRMC_RE_SLICE_PERC_LINEAR
@@ -2627,7 +2687,7 @@ int32_t rrrmc_set_couplings_dense(rrrmc_ctx* ctx, const double* J)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_dense(c, J));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qskn = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn) || model_slice(ctx->model) == RRRMC_RE_SLICE_SKN;   // slice graphs: J is Nk x Nk
+    const bool qskn = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_skn) || model_slice(ctx->model) == RRRMC_RE_SLICE_SKN || mixed_has(ctx, RRRMC_RE_SLICE_SKN);   // slice graphs: J is Nk x Nk
     if (ctx->model != RRRMC_MODEL_SK_NORMAL && !qskn) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_dense is for RRRMC_MODEL_SK_NORMAL (or a GraphQuant over GraphSKNormal slices)");
     if (!J) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J is NULL");
     const int64_t N = qskn ? ctx->qNk : ctx->N;
@@ -2648,7 +2708,8 @@ int32_t rrrmc_set_couplings_dense(rrrmc_ctx* ctx, const double* J)
         HIP_TRY(ctx, hipMemcpy(ctx->sk_J4, J4.data(), sizeof(double) * N * ld, hipMemcpyHostToDevice));
     }
     ctx->graph_set = true;
-    return RRRMC_OK;
+    if (is_mixed(ctx)) { ctx->std_cache_live = false; ctx->q_cache_valid = false; }
+    return mixed_uploaded(ctx, RRRMC_OK, MG_SKN);
 }
 
 int32_t rrrmc_energy_f64(rrrmc_ctx* ctx, double* E_out)
@@ -2775,7 +2836,7 @@ int32_t rrrmc_set_couplings_bits(rrrmc_ctx* ctx, const uint64_t* Jc)
     RRRMC_MULTI(ctx, false, rrrmc_set_couplings_bits(c, Jc));
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    const bool qsk = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk) || model_slice(ctx->model) == RRRMC_RE_SLICE_SK;     // the slice graph of a GraphQSKT / GraphSKRE / GraphSKLE
+    const bool qsk = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_sk) || model_slice(ctx->model) == RRRMC_RE_SLICE_SK || mixed_has(ctx, RRRMC_RE_SLICE_SK);     // the slice graph of a GraphQSKT / GraphSKRE / GraphSKLE
     if (ctx->model != RRRMC_MODEL_SK_BINARY && !qsk)
         return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_couplings_bits is for RRRMC_MODEL_SK_BINARY and for contexts made by rrrmc_ctx_create_quant_sk");
     if (!Jc) return fail(ctx, RRRMC_ERR_INVALID_ARG, "J_chunks is NULL");
@@ -2793,7 +2854,8 @@ int32_t rrrmc_set_couplings_bits(rrrmc_ctx* ctx, const uint64_t* Jc)
     if (qsk) ctx->q_cache_valid = false;
     ctx->skb_J4_valid = false;
     ctx->graph_set = true;
-    return RRRMC_OK;
+    if (is_mixed(ctx)) ctx->std_cache_live = false;
+    return mixed_uploaded(ctx, RRRMC_OK, MG_SK);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -3159,7 +3221,7 @@ int32_t rrrmc_set_graph_f64(rrrmc_ctx* ctx, const int32_t* A, const double* J)
     smp_drop(ctx);
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
     // the slice graph of a GraphQEAT, or of an ensemble over sparse Float64 slices (GraphEARE, GraphEALE, GraphEATLE): (A, J) is Nk x K
-    const bool espf = ens_slice(ctx->model) == RRRMC_RE_SLICE_SPARSE_F64;
+    const bool espf = ens_slice(ctx->model) == RRRMC_RE_SLICE_SPARSE_F64 || mixed_has(ctx, RRRMC_RE_SLICE_SPARSE_F64);
     const bool qspf = (ctx->model == RRRMC_MODEL_QUANT_RRG && ctx->q_spf) || espf;
     if (ctx->model != RRRMC_MODEL_SPARSE_F64 && !qspf) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_graph_f64 is for RRRMC_MODEL_SPARSE_F64 (or a context made by rrrmc_ctx_create_quant_f64 / _re_f64 / _le_f64 / _tle_f64)");
     if (!A || !J) return fail(ctx, RRRMC_ERR_INVALID_ARG, "A and J must not be NULL");
@@ -3188,7 +3250,7 @@ int32_t rrrmc_set_graph_f64(rrrmc_ctx* ctx, const int32_t* A, const double* J)
         ctx->q_cache_valid = false;
         if (espf) ctx->std_cache_live = false;
         ctx->graph_set = true;
-        return RRRMC_OK;
+        return mixed_uploaded(ctx, RRRMC_OK, MG_SPF);
     }
     HIP_TRY(ctx, hipMemcpy(ctx->pf_J, J, sizeof(double) * N * K, hipMemcpyHostToDevice));
     ctx->h_A.assign(A, A + N * K);

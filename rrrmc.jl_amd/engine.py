@@ -20,8 +20,7 @@ class Engine:
         self._units = X._units          # device energies are int64 level units: X.energy_value converts
         if devices is not None:
             ids = np.asarray(list(devices), np.int32)
-            kind, N, K, M = X._multi_args()
-            check(lib().rrrmc_ctx_create_multi(C.byref(self._ctx), kind, N, K, M, self.R, ids, len(ids), replica0))
+            X._create_multi(C.byref(self._ctx), self.R, ids, replica0)
         else:
             X._create(C.byref(self._ctx), self.R, device, replica0)
         try:
@@ -259,6 +258,21 @@ class Engine:
         b = C.c_int32(0)
         check(lib().rrrmc_af_build(self._ctx, C.byref(b)), self._ctx)
         return int(b.value)
+
+    def mixed_build(self):
+        """the kernel build of the last standardMC call on a GraphMixed (or a field wrapper over one): 1 one thread per chain, 2 one wavefront
+        per chain, 0 none yet"""
+        b = C.c_int32(0)
+        check(lib().rrrmc_mixed_build(self._ctx, C.byref(b)), self._ctx)
+        return int(b.value)
+
+    def mixed_energies(self):
+        """energy(graphs[c], C) of every component of a GraphMixed for the live configuration: (n,) for one replica, (R, n) otherwise.
+        Read-only: a run the engine continues is not disturbed."""
+        n = len((self.X if hasattr(self.X, "graphs") else self.X.X1).graphs)
+        out = np.zeros((self.R, n), np.float64)
+        check(lib().rrrmc_mixed_energies(self._ctx, out.reshape(-1)), self._ctx)
+        return out[0] if self.R == 1 else out
 
     def xentr_build(self):
         """the kernel build of the last standardMC call on a stand-alone GraphPercXEntr: 1 one thread per chain, 2 one wavefront per chain,

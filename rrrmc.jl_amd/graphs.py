@@ -98,6 +98,11 @@ class _DeviceGraph:
         """(kind, N, K, M) of rrrmc_ctx_create_multi"""
         return self.model_kind, self.N, self.K, 0
 
+    def _create_multi(self, ctx, R, ids, replica0):
+        """the same context over the devices ``ids``"""
+        kind, N, K, M = self._multi_args()
+        check(lib().rrrmc_ctx_create_multi(ctx, kind, N, K, M, R, ids, len(ids), replica0))
+
     def _upload(self, ctx):
         self._upload_couplings(ctx)
 
@@ -1112,6 +1117,97 @@ def GraphPercLinearLE(*args, seed=DEFAULT_SEED):
     return _pattern_ensemble(GraphLocalEntropy, GraphPercLinear, "N, P", args, seed=seed)
 
 
+# storage group of every component kind of a GraphMixed (mixed_models.hpp): a context holds one upload of each group
+_MIXED_GROUPS = {1: "{SK}", 2: "{SKN}", 3: "{PERC_STEP, PERC_LINEAR, PERC_XENTR}", 4: "{PERC_STEP, PERC_LINEAR, PERC_XENTR}",
+                 11: "{PERC_STEP, PERC_LINEAR, PERC_XENTR}", 5: "{COMM_STEP, COMM_RELU, COMM_QU}", 6: "{COMM_STEP, COMM_RELU, COMM_QU}",
+                 9: "{COMM_STEP, COMM_RELU, COMM_QU}", 8: "{SAT}", 12: "{SPARSE_F64}"}
+
+
+class _PM1AsF64:
+    """A ±J ``GraphRRG`` / ``GraphEA`` (levels (-1, 1)) as a sparse Float64 component of a ``GraphMixed``: the couplings go up as ±1.0.  Every
+    term of its energy and ΔE is a small integer, so the Float64 sums are the reference's integers whatever the order of additions."""
+
+    def __init__(self, g):
+        self.g, self.N, self.K = g, g.N, g.K
+        self.A, self.J = g.A, np.ascontiguousarray(g.J, np.float64)
+        self.energy_dtype = np.int64
+
+    def _upload_couplings(self, ctx):
+        check(lib().rrrmc_set_graph_f64(ctx, self.A, self.J.reshape(-1)), ctx)
+
+
+class GraphMixed(_DeviceGraph):
+    """``GraphMixed(graphs...)`` — two or more graphs on one set of spins (src/graphs/Mixed.jl:15-61): energy and delta_energy are the sums
+    of the components', folded from the left in the order given (the order is part of the model: Float64 sums), ``update_cache!`` goes to
+    every component.  A component is ``None`` (GraphEmpty), a ``GraphSK``, ``GraphSKNormal``, ``GraphPercStep``, ``GraphPercLinear``,
+    ``GraphPercXEntr``, ``GraphCommStep``, ``GraphCommReLU``, ``GraphCommQu``, ``GraphSAT``, ``GraphRRGNormal`` / ``GraphEANormal`` (K <= 8),
+    or a ±J ``GraphRRG`` / ``GraphEA`` with levels (-1, 1) and K <= 8, whose couplings are uploaded as ±1.0.  At most one component of each
+    storage group ({SK}, {SKN}, the three perceptrons, the three committee machines, {SAT}, the sparse graphs): a context holds one upload
+    of each.  ``standardMC`` runs on the mix, ``rrrMC`` on ``GraphAddFields`` / ``GraphAddSubFields`` over it.  ``ET`` is Int when every
+    component's is, else Float64."""
+    model_kind = 102        # RRRMC_MODEL_MIXED
+    K = 0
+    _wrap = 0
+    _engine = None          # mixed_energies / step_energy read the live engine
+
+    def __init__(self, *graphs):
+        if len(graphs) < 2:
+            raise ValueError("at least 2 base graphs needed")                                   # Mixed.jl:22
+        if len(graphs) > 7:
+            raise NotImplementedError("GraphMixed: %d components: the mixed kernels cover <= 7" % len(graphs))
+        comps = []
+        for g in graphs:
+            if isinstance(g, GraphMixed):
+                raise TypeError("GraphMixed: a component is a GraphMixed: a mix does not nest (list its components instead)")
+            if isinstance(g, _SparseLevelsGraph):
+                raise TypeError("GraphMixed: a %s with levels %r is not wired as a component (general-level graphs are not; levels (-1, 1) are)" % (type(g).__name__, g.levels))
+            if isinstance(g, _DiscretizedGraph):
+                raise TypeError("GraphMixed: a %s is not wired as a component (discretised graphs are not)" % type(g).__name__)
+            if isinstance(g, GraphQuant):
+                raise TypeError("GraphMixed: GraphQuant is not wired as a component")
+            if isinstance(g, (GraphRobustEnsemble, GraphLocalEntropy, GraphTopologicalLocalEntropy)):
+                raise TypeError("GraphMixed: a %s is not wired as a component (the ensembles are not)" % type(g).__name__)
+            if isinstance(g, _SparsePM1Graph):
+                g = _PM1AsF64(g)
+            elif g is not None and not isinstance(g, (GraphSK, GraphSKNormal, _GraphPerc, GraphPercXEntr, _GraphComm, GraphSAT, _SparseF64Graph)):
+                raise TypeError("GraphMixed: a %s is not wired as a component" % type(g).__name__)
+            comps.append(g)
+        Ns = {int(g.N) for g in comps if g is not None}
+        if not Ns:
+            raise ValueError("GraphMixed: at least one component must not be None (GraphEmpty), which carries no N here")
+        if len(Ns) != 1:
+            raise ValueError("same N for all graphs required")                                  # Mixed.jl:24
+        self.N = Ns.pop()
+        self.graphs = tuple(graphs)
+        self._comps = tuple(comps)
+        self.kinds = np.asarray([12 if isinstance(g, (_PM1AsF64, _SparseF64Graph)) else _ensemble_slice_kind(g) for g in comps], np.int32)
+        seen = {}
+        for c, k in enumerate(self.kinds):
+            grp = _MIXED_GROUPS.get(int(k))
+            if grp is None:
+                continue
+            if grp in seen:
+                raise NotImplementedError("GraphMixed: component %d is a second graph of the storage group %s (component %d is the first): "
+                                          "a context holds one upload of each group" % (c, grp, seen[grp]))
+            seen[grp] = c
+        self.Ksp = next((int(g.K) for g in comps if isinstance(g, (_PM1AsF64, _SparseF64Graph))), 0)
+        if self.Ksp > 8:
+            raise NotImplementedError("GraphMixed: K = %d: a sparse component takes 1 <= K <= 8" % self.Ksp)
+        self.K2 = next((int(g.K2) for g in comps if isinstance(g, _GraphComm)), 0)
+        self.energy_dtype = np.int64 if all(g is None or np.dtype(g.energy_dtype) == np.int64 for g in comps) else np.float64
+
+    def _create(self, ctx, R, device, replica0, wrap=0):
+        check(lib().rrrmc_ctx_create_mixed(ctx, self.kinds, len(self.kinds), wrap, self.N, self.Ksp, self.K2, R, device, replica0))
+
+    def _create_multi(self, ctx, R, ids, replica0, wrap=0):
+        check(lib().rrrmc_ctx_create_mixed_multi(ctx, self.kinds, len(self.kinds), wrap, self.N, self.Ksp, self.K2, R, ids, len(ids), replica0))
+
+    def _upload_couplings(self, ctx):
+        for g in self._comps:
+            if g is not None:
+                g._upload_couplings(ctx)
+
+
 class GraphAddFields(_DeviceGraph):
     """``GraphAddFields(fields, g)`` — external fields added to a graph ``g`` (src/graphs/AddFields.jl:58-90): a DoubleGraph whose inner
     graph ``GraphAF(fields)`` has energy Σ_i h_i σ_i, delta_energy −2 σ_i h_i and no neighbours, and whose residual is ``g``'s own
@@ -1125,10 +1221,17 @@ class GraphAddFields(_DeviceGraph):
     _engine = None          # step_energy over a perceptron reads the live engine
 
     def _create(self, ctx, R, device, replica0):
+        if isinstance(self.X1, GraphMixed):
+            return self.X1._create(ctx, R, device, replica0, wrap=1 + self._sub)
         check(lib().rrrmc_ctx_create_af(ctx, self.slice_kind, self._sub, self.N, self.K2, R, device, replica0))
 
     def _multi_args(self):
         return self.model_kind, self.N, self.K2, 0
+
+    def _create_multi(self, ctx, R, ids, replica0):
+        if isinstance(self.X1, GraphMixed):
+            return self.X1._create_multi(ctx, R, ids, replica0, wrap=1 + self._sub)
+        _DeviceGraph._create_multi(self, ctx, R, ids, replica0)
 
     def _upload(self, ctx):
         if self.X1 is not None:
@@ -1139,15 +1242,19 @@ class GraphAddFields(_DeviceGraph):
         fields = np.ascontiguousarray(fields, np.float64)
         if fields.ndim != 1 or len(fields) < 1:
             raise ValueError("fields must be a non-empty vector")
-        if g is not None and not isinstance(g, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT, GraphPercXEntr)):
+        if g is not None and not isinstance(g, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT, GraphPercXEntr, GraphMixed)):
             raise TypeError("%s wraps GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, GraphCommStep, GraphCommReLU, "
-                            "GraphCommQu, GraphSAT or GraphPercXEntr; sparse graphs (GraphRRG*, GraphEA*), GraphQuant and the ensembles are not wired as g, "
+                            "GraphCommQu, GraphSAT, GraphPercXEntr or a GraphMixed of them; sparse graphs (GraphRRG*, GraphEA*), GraphQuant and the ensembles are not wired as g, "
                             "given a %s" % (type(self).__name__, type(g).__name__))
         if g is not None and g.N != len(fields):
             raise ValueError("incompatible length, fields size=%d graph size=%d" % (len(fields), g.N))       # AddFields.jl:65
         if not np.all(np.isfinite(fields)):
             raise ValueError("the fields must be finite")
         self.fields, self.N, self.X1 = fields, len(fields), g
+        if isinstance(g, GraphMixed):
+            self.slice_kind, self.K2 = 13, g.K2                                                               # RRRMC_RE_SLICE_MIXED
+            self.model_kind = 104 if self._sub else 103                                                       # RRRMC_MODEL_MIXED_ASF / _MIXED_AF
+            return
         self.slice_kind = _ensemble_slice_kind(g)
         self.K2 = int(getattr(g, "K2", 0)) if isinstance(g, _GraphComm) else 0
         if self.slice_kind == 11:

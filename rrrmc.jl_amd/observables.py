@@ -63,6 +63,15 @@ class SnapshotLog:
         return cols, bitmatrix_chunks(cols)
 
 
+def mixed_energies(X, C=None):
+    """the energy of every component of a ``GraphMixed`` (or of a field wrapper over one) — shape (n,) for one replica of the batch, (R, n)
+    otherwise; their sum from the left is ``energy(X, C)`` of the mix.  Read as ``LEenergies`` reads: the live configuration of the engine
+    that runs ``X`` (inside a hook: the sample's), or ``C``; recomputed from the configuration on the device, so a hook that calls it does
+    not change the run."""
+    from .graphs import _le_observable
+    return _le_observable(X, C, "mixed_energies", "mixed_energies")
+
+
 def _julia_num(x):
     """Julia prints Int energies as integers and Float64 ones with the shortest round-trip repr, as Python does."""
     return str(int(x)) if isinstance(x, (int, np.integer)) else repr(float(x))

@@ -13,6 +13,8 @@
                                             LDS and in global memory, beside GraphPercLinear(1001, 400)
   python tools/bench_models.py eare [R ...] GraphEARE / GraphEATLE(10, 3, 5) at β = 0.8 and 0.2 beside GraphSKRE(1024, 5): rrrMC (both builds)
                                             and standardMC
+  python tools/bench_models.py mixed [R ...] GraphMixed(GraphSK(1001), GraphPercStep(1001, 400), GraphSAT(1001, 3, 4.2)), β = 1: standardMC through
+                                            the wave and the thread build, and rrrMC through GraphAddSubFields over it
 """
 import json
 import os
@@ -409,6 +411,8 @@ def _timed_legs(pkg, X, R, legs, envs, beta, it, step, seed, reps):
             out[name]["build"] = eng.sat_build()
         if not rrr and type(X).__name__ == "GraphPercXEntr":
             out[name]["build"] = eng.xentr_build()
+        if type(X).__name__ == "GraphMixed" or type(getattr(X, "X1", None)).__name__ == "GraphMixed":
+            out[name]["build"] = eng.af_build() if rrr else eng.mixed_build()
         eng.close()
     for k in envs:
         os.environ.pop(k, None)
@@ -483,6 +487,26 @@ def bench_eare(L=10, D=3, M=5, gamma=1.5, lam=0.2, betas=(0.8, 0.2), iters=1 << 
             print(json.dumps(out), flush=True)
 
 
+def bench_mixed(N=1001, P=400, K=3, alpha=4.2, beta=1.0, iters=1 << 14, step=1 << 8, seed=0x5EED, reps=3):
+    """GraphMixed(GraphSK(1001), GraphPercStep(1001, 400), GraphSAT(1001, 3, 4.2)) under standardMC at β = 1 through both builds (one wavefront
+    per chain, one thread per chain) and the build the library picks by itself, and rrrMC on GraphAddSubFields(h, mixed) with Gaussian fields
+    through its two builds.  Kernel iterations/s per chain count: python tools/bench_models.py mixed 8 512 4096 16384"""
+    pkg = entry.load_package()
+    X = pkg.GraphMixed(pkg.GraphSK(N, seed=seed), pkg.GraphPercStep(N, P, seed=seed), pkg.GraphSAT(N, K, alpha, seed=seed))
+    Xw = pkg.GraphAddSubFields(np.random.default_rng(seed).normal(size=N), X)
+    envs = ("RRRMC_MIXED_NO_WAVE", "RRRMC_MIXED_WAVE", "RRRMC_AF_NO_LDS")
+    legs = (("wave", {"RRRMC_MIXED_WAVE": "1"}, False), ("thread", {"RRRMC_MIXED_NO_WAVE": "1"}, False), ("default", {}, False))
+    rlegs = (("rrr_lds", {}, True), ("rrr_global", {"RRRMC_AF_NO_LDS": "1"}, True))
+    for R in ([int(a) for a in sys.argv[2:]] or [8, 512, 4096, 16384]):
+        it = max(step, iters * 1024 // max(R, 1024))
+        out = {"model": "GraphMixed(SK, PercStep, SAT)", "N": N, "P": P, "clauses": X.graphs[2].M, "beta": beta, "replicas": R, "iters": it}
+        out.update(_timed_legs(pkg, X, R, legs, envs, beta, it, step, seed, reps))
+        print(json.dumps(out), flush=True)
+        out = {"model": "GraphAddSubFields(h, GraphMixed(SK, PercStep, SAT))", "N": N, "beta": beta, "replicas": R, "iters": it}
+        out.update(_timed_legs(pkg, Xw, R, rlegs, envs, beta, it, step, seed, reps))
+        print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "sk"
-    {"eare": bench_eare, "sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm, "sat": bench_sat, "satre": bench_satre, "tle": bench_tle, "xentr": bench_xentr}[which]()
+    {"mixed": bench_mixed, "eare": bench_eare, "sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm, "sat": bench_sat, "satre": bench_satre, "tle": bench_tle, "xentr": bench_xentr}[which]()
