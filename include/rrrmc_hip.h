@@ -276,6 +276,18 @@ RRRMC_API int32_t rrrmc_fetch_results(rrrmc_ctx *ctx, int64_t *Es_out, int64_t *
  * zero (beta = 1 at K = 3: 2 = two blocks of class 0, none of class 1).  RRRMC_SWEEP_GENERIC=1 in the environment of a call selects the
  * generic kernel.  Multi-device contexts report their first shard. */
 RRRMC_API int32_t rrrmc_sweep_build(rrrmc_ctx *ctx, int32_t *build_out);
+/* Which kernels the last standardMC or colour-sweep call on a sparse +-J context launched, and the layout they ran in (out: four values):
+ *   out[0]  the path: 0..3 = sweep_kernel MODE 0..3 (0 neighbour table in LDS, 1 table in HBM / byte offsets, 2 table in HBM / word
+ *           indices, 3 one word per site); 4 = big_mask_kernel + big_apply_kernel; 5 = big_mask_kernel + big_applyc_kernel (compact
+ *           masks); 6 = big_sweep_kernel (no mask pass); 7 = colour sweep, plain build; 8 = colour sweep, the build that counts accepted
+ *           moves; -1 = no such call yet
+ *   out[1]  K
+ *   out[2]  the chunk length C of the context
+ *   out[3]  lg2 of the replicas per workgroup of the big-N path (paths 4..6), else -1
+ * The layout is chosen at context creation; tests move it with RRRMC_FORCE_WIDE (1: table in HBM; 2: word indices, MODE 2, at any
+ * N <= 32767), RRRMC_FORCE_SINGLE, RRRMC_FORCE_BIG, RRRMC_BIG_NO_MASKS and RRRMC_BIG_LGR (0..5: 2^n replicas per workgroup, honoured where
+ * n is no larger than the size's own value).  Multi-device contexts report their first shard. */
+RRRMC_API int32_t rrrmc_sweep_layout(rrrmc_ctx *ctx, int32_t *out);
 
 /* ---- colour-parallel ("checkerboard") sweeps: build-defined extension for large sparse graphs ---------------------
  * The reference's standardMC is random-site (src/RRRMC.jl:113) and its kernel here keeps a replica group's spins in

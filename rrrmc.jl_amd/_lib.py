@@ -39,7 +39,7 @@ SYMBOLS = [
     "rrrmc_ctx_create_perc", "rrrmc_set_patterns", "rrrmc_gen_patterns",
     "rrrmc_ctx_create_comm", "rrrmc_ctx_create_comm_qu", "rrrmc_set_comm_patterns", "rrrmc_gen_comm_patterns",
     "rrrmc_ctx_create_quant_pattern", "rrrmc_quant_renergies", "rrrmc_quant_pattern_build",
-    "rrrmc_ctx_create_sat", "rrrmc_set_clauses", "rrrmc_sat_build", "rrrmc_sweep_build", "rrrmc_gen_ksat", "rrrmc_check_clauses",
+    "rrrmc_ctx_create_sat", "rrrmc_set_clauses", "rrrmc_sat_build", "rrrmc_sweep_build", "rrrmc_sweep_layout", "rrrmc_gen_ksat", "rrrmc_check_clauses",
     "rrrmc_ctx_create_tle", "rrrmc_tle_set_topology", "rrrmc_tle_check_topology", "rrrmc_tle_set_params", "rrrmc_tle_tables", "rrrmc_tle_cache", "rrrmc_tle_build",
     "rrrmc_ctx_create_af", "rrrmc_af_set_fields", "rrrmc_af_build", "rrrmc_af_cache",
     "rrrmc_ctx_create_mixed", "rrrmc_ctx_create_mixed_multi", "rrrmc_mixed_energies", "rrrmc_mixed_build",
@@ -279,6 +279,8 @@ def lib():
     L.rrrmc_set_clauses.argtypes = [vp, C.c_int64, C.c_int64, i32p, i8p]
     L.rrrmc_sweep_build.restype = C.c_int32
     L.rrrmc_sweep_build.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.rrrmc_sweep_layout.restype = C.c_int32
+    L.rrrmc_sweep_layout.argtypes = [vp, C.POINTER(C.c_int32)]
     L.rrrmc_sat_build.restype = C.c_int32
     L.rrrmc_sat_build.argtypes = [vp, C.POINTER(C.c_int32)]
     L.rrrmc_check_clauses.restype = C.c_int32

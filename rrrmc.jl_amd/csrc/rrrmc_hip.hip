@@ -157,6 +157,7 @@ struct rrrmc_ctx {
     bool big_bufs_ready = false;        // ensure_big_buffers has run
     bool big_mode = false;              // N does not fit LDS: random-site standardMC through plan_big_kernel / big_sweep_kernel (spins in HBM/L2)
     int sweep_build = -1;               // rrrmc_sweep_build: zero-block pattern of the sweep kernel the last standardMC call launched (0 generic, -1 none)
+    int sweep_path = -1;                // rrrmc_sweep_layout: the kernels the last standardMC / colour-sweep call launched (-1 none)
     int sweep_mode = 0;                 // sweep_kernel<K, MODE>: 0 LDS table / byte offsets, 1 HBM table / byte offsets, 2 HBM table / word indices
     int ncolors = 0;
     std::vector<int32_t> color_count;   // sites per colour
@@ -950,8 +951,9 @@ int32_t rrrmc_ctx_create(rrrmc_ctx** out, int32_t model, int64_t N, int64_t K, i
     };
     const int Cn = max_chunk(false), Cw = max_chunk(true), Cs = N > 8192 ? max_chunk(true, true) : 0;
     ctx->wide = Cw >= Cn + Cn / 8;
-    if (const char* fw = std::getenv("RRRMC_FORCE_WIDE")) ctx->wide = ctx->wide || fw[0] == '1';       // timing experiments
-    ctx->sweep_mode = !ctx->wide ? 0 : (N <= 8192 ? 1 : 2);
+    bool force_words = false;          // tests: "2" gives word indices (MODE 2) wherever they fit 16 bits, "1" the table in HBM / L2 in the size's own index form
+    if (const char* fw = std::getenv("RRRMC_FORCE_WIDE")) { force_words = fw[0] == '2' && N <= 32767; ctx->wide = ctx->wide || fw[0] == '1' || force_words; }       // tests / timing experiments
+    ctx->sweep_mode = !ctx->wide ? 0 : (N <= 8192 && !force_words ? 1 : 2);
     int C = ctx->wide ? Cw : Cn;
     // one word per site (the consumer pays three more instructions per neighbour): only where it buys clearly longer chunks
     bool single = N > 8192 && N <= 32767 && Cs >= 4 * kWave && Cs >= C + C / 2;
@@ -977,6 +979,8 @@ int32_t rrrmc_ctx_create(rrrmc_ctx** out, int32_t model, int64_t N, int64_t K, i
         // few replica groups: the acceptance masks of a batch are made by the whole device first (big_mask_kernel), the per-group
         // workgroups only apply them.  The mask buffers (2 x at most 4 GiB) bound the batch.
         ctx->big_lgr = big_lds_lgr(N);
+        // tests: fewer replicas per workgroup than the size needs (a smaller image always fits; everything below follows from the value)
+        if (const char* e = std::getenv("RRRMC_BIG_LGR")) { if (e[0] >= '0' && e[0] <= '5' && !e[1] && e[0] - '0' <= ctx->big_lgr) ctx->big_lgr = e[0] - '0'; }
         ctx->big_cm = big_masks_compact((int)K, ctx->big_lgr);
         // four mask words per (slot, group), or one per (slot, workgroup) where a workgroup's mask bits fit a word
         const int64_t per_slot = (int64_t)ctx->G * (ctx->big_cm ? 4 * (32 >> ctx->big_lgr) : 16);
@@ -1381,7 +1385,9 @@ int32_t rrrmc_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int6
     if (ctx->model != RRRMC_MODEL_SPARSE_PM1) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "standardMC is not wired for this model on the device: use rrrmc_rrr_mc_async");
     if (!ctx->lds_mode && !ctx->big_mode) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "N=%lld is beyond the random-site kernels (N <= 2^20): use rrrmc_colored_sweeps_async", (long long)ctx->N);
     if ((rc = pm1_refuse_beta(ctx, beta))) return rc;
-    return pm1_standard_mc_async(ctx, beta, iters, step);
+    if ((rc = pm1_standard_mc_async(ctx, beta, iters, step))) return rc;
+    ctx->sweep_path = ctx->lds_mode ? ctx->sweep_mode : !ctx->big_masks ? 6 : ctx->big_cm ? 5 : 4;
+    return RRRMC_OK;
 }
 
 int32_t rrrmc_standard_mc_fast_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t step)
@@ -1711,6 +1717,7 @@ int32_t rrrmc_colored_sweeps_async(rrrmc_ctx* ctx, double beta, int64_t sweeps, 
     ctx->results_valid = true;
     ctx->timing_valid = true;
     ctx->colored_call = true;
+    ctx->sweep_path = ctx->color_count_acc ? 8 : 7;
     return RRRMC_OK;
 }
 
@@ -1922,6 +1929,18 @@ int32_t rrrmc_sweep_build(rrrmc_ctx* ctx, int32_t* build_out)
     if (is_multi(ctx)) return rrrmc_sweep_build(ctx->kids[0], build_out);
     if (ctx->model != RRRMC_MODEL_SPARSE_PM1) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_sweep_build is for sparse +-J contexts");
     *build_out = ctx->sweep_build;
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_sweep_layout(rrrmc_ctx* ctx, int32_t* out)
+{
+    if (!ctx || !out) return RRRMC_ERR_INVALID_ARG;
+    if (is_multi(ctx)) return rrrmc_sweep_layout(ctx->kids[0], out);
+    if (ctx->model != RRRMC_MODEL_SPARSE_PM1) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_sweep_layout is for sparse +-J contexts");
+    out[0] = ctx->sweep_path;
+    out[1] = (int32_t)ctx->K;
+    out[2] = ctx->C;
+    out[3] = ctx->sweep_path >= 4 && ctx->sweep_path <= 6 ? ctx->big_lgr : -1;
     return RRRMC_OK;
 }
 

@@ -380,6 +380,14 @@ class Engine:
         check(lib().rrrmc_sweep_build(self._ctx, C.byref(b)), self._ctx)
         return b.value
 
+    def sweep_layout(self):
+        """What the last standardMC / colour-sweep call on a sparse +-J graph ran, as (path, K, C, big_lgr): path 0..3 = sweep_kernel
+        MODE 0..3, 4 = big_mask + big_apply, 5 = big_mask + big_applyc, 6 = big_sweep, 7 / 8 = colour sweep plain / counting, -1 = no
+        call yet; C the context's chunk length; big_lgr = lg2 of the replicas per workgroup on paths 4..6, else -1."""
+        out = (C.c_int32 * 4)(-2, -2, -2, -2)
+        check(lib().rrrmc_sweep_layout(self._ctx, out), self._ctx)
+        return tuple(int(v) for v in out)
+
     def sat_build(self):
         """The kernel build the last standardMC call on a stand-alone GraphSAT ran: 0 = none yet, 1 = one thread per replica, 2 = one
         wavefront per replica."""

@@ -23,35 +23,39 @@ def _graph(pkg, kind, seed):
 
 
 CASES = [
-    # kind,            R,   beta, iters, step
-    (("rrg", 10, 3),   32,  2.0,  10000, 100),    # test/runtests.jl:36,125-130 (GraphRRG(10,3), beta=2, 10^4 iters, step 100)
-    (("ea", 2, 3),     32,  2.0,  10000, 100),    # runtests.jl:46 GraphEA(2,3): L=2 => doubled neighbours
-    (("ea", 3, 2),     32,  2.0,  10000, 100),    # runtests.jl:56 GraphEA(3,2)
-    (("rrg", 128, 3),  1,   1.0,  20000, 1000),   # BASELINE config 1 shape (1 chain)
-    (("rrg", 128, 3),  40,  1.0,  5000,  1),      # step = 1 (reference default), R not a multiple of 32
-    (("rrg", 256, 3),  96,  0.5,  30000, 4096),
-    (("rrg", 1024, 3), 64,  1.0,  50000, 1024),
-    (("rrg", 4096, 3), 64,  1.0,  40000, 4096),   # BASELINE config 2 graph, few replicas
-    (("ea", 8, 3),     64,  1.0,  30000, 512),    # K = 6
-    (("rrg", 64, 5),   32,  0.7,  8000,  64),     # odd K > 3
-    (("rrg", 50, 4),   32,  1.3,  8000,  77),     # even K, step not dividing anything
-    (("circ", 100, 7), 32,  0.4,  5000,  500),    # K = 7 (4 classes)
-    (("rrg", 64, 3),   32,  0.0,  3000,  100),    # beta = 0: everything accepted
-    (("rrg", 64, 3),   32,  50.0, 3000,  100),    # very low temperature: thresholds of ~2^-144 underflow the 64-bit fraction
-    (("rrg", 5400, 3), 32,  1.0,  40000, 5000),   # about the largest N whose neighbour table still fits LDS next to a full chunk
-    (("rrg", 6000, 3), 32,  1.0,  40000, 5000),   # WIDE build by choice: word offsets, neighbour table in HBM/L2
-    (("rrg", 8192, 3), 32,  1.0,  60000, 8192),
-    (("rrg", 8200, 3), 32,  1.0,  60000, 8192),   # WIDE build by necessity (byte offsets no longer fit 16 bits)
-    (("rrg", 10000, 3), 40, 2.0,  80000, 10000),  # the size of the reference's scripts (scripts/scripts.jl:23 N = 10_000)
-    (("rrg", 12000, 4), 32, 1.0,  50000, 5000),   # even K, shorter chunks (LDS)
-    (("ea", 24, 3),    32,  1.0,  60000, 6000),   # EA 24^3 = 13824 spins, K = 6
-    (("rrg", 16384, 3), 32, 1.0,  70000, 16384),  # one word per site (MODE 3): half the state, chunks three times as long
-    (("rrg", 16500, 4), 32, 1.0,  50000, 7000),   # near the end of the two-copy layout's range (MODE 3 by choice)
+    # kind,            R,   beta, iters, step, path (what Engine.sweep_layout reports: sweep_kernel MODE 0..3)
+    (("rrg", 10, 3),   32,  2.0,  10000, 100, 0),    # test/runtests.jl:36,125-130 (GraphRRG(10,3), beta=2, 10^4 iters, step 100)
+    (("ea", 2, 3),     32,  2.0,  10000, 100, 0),    # runtests.jl:46 GraphEA(2,3): L=2 => doubled neighbours
+    (("ea", 3, 2),     32,  2.0,  10000, 100, 0),    # runtests.jl:56 GraphEA(3,2)
+    (("rrg", 128, 3),  1,   1.0,  20000, 1000, 0),   # BASELINE config 1 shape (1 chain)
+    (("rrg", 128, 3),  40,  1.0,  5000,  1, 0),      # step = 1 (reference default), R not a multiple of 32
+    (("rrg", 256, 3),  96,  0.5,  30000, 4096, 0),
+    (("rrg", 1024, 3), 64,  1.0,  50000, 1024, 0),
+    (("rrg", 4096, 3), 64,  1.0,  40000, 4096, 1),   # BASELINE config 2 graph, few replicas (table in HBM: C = 1536 against 1088)
+    (("ea", 8, 3),     64,  1.0,  30000, 512, 0),    # K = 6
+    (("rrg", 64, 5),   32,  0.7,  8000,  64, 0),     # odd K > 3
+    (("rrg", 50, 4),   32,  1.3,  8000,  77, 0),     # even K, step not dividing anything
+    (("circ", 100, 7), 32,  0.4,  5000,  500, 0),    # K = 7 (4 classes)
+    (("rrg", 64, 3),   32,  0.0,  3000,  100, 0),    # beta = 0: everything accepted
+    (("rrg", 64, 3),   32,  50.0, 3000,  100, 0),    # very low temperature: thresholds of ~2^-144 underflow the 64-bit fraction
+    (("rrg", 5400, 3), 32,  1.0,  40000, 5000, 1),   # the table would still fit LDS beside a chunk of 832; the context takes 1408 without it
+    (("rrg", 6000, 3), 32,  1.0,  40000, 5000, 1),   # WIDE build by choice: neighbour table in HBM/L2, byte offsets (MODE 1)
+    (("rrg", 8192, 3), 32,  1.0,  60000, 8192, 1),   # the last N with byte offsets (MODE 1)
+    (("rrg", 8200, 3), 32,  1.0,  60000, 8192, 2),   # WIDE build by necessity (byte offsets no longer fit 16 bits): word indices, MODE 2
+    (("rrg", 10000, 3), 40, 2.0,  80000, 10000, 3),  # the size of the reference's scripts (scripts/scripts.jl:23 N = 10_000)
+    (("rrg", 12000, 4), 32, 1.0,  50000, 5000, 3),   # even K, shorter chunks (LDS); one word per site by choice
+    (("ea", 24, 3),    32,  1.0,  60000, 6000, 3),   # EA 24^3 = 13824 spins, K = 6
+    (("rrg", 16384, 3), 32, 1.0,  70000, 16384, 3),  # one word per site (MODE 3): half the state, chunks three times as long
+    (("rrg", 16500, 4), 32, 1.0,  50000, 7000, 3),   # near the end of the two-copy layout's range (MODE 3 by choice)
+    # (new cases go at the end: the test ids carry a case's position in this list)
+    (("rrg", 1758, 3), 32,  1.0,  20000, 2000, 0),   # the largest N at K = 3 that keeps the neighbour table in LDS (MODE 0: C = 1600 against 1728 without it)
+    (("rrg", 1760, 3), 32,  1.0,  20000, 2000, 1),   # ... and the first that gives it up for a chunk an eighth longer (1728 against 1536: Cw >= Cn + Cn / 8)
 ]
 
 
-@pytest.mark.parametrize("kind,R,beta,iters,step", CASES)
+@pytest.mark.parametrize("kind,R,beta,iters,step", [c[:5] for c in CASES])
 def test_standard_mc_bit_exact(pkg, oracle, kind, R, beta, iters, step):
+    path = {c[:5]: c[5] for c in CASES}[(kind, R, beta, iters, step)]
     seed = 0xC0FFEE + 7 * kind[1] + R
     X = _graph(pkg, kind, seed)
     with pkg.Engine(X, R) as eng:
@@ -60,9 +64,11 @@ def test_standard_mc_bit_exact(pkg, oracle, kind, R, beta, iters, step):
         C0 = eng.get_config()
         E0 = eng.energy()
         Es, acc = eng.standard_mc(beta, iters, step)
+        layout = eng.sweep_layout()
         C1 = eng.get_config()
         E1 = eng.energy()
         lf = eng.fields()
+    assert layout[0] == path and layout[1] == X.A.shape[1], layout          # the layout the case's comment names is the one that ran
     A, J = X.A, X.J.astype(np.int32)
     assert (C0.s == oracle.init_configs(seed, 0, R, X.N)).all()
     Es_ref, ch_ref, acc_ref = oracle.standard_mc_sparse_batch(A, J, beta, iters, step, seed, C0.s, form="ea" if kind[0] == "ea" else "rrg")
