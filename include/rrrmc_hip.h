@@ -152,7 +152,12 @@ enum rrrmc_model {
        rrrmc_ctx_create_mixed_multi (rrrmc_ctx_create_multi cannot carry a component list and refuses them) */
     RRRMC_MODEL_MIXED = 102,          /* GraphMixed(graphs...) */
     RRRMC_MODEL_MIXED_AF = 103,       /* GraphAddFields(h, GraphMixed(graphs...)) */
-    RRRMC_MODEL_MIXED_ASF = 104       /* GraphAddSubFields(h, GraphMixed(graphs...)) */
+    RRRMC_MODEL_MIXED_ASF = 104,      /* GraphAddSubFields(h, GraphMixed(graphs...)) */
+    /* the regular 3-spin model (src/graphs/PSpin3.jl) and the two field wrappers over it: the models of contexts made by
+       rrrmc_ctx_create_pspin3; selectors of rrrmc_ctx_create_multi (N, K; M ignored) */
+    RRRMC_MODEL_PSPIN3 = 105,         /* GraphPSpin3(N, K): energy = -(sum over the triples of the three spins' product) (reported as Float64) */
+    RRRMC_MODEL_PSPIN3_AF = 106,      /* GraphAddFields(h, GraphPSpin3) */
+    RRRMC_MODEL_PSPIN3_ASF = 107      /* GraphAddSubFields(h, GraphPSpin3) */
 };
 
 /* slice families of rrrmc_ctx_create_re */
@@ -174,8 +179,10 @@ enum rrrmc_re_slice {
     RRRMC_RE_SLICE_SPARSE_F64 = 12, /* GraphEANormal / GraphRRGNormal (src/graphs/EA.jl:534-680, RRG.jl:503-617): (A, J) with rrrmc_set_graph_f64.
                                        The slice graph has a K of its own, so these contexts are made by rrrmc_ctx_create_re_f64 / _le_f64 /
                                        _tle_f64; rrrmc_ctx_create_re / _le / _tle refuse the kind and name that creator */
-    RRRMC_RE_SLICE_MIXED = 13       /* GraphMixed: the g of the field wrappers made by rrrmc_ctx_create_mixed only.  rrrmc_ctx_create_af, _re, _le,
+    RRRMC_RE_SLICE_MIXED = 13,      /* GraphMixed: the g of the field wrappers made by rrrmc_ctx_create_mixed only.  rrrmc_ctx_create_af, _re, _le,
                                        _tle and _quant_pattern refuse it, and so does a component list (a mix does not nest) */
+    RRRMC_RE_SLICE_PSPIN3 = 14      /* GraphPSpin3 (src/graphs/PSpin3.jl): the g of the field wrappers made by rrrmc_ctx_create_pspin3 only.
+                                       rrrmc_ctx_create_af, _re, _le, _tle, _quant_pattern and _mixed refuse it */
 };
 
 /* Library ABI version (major*10000 + minor*100 + patch). */
@@ -630,6 +637,36 @@ RRRMC_API int32_t rrrmc_mixed_energies(rrrmc_ctx *ctx, double *E_out);
  * thread per chain, 2 one wavefront per chain.  Up to 16384 chains run the wave build; RRRMC_MIXED_NO_WAVE=1 / RRRMC_MIXED_WAVE=1 force a
  * build; the builds give the same bits. */
 RRRMC_API int32_t rrrmc_mixed_build(rrrmc_ctx *ctx, int32_t *build_out);
+
+/* ---- The regular 3-spin model (src/graphs/PSpin3.jl; RRRMC_MODEL_PSPIN3, RRRMC_MODEL_PSPIN3_AF, RRRMC_MODEL_PSPIN3_ASF) ------
+ * rrrmc_ctx_create_pspin3: R chains of GraphPSpin3(N, K) -- K layers, each a partition of the N sites into N / 3 triples, all couplings
+ * +1 -- or of a field wrapper over it.  wrap: 0 the graph itself, 1 GraphAddFields(h, g), 2 GraphAddSubFields(h, g).  Limits: N <= 65535
+ * (16-bit site ids), N % 3 == 0, 1 <= K <= 16; RRRMC_ERR_UNSUPPORTED beyond.  Spins: one BitVector of N bits per chain (chunks of 64).
+ * rrrmc_set_pspin3: the partner table A[N][2K], 0-based: A[i][2k], A[i][2k+1] are the two partners of i in layer k (PSpin3.jl:32-43).
+ * Checked: every id in range; the two partners of a slot distinct and different from i; for slot k of i = (y, z), y's list holds the pair
+ * {i, z} and z's list the pair {i, y} as often as i's holds {y, z} (a pair that two layers share counts twice).  A malformed table is
+ * RRRMC_ERR_INVALID_ARG.  Then rrrmc_af_set_fields for wrap 1 or 2.
+ * energy = -(sum over the triples of the product of the three spins), delta_energy(i) = 2 (2c - K) with c the layers whose triple has the
+ * product +1: integers, reported through the Float64 entry points as exact doubles; recomputed from the spins (the reference's
+ * LocalFields{Int} is an exact function of the configuration).
+ * Samplers.  wrap 0: rrrmc_standard_mc_async (the SITE / ACCEPT_F64 streams and det_exp; every beta but NaN -- beta = +inf with
+ * delta_energy = 0 is rejected, as in the reference); rrrmc_rrr_mc_async, rrrmc_bkl_mc_async, rrrmc_wtm_mc_async and rrrmc_extremal_opt_async
+ * answer RRRMC_ERR_UNSUPPORTED and name the field wrappers as the way to run rrrMC.  wrap 1 and 2: rrrmc_rrr_mc_async and
+ * rrrmc_standard_mc_async as on every context of rrrmc_ctx_create_af (rrrmc_af_cache, rrrmc_af_build too).  rrrmc_set_resume,
+ * rrrmc_set_debug_checks (the tracked E against the energy of the configuration), timing, rrrmc_energy_f64 / rrrmc_tracked_energy_f64,
+ * spins, seeds and rrrmc_ctx_create_multi as for rrrmc_ctx_create_sat.
+ * rrrmc_pspin_build: the kernel build of the last standardMC call on wrap 0 (the first shard of a multi-device context): 0 none yet, 1 one
+ * thread per chain, 2 one wavefront per chain (64 consecutive iterations side by side, retired in the chain's order).  Up to 16384 chains
+ * run the wave build (the two cross between 16384 and 32768 chains, profiles/r20/pspin3.md); RRRMC_PSPIN_NO_WAVE=1 / RRRMC_PSPIN_WAVE=1
+ * force a build; the builds give the same bits. */
+RRRMC_API int32_t rrrmc_ctx_create_pspin3(rrrmc_ctx **out, int64_t N, int64_t K, int32_t wrap, int64_t R, int32_t device, uint32_t replica0);
+RRRMC_API int32_t rrrmc_set_pspin3(rrrmc_ctx *ctx, const int32_t *A);
+RRRMC_API int32_t rrrmc_pspin_build(rrrmc_ctx *ctx, int32_t *build_out);
+/* The constructor's K randperm(N) (PSpin3.jl:32-43; the reference's rand is unpinned) on a Philox stream of its own (PSPIN = 13): layer k
+ * is the Fisher-Yates shuffle l = 0 .. N-1; for j = N-1 down to 1: swap(l[j], l[floor(u64 * (j+1) / 2^64)]) with the draws k (N-1) + (N-1-j)
+ * of the stream; consecutive threes of l are the triples (v1, v2, v3): v1 lists (v2, v3), v2 (v1, v3), v3 (v1, v2).  A_out[N][2K], 0-based.
+ * A host function: no device is touched. */
+RRRMC_API int32_t rrrmc_gen_pspin3(int64_t N, int64_t K, uint64_t seed, int32_t *A_out);
 
 /* rrrMC(X::DoubleGraph, beta, iters; step, staged_thr, staged_thr_fact) (src/RRRMC.jl:221-290) for all R replicas.
  *   fourK = round(2/beta * log(coth(beta * Gamma / M)), digits = 8)  (QT.jl:165) is computed by the caller.

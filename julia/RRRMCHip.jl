@@ -391,6 +391,12 @@ function Ctx(X::AddFieldsGraph, R::Integer; device = 0, replica0 = 0, devices = 
         GC.@preserve h check(ccall((:rrrmc_af_set_fields, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, h), ctx.p)
         return ctx
     end
+    if g isa RRRMC.PSpin3.GraphPSpin3          # a wrapper over a GraphPSpin3: rrrmc_ctx_create_pspin3 with wrap 1 / 2, the table, then the fields
+        ctx = pspin_ctx(g, sub ? 2 : 1, R; device = device, replica0 = replica0, devices = devices)
+        h = Vector{Float64}(X.X0.fields)
+        GC.@preserve h check(ccall((:rrrmc_af_set_fields, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), ctx.p, h), ctx.p)
+        return ctx
+    end
     kind = g isa XEntrGraph ? 11 : ens_kind(typeof(g), sub ? "GraphAddSubFields" : "GraphAddFields")          # (no ensemble takes GraphPercXEntr)
     K2 = g isa CommGraph ? g.K2 : 0
     ref = Ref{Ptr{Cvoid}}(C_NULL)
@@ -475,6 +481,33 @@ function Ctx(X::RRRMC.SAT.GraphSAT, R::Integer; device = 0, replica0 = 0, device
         ref[] = create(SAT, X.N, 0, 0, R; replica0 = replica0, devices = devices)
     end
     return set_patterns!(Ctx(ref[], R, X.N, true), X)
+end
+# ---- GraphPSpin3 (src/graphs/PSpin3.jl), stand-alone: standardMC only (rrrMC / bklMC / wtmMC / extremal_opt answer RRRMC_ERR_UNSUPPORTED ----
+# and name the field wrappers); rrrMC through GraphAddFields / GraphAddSubFields over it.  The integer energies arrive as exact Float64s.
+# wrap: 0 the graph, 1 / 2 the wrappers (RRRMC_MODEL_PSPIN3 + wrap as the multi-device selector).  X.A goes up 0-based, [N][2K] row-major.
+# (Checked statically only, as the rest of this file.)
+const PSPIN3 = 105
+function pspin_ctx(X::RRRMC.PSpin3.GraphPSpin3{K}, wrap::Integer, R::Integer; device = 0, replica0 = 0, devices = nothing) where {K}
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    if devices === nothing
+        check(ccall((:rrrmc_ctx_create_pspin3, LIB), Int32, (Ref{Ptr{Cvoid}}, Int64, Int64, Int32, Int64, Int32, UInt32), ref, X.N, K, wrap, R, device, replica0))
+    else
+        ref[] = create(PSPIN3 + wrap, X.N, K, 0, R; replica0 = replica0, devices = devices)
+    end
+    ctx = Ctx(ref[], R, X.N, true)
+    A = Matrix{Int32}(undef, 2K, X.N)
+    for i = 1:X.N, q = 1:2K
+        A[q, i] = X.A[i][q] - 1
+    end
+    GC.@preserve A check(ccall((:rrrmc_set_pspin3, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}), ctx.p, A), ctx.p)
+    return ctx
+end
+Ctx(X::RRRMC.PSpin3.GraphPSpin3, R::Integer; device = 0, replica0 = 0, devices = nothing) = pspin_ctx(X, 0, R; device = device, replica0 = replica0, devices = devices)
+# which kernel ran the last standardMC call on a stand-alone GraphPSpin3: 0 none yet, 1 one thread per chain, 2 one wavefront per chain
+function pspin_build(ctx::Ctx)
+    b = Ref{Int32}(0)
+    check(ccall((:rrrmc_pspin_build, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), ctx.p, b), ctx.p)
+    return Int(b[])
 end
 # which build of the sweep kernel the last standardMC call on a sparse +-J graph launched: -1 none, 0 generic, else its zero-block pattern
 function sweep_build(ctx::Ctx)

@@ -45,6 +45,7 @@ SYMBOLS = [
     "rrrmc_ctx_create_mixed", "rrrmc_ctx_create_mixed_multi", "rrrmc_mixed_energies", "rrrmc_mixed_build",
     "rrrmc_ctx_create_perc_xentr", "rrrmc_set_loss_table", "rrrmc_xentr_build", "rrrmc_perc_step_energy",
     "rrrmc_ctx_create_re_f64", "rrrmc_ctx_create_le_f64", "rrrmc_ctx_create_tle_f64", "rrrmc_gen_couplings_uniform",
+    "rrrmc_ctx_create_pspin3", "rrrmc_set_pspin3", "rrrmc_pspin_build", "rrrmc_gen_pspin3",
 ]
 
 
@@ -281,6 +282,14 @@ def lib():
     L.rrrmc_sweep_build.argtypes = [vp, C.POINTER(C.c_int32)]
     L.rrrmc_sweep_layout.restype = C.c_int32
     L.rrrmc_sweep_layout.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.rrrmc_ctx_create_pspin3.restype = C.c_int32
+    L.rrrmc_ctx_create_pspin3.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_uint32]
+    L.rrrmc_set_pspin3.restype = C.c_int32
+    L.rrrmc_set_pspin3.argtypes = [vp, _I32OrNull]
+    L.rrrmc_pspin_build.restype = C.c_int32
+    L.rrrmc_pspin_build.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.rrrmc_gen_pspin3.restype = C.c_int32
+    L.rrrmc_gen_pspin3.argtypes = [C.c_int64, C.c_int64, C.c_uint64, _I32OrNull]
     L.rrrmc_sat_build.restype = C.c_int32
     L.rrrmc_sat_build.argtypes = [vp, C.POINTER(C.c_int32)]
     L.rrrmc_check_clauses.restype = C.c_int32

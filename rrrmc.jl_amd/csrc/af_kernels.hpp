@@ -1,6 +1,7 @@
 // gfx950 kernels for GraphAddFields / GraphAddSubFields (src/graphs/AddFields.jl:16-123): a DoubleGraph whose inner graph X0 = GraphAF(h)
 // is N independent external fields (energy Σ_i h_i σ_i, delta_energy −2 σ_i h_i, no neighbours) over one graph g of N spins — any of the
-// nine slice kinds of re_kernels.hpp, or GraphPercXEntr (xentr_kernels.hpp), used as ONE slice (M = 1, so the ABI site order is the slice's own).
+// nine slice kinds of re_kernels.hpp, GraphPercXEntr (xentr_kernels.hpp) or GraphPSpin3 (pspin_kernels.hpp), used as ONE slice (M = 1, so
+// the ABI site order is the slice's own).
 //   GraphAddFields    (sub = 0): E = energy(X0) + energy(g), ΔE = ΔE(X0) + ΔE(g), residual = ΔE(g)
 //   GraphAddSubFields (sub = 1): E = energy(g),              ΔE = ΔE(g),          residual = ΔE(g) − ΔE(X0)
 // Samplers: rrrMC(X::DoubleGraph) (src/RRRMC.jl:221-290) over DeltaECacheCont (src/DeltaE.jl:297-410) and the DynamicSampler
@@ -59,6 +60,7 @@ __device__ __forceinline__ double af_g_energy(const ReParams& P, long long n, do
     else if constexpr (SLICE == RE_SKN || SLICE == RE_PXE) return eskn;          // (a Float64 sum made in the reference's order)
     else if constexpr (kPercSlice<SLICE>) return perc_energy_of<SLICE == RE_PLIN>(n, P.pc.sN);
     else if constexpr (kCommSlice<SLICE> || SLICE == RE_SAT) return (double)n;
+    else if constexpr (SLICE == RE_PSPIN3) return (double)(n / 3);                // every triple was met by its three sites (PSpin3.jl:88-89)
     else return 0.0;
 }
 
@@ -109,6 +111,8 @@ __global__ __launch_bounds__(kAfInitThreads) void af_init_kernel(AfParams A, int
         comm_init_rows<comm_kind_of_slice(SLICE)>(P.cm, comm_view<comm_kind_of_slice(SLICE)>(P.cm, r), sp, N, N, s_n);
     } else if constexpr (SLICE == RE_SAT) {
         sat_init_rows(P.sat, sp, N, 0, 1, s_n);
+    } else if constexpr (SLICE == RE_PSPIN3) {
+        pspin_init_row(P.ps3, sp, s_n);
     } else if constexpr (SLICE == RE_PXE) {
         __shared__ double s_t[kPercPmax];
         const double Eg = xentr_init_chain(P.pc, P.xe, P.pc.ds + (size_t)r * 64 * P.pc.PW, 1, sp, N, s_t);

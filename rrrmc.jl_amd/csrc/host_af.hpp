@@ -4,11 +4,15 @@
 // frame of a sampler call is theirs (host_ens.hpp).  The model <-> (wrapper, kind of g) relation is the table of af_models.hpp.
 // Included by rrrmc_hip.hip inside its anonymous namespace, after host_ens.hpp; not a stand-alone translation unit.
 // (a mixed context, host_mixed.hpp, is one of the family: the stand-alone GraphMixed runs as a GraphAddSubFields whose fields are never read)
-inline bool is_af(const rrrmc_ctx* ctx) { return af_family(ctx->model) != AF_NONE || is_mixed(ctx); }
+// (so is a wrapper over a GraphPSpin3, host_pspin.hpp, whose model ids have a lookup of their own: af_slice_of / af_sub_of below)
+inline bool is_af(const rrrmc_ctx* ctx) { return af_family(ctx->model) != AF_NONE || is_mixed(ctx) || pspin_af(ctx); }
+// the kind of g and the wrapper of a context of the family that is no mix
+inline int af_slice_of(const rrrmc_ctx* ctx) { return pspin_af(ctx) ? (int)RE_PSPIN3 : (int)af_slice(ctx->model); }
+inline bool af_sub_of(const rrrmc_ctx* ctx) { return pspin_af(ctx) ? pspin_wrap(ctx->model) == 2 : af_family(ctx->model) == AF_ADDSUB; }
 inline const char* af_graph_name(const rrrmc_ctx* ctx)
 {
     if (is_mixed(ctx)) return mixed_wrap(ctx->model) == 0 ? "GraphMixed" : mixed_wrap(ctx->model) == 2 ? "GraphAddSubFields over a GraphMixed" : "GraphAddFields over a GraphMixed";
-    return af_family(ctx->model) == AF_ADDSUB ? "GraphAddSubFields" : "GraphAddFields";
+    return af_sub_of(ctx) ? "GraphAddSubFields" : "GraphAddFields";
 }
 int32_t mixed_run_init(rrrmc_ctx* ctx, double beta, bool cache);          // host_mixed.hpp
 int32_t mixed_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, int64_t step, double staged_thr, double staged_thr_fact);
@@ -19,8 +23,8 @@ int32_t af_not_wired(rrrmc_ctx* ctx, const char* sampler)
 }
 int32_t af_needs_fields(rrrmc_ctx* ctx) { return fail(ctx, RRRMC_ERR_STATE, "a %s needs its fields: call rrrmc_af_set_fields first", af_graph_name(ctx)); }
 
-// g is any ensemble slice kind, or GraphPercXEntr (which no ensemble takes): the wrappers' kernels are built over this set
-using AfSlices = SliceSet<RE_EMPTY, RE_SK, RE_SKN, RE_PSTEP, RE_PLIN, RE_CSTEP, RE_CRELU, RE_SAT, RE_CQU, RE_PXE>;
+// g is any ensemble slice kind, or GraphPercXEntr or GraphPSpin3 (which no ensemble takes): the wrappers' kernels are built over this set
+using AfSlices = SliceSet<RE_EMPTY, RE_SK, RE_SKN, RE_PSTEP, RE_PLIN, RE_CSTEP, RE_CRELU, RE_SAT, RE_CQU, RE_PXE, RE_PSPIN3>;
 static_assert((int)RE_PXE == RRRMC_RE_SLICE_PERC_XENTR, "ReSlice is rrrmc_re_slice");
 
 constexpr int64_t kAfNmax = 65535;          // N of a wrapper over GraphEmpty / GraphSK / GraphSKNormal (the other kinds bring their own bound)
@@ -108,20 +112,21 @@ AfParams af_params(rrrmc_ctx* ctx, double beta)
 {
     AfParams A{};
     ReParams& P = A.re;
-    const int slice = af_slice(ctx->model);
+    const int slice = af_slice_of(ctx);
     if (slice == RE_SK) { P.Jb = ctx->q_Jb; P.Wk = (int)ctx->q_Wk; P.sN = std::sqrt((double)ctx->N); }
     if (slice == RE_SKN) { P.Jd = ctx->sk_J; P.slf = ctx->q_slf; P.smv = ctx->q_smv; P.scur = ctx->q_scur; }
     if (slice == RE_PSTEP || slice == RE_PLIN) P.pc = perc_params(ctx, 1);
     if (slice == RE_PXE) { P.pc = perc_params(ctx, 1); P.xe = xentr_params(ctx); }
     if (slice == RE_CSTEP || slice == RE_CRELU || slice == RE_CQU) P.cm = comm_params(ctx, 1);
     if (slice == RE_SAT) P.sat = sat_table(ctx);
+    if (slice == RE_PSPIN3) P.ps3 = pspin_table(ctx);
     P.abi = ctx->q_spins; P.sp = ctx->q_spins;          // M = 1: the ABI site order is the slice's own
     P.zz = ctx->q_z; P.E_cur = ctx->sk_E; P.acc_rate = ctx->q_accrate; P.stats = ctx->q_stats; P.Es = ctx->sk_Es; P.flag = ctx->dbg_flag;
     P.beta = beta;
     P.k0 = (uint32_t)ctx->seed; P.k1 = (uint32_t)(ctx->seed >> 32); P.replica0 = ctx->replica0;
     P.Nk = (int)ctx->N; P.M = 1; P.L = 0; P.N = (int)ctx->N; P.W = (int)ctx->qW; P.R = (int)ctx->R;
     A.h = ctx->af_h; A.dEs = ctx->af_dEs; A.v = ctx->af_v; A.ps = ctx->af_ps; A.tref = ctx->af_tref; A.status = ctx->af_status;
-    A.sub = af_family(ctx->model) == AF_ADDSUB ? 1 : 0; A.levs = ctx->af_levs; A.N2 = (int)ctx->af_N2;
+    A.sub = af_sub_of(ctx) ? 1 : 0; A.levs = ctx->af_levs; A.N2 = (int)ctx->af_N2;
     return A;
 }
 
@@ -131,7 +136,7 @@ int32_t af_run_init(rrrmc_ctx* ctx, double beta, bool cache)
     if (is_mixed(ctx)) return mixed_run_init(ctx, beta, cache);
     const AfParams A = af_params(ctx, beta);
     const dim3 grid((unsigned)ctx->R), blk(kAfInitThreads);
-    if (!with_slice(AfSlices{}, af_slice(ctx->model), [&](auto s) { hipLaunchKernelGGL(af_init_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, A, cache ? 1 : 0); }))
+    if (!with_slice(AfSlices{}, af_slice_of(ctx), [&](auto s) { hipLaunchKernelGGL(af_init_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, A, cache ? 1 : 0); }))
         return ens_bad_slice(ctx);
     HIP_TRY(ctx, hipGetLastError());
     return RRRMC_OK;
@@ -145,7 +150,7 @@ int32_t af_debug_check(rrrmc_ctx* ctx, const AfParams& A0, bool cache)
     AfParams A = A0;
     A.re.flag = ctx->dbg_flag;
     const dim3 grid((unsigned)((ctx->R + 63) / 64)), blk(64);
-    if (!with_slice(AfSlices{}, af_slice(ctx->model), [&](auto s) { hipLaunchKernelGGL(af_check_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, A, cache ? 1 : 0); }))
+    if (!with_slice(AfSlices{}, af_slice_of(ctx), [&](auto s) { hipLaunchKernelGGL(af_check_kernel<decltype(s)::value>, grid, blk, 0, ctx->stream, A, cache ? 1 : 0); }))
         return ens_bad_slice(ctx);
     HIP_TRY(ctx, hipGetLastError());
     return RRRMC_OK;
@@ -173,7 +178,7 @@ int32_t af_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, i
     else { rc = af_run_init(ctx, beta, !standard); if (rc) return rc; }
     AfParams A = af_params(ctx, beta);
     ens_call_params(ctx, C, iters, step, staged_thr, staged_thr_fact, &A.re);
-    const int slice = af_slice(ctx->model);
+    const int slice = af_slice_of(ctx);
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_sweep[0], st));
     if (standard) {

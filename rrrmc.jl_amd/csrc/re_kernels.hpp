@@ -20,6 +20,7 @@
 #include "xentr_kernels.hpp" // the cross-entropy perceptron as the g of a field wrapper (XentrParams, xentr_residual, xentr_update)
 #include "comm_kernels.hpp"  // the binary committee machine slices (CommParams, comm_residual, comm_update, comm_init_rows)
 #include "sat_kernels.hpp"   // the K-SAT slices (SatTable, sat_delta, sat_row_energy, sat_init_rows)
+#include "pspin_kernels.hpp" // GraphPSpin3 as the g of a field wrapper (PspinTable, pspin_delta, pspin_energy, pspin_init_row)
 
 namespace rrrmc {
 
@@ -30,7 +31,8 @@ enum ReSlice { RE_EMPTY = 0, RE_SK = 1, RE_SKN = 2,          // GraphEmpty (Grap
                RE_CQU = 9,                                   // GraphCommQu (GraphCommQuRE)
                RE_PXE = 11,                                  // GraphPercXEntr: the g of GraphAddFields / GraphAddSubFields only (af_kernels.hpp); 10 is unassigned
                RE_SPF = 12,                                  // GraphEANormal / GraphRRGNormal: sparse Float64 couplings (GraphEARE, GraphEALE, GraphEATLE)
-               RE_MIXED = 13 };                              // GraphMixed: the g of the field wrappers over a mix only (mixed_kernels.hpp)
+               RE_MIXED = 13,                                // GraphMixed: the g of the field wrappers over a mix only (mixed_kernels.hpp)
+               RE_PSPIN3 = 14 };                             // GraphPSpin3: the g of the field wrappers made by rrrmc_ctx_create_pspin3 only (pspin_kernels.hpp)
 template <int SLICE> constexpr bool kPercSlice = SLICE == RE_PSTEP || SLICE == RE_PLIN;
 template <int SLICE> constexpr bool kCommSlice = SLICE == RE_CSTEP || SLICE == RE_CRELU || SLICE == RE_CQU;
 // slices whose state is a pure function of the configuration, updated once per accepted move by the whole wavefront in the LDS builds
@@ -46,6 +48,7 @@ struct ReParams {
     XentrParams xe;                                         // GraphPercXEntr (with pc): the loss table, the global build's term buffer
     CommParams cm;                                          // committee machine slices: the same for GraphCommStep / GraphCommReLU / GraphCommQu
     SatTable sat;                                           // K-SAT slices: the shared occurrence program (no per-slice state)
+    PspinTable ps3;                                         // GraphPSpin3 under a field wrapper: the partner table (no per-chain state)
     double* slf;                                            // [R][2][M][Nk]  every slice's lfields / lfields_last (SK.jl:212-276)
     int32_t* smv;                                           // [R][M]         move_last of every slice (-1 = none)
     uint8_t* scur;                                          // [R][M]         which of the two arrays is `lfields`
@@ -199,11 +202,24 @@ __device__ __forceinline__ void re_slice_update(const RrrView&, const SatTable&,
 {
     static_assert(SLICE == RE_SAT, "a SatTable goes with a K-SAT slice");
 }
+// ... and with GraphPSpin3 (pspin_kernels.hpp), M = 1: delta_energy from the spins, no update_cache!
+template <int SLICE, bool WAVE = false>
+__device__ __forceinline__ double re_residual(const RrrView& v, const PspinTable& pt, int x, int /*k*/, int i)
+{
+    static_assert(SLICE == RE_PSPIN3, "a PspinTable goes with GraphPSpin3");
+    return (double)pspin_delta(pt, i, PspinRowBits{v.sp, x - i});
+}
+template <int SLICE, bool WAVE>
+__device__ __forceinline__ void re_slice_update(const RrrView&, const PspinTable&, int, int, int)
+{
+    static_assert(SLICE == RE_PSPIN3, "a PspinTable goes with GraphPSpin3");
+}
 // the view of one chain's slice state that the kernels pass to the two above
 template <int SLICE, class PP>
 __device__ __forceinline__ auto re_slice_view(const PP& P, int r)
 {
     if constexpr (SLICE == RE_SAT) return P.sat;
+    else if constexpr (SLICE == RE_PSPIN3) return P.ps3;
     else if constexpr (SLICE == RE_PXE) return xentr_view(P.pc, P.xe, r);
     else if constexpr (kCommSlice<SLICE>) return comm_view<comm_kind_of_slice(SLICE)>(P.cm, r);
     else return perc_view(P.pc, r);
@@ -297,6 +313,8 @@ __device__ inline double re_slice_energy(const ReParams& P, const RrrView& v, in
         return (double)sat_row_energy(P.sat, v.sp, k * Nk);
     } else if constexpr (SLICE == RE_PXE) {
         return xentr_row_energy(P.pc, P.xe, v.sp, P.N);
+    } else if constexpr (SLICE == RE_PSPIN3) {
+        return (double)pspin_energy(P.ps3, PspinRowBits{v.sp, k * Nk});
     } else {
         return 0.0;
     }

@@ -45,6 +45,7 @@ typedef hipError_t dev_err_t;
 #include "comm_kernels.hpp"
 #include "quant_pat_kernels.hpp"
 #include "sat_kernels.hpp"
+#include "pspin_kernels.hpp"
 #include "re_kernels.hpp"
 #include "le_kernels.hpp"
 #include "tle_kernels.hpp"
@@ -357,6 +358,11 @@ struct rrrmc_ctx {
     uint32_t* sat_spT = nullptr;   // [qW][R] the thread build's transposed spins (allocated on first use)
     int64_t sat_Mc = 0, sat_maxconn = 0;
     int sat_build = 0;             // the build of the last standardMC call: 1 thread per replica, 2 wavefront per replica
+    // ---- the regular 3-spin model (RRRMC_MODEL_PSPIN3, and the g of the field wrappers over it; host_pspin.hpp): spins in q_spins, E in
+    //      sk_E, counts in q_stats; no per-chain cache.  K is the context's K; the wrappers' buffers are af_* above ----
+    uint16_t* ps_A = nullptr;      // [N][2K] the partner table (pspin_core.hpp)
+    uint32_t* ps_spT = nullptr;    // [qW][R] the thread build's transposed spins (allocated on first use)
+    int ps_build = 0;              // the build of the last standardMC call: 1 thread per chain, 2 wavefront per chain
 
     // ---- fast standardMC on RRRMC_MODEL_SPARSE_F64 (spf_fast_kernels.hpp; allocated on first use) ----
     std::vector<double> h_Jf;           // host copy of the couplings (threshold tables per beta)
@@ -592,7 +598,8 @@ inline int32_t mixed_uploaded(rrrmc_ctx* ctx, int32_t rc, int bit)
 inline bool chunk_layout(const rrrmc_ctx* ctx) { return is_mixed(ctx) || ctx->model == RRRMC_MODEL_QUANT_RRG || ctx->model == RRRMC_MODEL_SPARSE_DISCRETIZED || ctx->model == RRRMC_MODEL_SPARSE_LEVELS ||
                                                        ctx->model == RRRMC_MODEL_PERC_STEP || ctx->model == RRRMC_MODEL_PERC_LINEAR || ctx->model == RRRMC_MODEL_PERC_XENTR ||
                                                        ctx->model == RRRMC_MODEL_COMM_STEP || ctx->model == RRRMC_MODEL_COMM_RELU || ctx->model == RRRMC_MODEL_COMM_QU ||
-                                                       ctx->model == RRRMC_MODEL_SAT || ens_family(ctx->model) != ENS_NONE || af_family(ctx->model) != AF_NONE; }
+                                                       ctx->model == RRRMC_MODEL_SAT || ens_family(ctx->model) != ENS_NONE || af_family(ctx->model) != AF_NONE ||
+                                                       pspin_wrap(ctx->model) >= 0; }
 inline bool sparse_int_model(const rrrmc_ctx* ctx) { return ctx->model == RRRMC_MODEL_SPARSE_PM1 || ctx->model == RRRMC_MODEL_SPARSE_LEVELS; }
 inline double lv_to_f64(const rrrmc_ctx* ctx, long long units) { return (double)(units * ctx->lv_mul) / ctx->lv_div; }
 
@@ -747,6 +754,7 @@ inline void smp_commit(rrrmc_ctx* ctx, int kind, int64_t n) { ctx->smp_kind = ki
 #include "host_comm.hpp"
 #include "host_quant_pat.hpp"
 #include "host_sat.hpp"
+#include "host_pspin.hpp"
 #include "host_ens.hpp"
 #include "host_re.hpp"
 #include "host_le.hpp"
@@ -1374,6 +1382,7 @@ int32_t rrrmc_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int6
     if (is_xentr(ctx)) return xentr_mc_async(ctx, beta, iters, step);
     if (is_comm(ctx)) return comm_mc_async(ctx, beta, iters, step);
     if (is_sat(ctx)) return sat_mc_async(ctx, beta, iters, step);
+    if (is_pspin(ctx)) return pspin_mc_async(ctx, beta, iters, step);
     if (is_af(ctx)) return af_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (is_re(ctx)) return re_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
     if (is_tle(ctx)) return tle_mc_async(ctx, true, beta, iters, step, 0.0, 0.0);
@@ -1413,8 +1422,8 @@ int32_t rrrmc_set_debug_checks(rrrmc_ctx* ctx, int32_t on)
 {
     RRRMC_MULTI(ctx, false, rrrmc_set_debug_checks(c, on));
     if (!ctx) return RRRMC_ERR_INVALID_ARG;
-    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_tle(ctx) && !is_af(ctx) && !is_perc(ctx) && !is_xentr(ctx) && !is_comm(ctx) && !quant_pat(ctx) && !is_sat(ctx))
-        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy, the GraphTopologicalLocalEntropy, GraphAddFields / GraphAddSubFields, the perceptron, the committee machine and the K-SAT graphs, and GraphQuant over perceptrons and committee machines");
+    if (ctx->model != RRRMC_MODEL_SPARSE_PM1 && ctx->model != RRRMC_MODEL_SK_NORMAL && ctx->model != RRRMC_MODEL_SPARSE_F64 && !is_re(ctx) && !is_le(ctx) && !is_tle(ctx) && !is_af(ctx) && !is_perc(ctx) && !is_xentr(ctx) && !is_comm(ctx) && !quant_pat(ctx) && !is_sat(ctx) && !is_pspin(ctx))
+        return fail(ctx, RRRMC_ERR_UNSUPPORTED, "the debug checks are wired for RRRMC_MODEL_SPARSE_PM1, RRRMC_MODEL_SK_NORMAL, RRRMC_MODEL_SPARSE_F64, the GraphRobustEnsemble, the GraphLocalEntropy, the GraphTopologicalLocalEntropy, GraphAddFields / GraphAddSubFields, the perceptron, the committee machine, the K-SAT and the 3-spin graphs, and GraphQuant over perceptrons and committee machines");
     ctx->debug_checks = on != 0;
     return RRRMC_OK;
 }
@@ -1988,6 +1997,40 @@ int32_t rrrmc_gen_ksat(int64_t N, int64_t K, double alpha, uint64_t seed, int64_
     return RRRMC_OK;
 }
 
+// ---- the regular 3-spin model: exported entry points (host_pspin.hpp) ----
+int32_t rrrmc_ctx_create_pspin3(rrrmc_ctx** out, int64_t N, int64_t K, int32_t wrap, int64_t R, int32_t device, uint32_t replica0)
+{
+    return pspin_ctx_create(out, N, K, wrap, R, device, replica0);
+}
+
+int32_t rrrmc_set_pspin3(rrrmc_ctx* ctx, const int32_t* A)
+{
+    RRRMC_MULTI(ctx, false, rrrmc_set_pspin3(c, A));
+    smp_drop(ctx);
+    if (!ctx) return RRRMC_ERR_INVALID_ARG;
+    if (pspin_wrap(ctx->model) < 0) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_set_pspin3 is for contexts made by rrrmc_ctx_create_pspin3");
+    return pspin_set_table(ctx, A);
+}
+
+int32_t rrrmc_pspin_build(rrrmc_ctx* ctx, int32_t* build_out)
+{
+    if (!ctx || !build_out) return RRRMC_ERR_INVALID_ARG;
+    if (is_multi(ctx)) return rrrmc_pspin_build(ctx->kids[0], build_out);
+    if (!is_pspin(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_pspin_build is for contexts made by rrrmc_ctx_create_pspin3 with wrap 0");
+    *build_out = ctx->ps_build;
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_gen_pspin3(int64_t N, int64_t K, uint64_t seed, int32_t* A_out)
+{
+    if (!A_out) return fail(nullptr, RRRMC_ERR_INVALID_ARG, "A_out is NULL");
+    char msg[256];
+    const int rcs = pspin_check_size(N, K, msg, sizeof msg);
+    if (rcs) return fail(nullptr, rcs == 3 ? RRRMC_ERR_UNSUPPORTED : RRRMC_ERR_INVALID_ARG, "%s", msg);
+    pspin_generate(N, K, seed, A_out);
+    return RRRMC_OK;
+}
+
 // ---- GraphLocalEntropy: exported entry points (host_le.hpp) ----------------------------------------------------------------------
 int32_t rrrmc_ctx_create_le(rrrmc_ctx** out, int64_t Nk, int64_t M, int32_t slice_kind, int64_t R, int32_t device, uint32_t replica0)
 {
@@ -2254,6 +2297,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     const bool quant = model == RRRMC_MODEL_QUANT_RRG || model == RRRMC_MODEL_QUANT_SK || model == RRRMC_MODEL_QUANT_SKN || model == RRRMC_MODEL_QUANT_F64 || qpat;
     const bool re = ens_family(model) == ENS_RE, le = ens_family(model) == ENS_LE, tle = ens_family(model) == ENS_TLE;
     const bool sat = model == RRRMC_MODEL_SAT;
+    const bool ps3 = pspin_wrap(model) >= 0;
     const bool af = af_family(model) != AF_NONE;
     const bool pc = model == RRRMC_MODEL_PERC_STEP || model == RRRMC_MODEL_PERC_LINEAR;
     const bool xe = model == RRRMC_MODEL_PERC_XENTR;
@@ -2265,7 +2309,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
     ctx->model = quant ? RRRMC_MODEL_QUANT_RRG : model; ctx->K = K; ctx->R = R; ctx->replica0 = replica0; ctx->device = device_ids[0];
     ctx->N = quant || re ? N * M : le || tle ? N * (M + 1) : N;
     if (re || le || tle) { ctx->qNk = N; ctx->qM = M; }
-    if (pc || xe || sat) { ctx->qNk = N; ctx->qM = 1; }
+    if (pc || xe || sat || ps3) { ctx->qNk = N; ctx->qM = 1; }
     if (cm) { ctx->qNk = N; ctx->qM = 1; ctx->cm_K2 = K; ctx->K = 0; }
     if (af) { ctx->qNk = N; ctx->qM = 1; ctx->K = 0; }
     if (quant) { ctx->qNk = N; ctx->qM = M; ctx->q_sk = model == RRRMC_MODEL_QUANT_SK; ctx->q_skn = model == RRRMC_MODEL_QUANT_SKN; ctx->q_spf = model == RRRMC_MODEL_QUANT_F64; ctx->q_pat = qpat; }
@@ -2290,6 +2334,7 @@ int32_t rrrmc_ctx_create_multi(rrrmc_ctx** out, int32_t model, int64_t N, int64_
                            : xe ? rrrmc_ctx_create_perc_xentr(&c, N, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : pc ? rrrmc_ctx_create_perc(&c, N, model == RRRMC_MODEL_PERC_LINEAR, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : sat ? rrrmc_ctx_create_sat(&c, N, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
+                           : ps3 ? rrrmc_ctx_create_pspin3(&c, N, K, pspin_wrap(model), b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : model == RRRMC_MODEL_COMM_QU ? rrrmc_ctx_create_comm_qu(&c, N / K, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                            : cm ? rrrmc_ctx_create_comm(&c, N / K, K, model == RRRMC_MODEL_COMM_RELU, b1 - b0, device_ids[d], replica0 + (uint32_t)b0)
                                                             : rrrmc_ctx_create(&c, model, N, K, b1 - b0, device_ids[d], replica0 + (uint32_t)b0);
@@ -2490,6 +2535,7 @@ int32_t rrrmc_rrr_mc_async(rrrmc_ctx* ctx, double beta, double fourK, int64_t it
     if (ctx->model == RRRMC_MODEL_SPARSE_F64) return spf_cont_async(ctx, 0, beta, iters, step, 1.0, staged_thr, staged_thr_fact);
     if (is_perc(ctx) || is_xentr(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone perceptron graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone committee machine graphs (DeltaECacheCont over AllButOne neighbourhoods): standardMC is");
+    if (is_pspin(ctx)) return pspin_not_wired(ctx, "rrrMC");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "rrrMC is not wired for the stand-alone GraphSAT (a DeltaECache of max_conn + 1 levels over variable-degree neighbourhoods): standardMC is, and rrrMC on GraphSATRE / GraphSATLE");
     if (is_af(ctx)) return af_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
     if (is_re(ctx)) return re_mc_async(ctx, false, beta, iters, step, staged_thr, staged_thr_fact);
@@ -2508,6 +2554,7 @@ int32_t rrrmc_bkl_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_t s
     if (rc) return rc;
     if (is_perc(ctx) || is_xentr(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone committee machine graphs (standardMC is)");
+    if (is_pspin(ctx)) return pspin_not_wired(ctx, "bklMC");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "bklMC is not wired for the stand-alone GraphSAT (standardMC is)");
     if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "bklMC");
     if (is_af(ctx)) return af_not_wired(ctx, "bklMC");
@@ -2551,6 +2598,7 @@ int32_t rrrmc_wtm_mc_async(rrrmc_ctx* ctx, double beta, int64_t samples, double 
     if (rc) return rc;
     if (is_perc(ctx) || is_xentr(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone committee machine graphs (standardMC is)");
+    if (is_pspin(ctx)) return pspin_not_wired(ctx, "wtmMC");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "wtmMC is not wired for the stand-alone GraphSAT (standardMC is)");
     if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "wtmMC");
     if (is_af(ctx)) return af_not_wired(ctx, "wtmMC");
@@ -2582,6 +2630,7 @@ int32_t rrrmc_extremal_opt_async(rrrmc_ctx* ctx, const double* ftau, int64_t ite
     if (rc) return rc;
     if (is_perc(ctx) || is_xentr(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone perceptron graphs (standardMC is)");
     if (is_comm(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone committee machine graphs (standardMC is)");
+    if (is_pspin(ctx)) return pspin_not_wired(ctx, "extremal_opt");
     if (is_sat(ctx)) return fail(ctx, RRRMC_ERR_UNSUPPORTED, "extremal_opt is not wired for the stand-alone GraphSAT (standardMC is)");
     if (ens_family(ctx->model) != ENS_NONE) return ens_not_wired(ctx, "extremal_opt");
     if (is_af(ctx)) return af_not_wired(ctx, "extremal_opt");
@@ -2755,6 +2804,9 @@ int32_t rrrmc_energy_f64(rrrmc_ctx* ctx, double* E_out)
     } else if (is_sat(ctx)) {
         ctx->std_cache_live = false;
         rc = sat_run_init(ctx);
+    } else if (is_pspin(ctx)) {
+        ctx->std_cache_live = false;
+        rc = pspin_run_init(ctx);
     } else if (is_af(ctx)) {
         if (!ctx->af_fields_set) return af_needs_fields(ctx);
         ctx->std_cache_live = false;

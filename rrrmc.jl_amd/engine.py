@@ -395,6 +395,13 @@ class Engine:
         check(lib().rrrmc_sat_build(self._ctx, C.byref(b)), self._ctx)
         return b.value
 
+    def pspin_build(self):
+        """The kernel build the last standardMC call on a stand-alone GraphPSpin3 ran: 0 = none yet, 1 = one thread per chain, 2 = one
+        wavefront per chain."""
+        b = C.c_int32(-1)
+        check(lib().rrrmc_pspin_build(self._ctx, C.byref(b)), self._ctx)
+        return b.value
+
     def spf_team_build(self):
         """(waves, width, slots) of the spf_team_kernel build the default standardMC of a GraphRRGNormal / GraphEANormal launches here;
         zeros when the one-wavefront kernel runs instead."""

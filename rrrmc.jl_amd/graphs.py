@@ -510,6 +510,7 @@ class GraphQuant(_DeviceGraph):
             raise ValueError("M must be greater than 2, given: %d" % M)          # QT.jl:47
         if Gamma < 0:
             raise ValueError("Γ must be >= 0")                                   # QT.jl:164
+        _refuse_pspin3(X1, "GraphQuant")
         self.X1, self.M, self.Gamma, self.beta = X1, int(M), float(Gamma), float(beta)
         self.sk_slices = isinstance(X1, GraphSK)
         self.skn_slices = isinstance(X1, GraphSKNormal)                    # GraphQSKNormalT (QAliases.jl:45-46; test/runtests.jl:80)
@@ -919,7 +920,71 @@ class GraphSAT(_DeviceGraph):
                 f.write("".join("%d " % ((2 * j - 1) * (i + 1)) for j, i in zip(Ja, Aa)) + "0\n")
 
 
+class GraphPSpin3(_DeviceGraph):
+    """``GraphPSpin3(N, K)`` (src/graphs/PSpin3.jl:14-53): the regular 3-spin model.  ``N`` spins, ``N`` divisible by 3; each of the ``K``
+    layers is a partition of the sites into ``N / 3`` triples, all couplings +1; energy = −Σ_triples σσσ.  ``ET = Int``.  ``A[i]`` holds
+    ``2K`` 0-based site ids: ``A[i][2k]``, ``A[i][2k + 1]`` are the two partners of ``i`` in layer ``k``, in the triple's own order
+    (PSpin3.jl:32-43).  The reference draws the layers with an unpinned ``randperm``: here ``seed`` names them (``rrrmc_gen_pspin3``, host
+    only), and ``from_triples(N, layers)`` takes explicit partitions.  ``standardMC`` runs on the graph, ``rrrMC`` on ``GraphAddFields`` /
+    ``GraphAddSubFields`` over it."""
+    model_kind = 105        # RRRMC_MODEL_PSPIN3
+    energy_dtype = np.int64
+    _staged_thr = 0.5
+
+    def _create(self, ctx, R, device, replica0, wrap=0):
+        check(lib().rrrmc_ctx_create_pspin3(ctx, self.N, self.K, wrap, R, device, replica0))
+
+    def _upload_couplings(self, ctx):
+        check(lib().rrrmc_set_pspin3(ctx, self.A.reshape(-1)), ctx)
+
+    def __init__(self, N, K, seed=DEFAULT_SEED):
+        N, K = int(N), int(K)
+        if K < 1:
+            raise ValueError("K must be >= 1, given: %d" % K)                                     # PSpin3.jl:22
+        if N < 3 or N % 3 != 0:
+            raise ValueError("N must be divisible by 3, given: %d" % N)                           # PSpin3.jl:24
+        A = np.zeros((N, 2 * K), np.int32)
+        check(lib().rrrmc_gen_pspin3(N, K, seed, A.reshape(-1)))
+        self.N, self.K, self.A = N, K, A
+
+    @classmethod
+    def from_triples(cls, N, layers):
+        """the graph of explicit layers: ``layers[k]`` lists the ``N / 3`` triples ``(v1, v2, v3)`` (0-based) of layer ``k``, which must
+        partition the sites; a layer may repeat"""
+        N = int(N)
+        if N < 3 or N % 3 != 0:
+            raise ValueError("N must be divisible by 3, given: %d" % N)
+        K = len(layers)
+        if K < 1:
+            raise ValueError("K must be >= 1, given: %d" % K)
+        A = np.zeros((N, 2 * K), np.int32)
+        for k, layer in enumerate(layers):
+            tr = np.asarray(layer, np.int64)
+            if tr.shape != (N // 3, 3):
+                raise ValueError("layer %d: expected %d triples of 3 sites, given an array of shape %r" % (k, N // 3, tr.shape))
+            if tr.min() < 0 or tr.max() >= N:
+                raise ValueError("layer %d: a site is out of range (N = %d)" % (k, N))
+            if len(np.unique(tr)) != N:
+                raise ValueError("layer %d is not a partition of the sites: a site appears twice" % k)
+            for v1, v2, v3 in tr.tolist():                                                        # PSpin3.jl:35-41
+                A[v1, 2 * k], A[v1, 2 * k + 1] = v2, v3
+                A[v2, 2 * k], A[v2, 2 * k + 1] = v1, v3
+                A[v3, 2 * k], A[v3, 2 * k + 1] = v1, v2
+        X = cls.__new__(cls)
+        X.N, X.K, X.A = N, K, A
+        return X
+
+
+def _refuse_pspin3(g, what):
+    """GraphPSpin3 runs stand-alone and under the field wrappers only"""
+    if isinstance(g, GraphPSpin3):
+        raise TypeError("%s: a GraphPSpin3 is not wired here: it runs stand-alone under standardMC, and under rrrMC as the g of "
+                        "GraphAddFields / GraphAddSubFields" % what)
+
+
 def _ensemble_slice_kind(slice_graph):
+    if isinstance(slice_graph, GraphPSpin3):
+        return 14           # RRRMC_RE_SLICE_PSPIN3 (the g of the field wrappers only)
     if isinstance(slice_graph, GraphSAT):
         return 8            # RRRMC_RE_SLICE_SAT (7 is unassigned)
     if isinstance(slice_graph, GraphCommQu):
@@ -1157,6 +1222,7 @@ class GraphMixed(_DeviceGraph):
             raise NotImplementedError("GraphMixed: %d components: the mixed kernels cover <= 7" % len(graphs))
         comps = []
         for g in graphs:
+            _refuse_pspin3(g, "GraphMixed")
             if isinstance(g, GraphMixed):
                 raise TypeError("GraphMixed: a component is a GraphMixed: a mix does not nest (list its components instead)")
             if isinstance(g, _SparseLevelsGraph):
@@ -1213,20 +1279,20 @@ class GraphAddFields(_DeviceGraph):
     graph ``GraphAF(fields)`` has energy Σ_i h_i σ_i, delta_energy −2 σ_i h_i and no neighbours, and whose residual is ``g``'s own
     delta_energy, so that ``rrrMC`` handles the fields through its DynamicSampler at O(log N) per move whatever ``g`` is.  ``g`` is ``None``
     (GraphEmpty), a ``GraphSK``, ``GraphSKNormal``, ``GraphPercStep``, ``GraphPercLinear``, ``GraphCommStep``, ``GraphCommReLU``,
-    ``GraphCommQu``, ``GraphSAT`` or ``GraphPercXEntr`` with ``len(fields)`` spins.  ``ET = Float64``: integer energies of ``g`` enter as
-    exact Float64s."""
+    ``GraphCommQu``, ``GraphSAT``, ``GraphPercXEntr`` or ``GraphPSpin3`` with ``len(fields)`` spins.  ``ET = Float64``: integer energies of
+    ``g`` enter as exact Float64s."""
     energy_dtype = np.float64
     K = 0
     _sub = 0
     _engine = None          # step_energy over a perceptron reads the live engine
 
     def _create(self, ctx, R, device, replica0):
-        if isinstance(self.X1, GraphMixed):
+        if isinstance(self.X1, (GraphMixed, GraphPSpin3)):
             return self.X1._create(ctx, R, device, replica0, wrap=1 + self._sub)
         check(lib().rrrmc_ctx_create_af(ctx, self.slice_kind, self._sub, self.N, self.K2, R, device, replica0))
 
     def _multi_args(self):
-        return self.model_kind, self.N, self.K2, 0
+        return self.model_kind, self.N, (self.X1.K if isinstance(self.X1, GraphPSpin3) else self.K2), 0
 
     def _create_multi(self, ctx, R, ids, replica0):
         if isinstance(self.X1, GraphMixed):
@@ -1242,9 +1308,9 @@ class GraphAddFields(_DeviceGraph):
         fields = np.ascontiguousarray(fields, np.float64)
         if fields.ndim != 1 or len(fields) < 1:
             raise ValueError("fields must be a non-empty vector")
-        if g is not None and not isinstance(g, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT, GraphPercXEntr, GraphMixed)):
+        if g is not None and not isinstance(g, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT, GraphPercXEntr, GraphMixed, GraphPSpin3)):
             raise TypeError("%s wraps GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, GraphCommStep, GraphCommReLU, "
-                            "GraphCommQu, GraphSAT, GraphPercXEntr or a GraphMixed of them; sparse graphs (GraphRRG*, GraphEA*), GraphQuant and the ensembles are not wired as g, "
+                            "GraphCommQu, GraphSAT, GraphPercXEntr, GraphPSpin3 or a GraphMixed of them; sparse graphs (GraphRRG*, GraphEA*), GraphQuant and the ensembles are not wired as g, "
                             "given a %s" % (type(self).__name__, type(g).__name__))
         if g is not None and g.N != len(fields):
             raise ValueError("incompatible length, fields size=%d graph size=%d" % (len(fields), g.N))       # AddFields.jl:65
@@ -1257,7 +1323,9 @@ class GraphAddFields(_DeviceGraph):
             return
         self.slice_kind = _ensemble_slice_kind(g)
         self.K2 = int(getattr(g, "K2", 0)) if isinstance(g, _GraphComm) else 0
-        if self.slice_kind == 11:
+        if self.slice_kind == 14:
+            self.model_kind = 107 if self._sub else 106                                                       # RRRMC_MODEL_PSPIN3_ASF / _AF
+        elif self.slice_kind == 11:
             self.model_kind = 101 if self._sub else 100                                                       # RRRMC_MODEL_XENTR_ASF / _AF
         else:
             self.model_kind = (57 if self._sub else 48) + (0, 1, 2, 3, 4, 5, 6, None, 7, 8)[self.slice_kind]  # RRRMC_MODEL_AF_* / RRRMC_MODEL_ASF_*
@@ -1297,6 +1365,7 @@ class GraphRobustEnsemble(_DeviceGraph):
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
             raise ValueError("M must be greater than 2, given: %d" % M)                  # RE.jl:37
+        _refuse_pspin3(slice_graph, "GraphRobustEnsemble")
         if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT, _SparseF64Graph)):
             raise TypeError("the slices of a GraphRobustEnsemble are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, "
                             "GraphCommStep, GraphCommReLU, GraphCommQu, GraphSAT, GraphEANormal or GraphRRGNormal")
@@ -1368,6 +1437,7 @@ class GraphLocalEntropy(_DeviceGraph):
     def __init__(self, Nk, M, gamma, beta, slice_graph=None):
         if M <= 2:
             raise ValueError("M must be greater than 2, given: %d" % M)                  # LE.jl:24
+        _refuse_pspin3(slice_graph, "GraphLocalEntropy")
         if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, _GraphPerc, _GraphComm, GraphSAT, _SparseF64Graph)):
             raise TypeError("the slices of a GraphLocalEntropy are GraphEmpty (None), GraphSK, GraphSKNormal, GraphPercStep, GraphPercLinear, "
                             "GraphCommStep, GraphCommReLU, GraphCommQu, GraphSAT, GraphEANormal or GraphRRGNormal")
@@ -1452,6 +1522,7 @@ class GraphTopologicalLocalEntropy(_DeviceGraph):
         check(lib().rrrmc_tle_set_params(ctx, self.gamma, self.lam, self.beta), ctx)
 
     def __init__(self, Nk, M, gamma, lam, beta, slice_graph=None):
+        _refuse_pspin3(slice_graph, "GraphTopologicalLocalEntropy")
         if slice_graph is not None and not isinstance(slice_graph, (GraphSK, GraphSKNormal, GraphSAT, _SparseF64Graph)):
             raise TypeError("the slices of a GraphTopologicalLocalEntropy are GraphEmpty (None), GraphSK, GraphSKNormal, GraphSAT, GraphEANormal or GraphRRGNormal")
         if slice_graph is not None and slice_graph.N != int(Nk):
@@ -1612,6 +1683,9 @@ def getN(X):
 
 def neighbors(X, i):
     """src/Interface.jl:158; RRG.jl:261 (uA = neighbours with non-zero coupling), EA.jl:292 (de-duplicated)."""
+    if isinstance(X, GraphPSpin3):
+        a = X.A[i]
+        return a[np.sort(np.unique(a, return_index=True)[1])].astype(np.int64)                     # unique(A[i]), first occurrences in order: PSpin3.jl:47, :177
     if isinstance(X, GraphSAT):
         return np.asarray(X.neighb[i], np.int64)                                                  # SAT.jl:322
     if getattr(X, "model_kind", 0) == 7 and not X.ea_form:
@@ -1623,6 +1697,9 @@ def all_delta_e(X):
     """allΔE (src/Interface.jl:200-201): RRG.jl:262-281, EA.jl:293-309 — sorted values of |dE|."""
     if isinstance(X, GraphSAT):
         return tuple(range(X.max_conn + 1))                                                       # SAT.jl:325
+    if isinstance(X, GraphPSpin3):                                                                # PSpin3.jl:178-180
+        K = X.K
+        return tuple(4 * d for d in range(K // 2 + 1)) if K % 2 == 0 else tuple(2 * (2 * d + 1) for d in range((K + 1) // 2))
     K = X.K
     if getattr(X, "model_kind", 0) == 7:
         es = {0}

@@ -15,6 +15,8 @@
                                             and standardMC
   python tools/bench_models.py mixed [R ...] GraphMixed(GraphSK(1001), GraphPercStep(1001, 400), GraphSAT(1001, 3, 4.2)), β = 1: standardMC through
                                             the wave and the thread build, and rrrMC through GraphAddSubFields over it
+  python tools/bench_models.py pspin3 [R ...] GraphPSpin3(3000, 3) and GraphPSpin3(3000, 8), β = 1: standardMC through the wave and the thread build,
+                                            beside GraphSAT(3000, 3, 4.2) under the same call
 """
 import json
 import os
@@ -409,6 +411,8 @@ def _timed_legs(pkg, X, R, legs, envs, beta, it, step, seed, reps):
                      "acceptance": float(res[1].mean()) / it, "energy_per_spin": float(res[0][:, -1].mean()) / X.N}
         if not rrr and hasattr(X, "max_conn"):
             out[name]["build"] = eng.sat_build()
+        if not rrr and type(X).__name__ == "GraphPSpin3":
+            out[name]["build"] = eng.pspin_build()
         if not rrr and type(X).__name__ == "GraphPercXEntr":
             out[name]["build"] = eng.xentr_build()
         if type(X).__name__ == "GraphMixed" or type(getattr(X, "X1", None)).__name__ == "GraphMixed":
@@ -507,6 +511,25 @@ def bench_mixed(N=1001, P=400, K=3, alpha=4.2, beta=1.0, iters=1 << 14, step=1 <
         print(json.dumps(out), flush=True)
 
 
+def bench_pspin3(N=3000, Ks=(3, 8), alpha=4.2, beta=1.0, iters=1 << 16, step=1 << 12, seed=0x5EED, reps=3):
+    """GraphPSpin3(3000, 3) and GraphPSpin3(3000, 8) under standardMC at β = 1 through both builds (one wavefront per chain with 64 iterations
+    side by side, one thread per chain) and the build the library picks by itself, and GraphSAT(3000, 3, 4.2) through its two builds under the
+    same call as the yardstick.  Kernel iterations/s per chain count (profiles/r20/pspin3.md):
+    python tools/bench_models.py pspin3 8 32 128 512 2048 8192 16384 32768 65536"""
+    pkg = entry.load_package()
+    envs = ("RRRMC_PSPIN_NO_WAVE", "RRRMC_PSPIN_WAVE", "RRRMC_SAT_NO_WAVE", "RRRMC_SAT_WAVE")
+    models = [("GraphPSpin3", {"N": N, "K": K}, pkg.GraphPSpin3(N, K, seed=seed),
+               (("wave", {"RRRMC_PSPIN_WAVE": "1"}, False), ("thread", {"RRRMC_PSPIN_NO_WAVE": "1"}, False), ("default", {}, False))) for K in Ks]
+    models.append(("GraphSAT", {"N": N, "K": 3, "alpha": alpha}, pkg.GraphSAT(N, 3, alpha, seed=seed),
+                   (("wave", {"RRRMC_SAT_WAVE": "1"}, False), ("thread", {"RRRMC_SAT_NO_WAVE": "1"}, False))))
+    for R in ([int(a) for a in sys.argv[2:]] or [8, 32, 128, 512, 2048, 8192, 16384, 32768, 65536]):
+        it = max(step, iters * 2048 // max(R, 2048))
+        for model, par, X, legs in models:
+            out = {"model": model, **par, "beta": beta, "replicas": R, "iters": it}
+            out.update(_timed_legs(pkg, X, R, legs, envs, beta, it, step, seed, reps))
+            print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "sk"
-    {"mixed": bench_mixed, "eare": bench_eare, "sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm, "sat": bench_sat, "satre": bench_satre, "tle": bench_tle, "xentr": bench_xentr}[which]()
+    {"pspin3": bench_pspin3, "mixed": bench_mixed, "eare": bench_eare, "sk": bench_sk, "ea": bench_ea, "quant": bench_quant, "spf": bench_spf, "spf_fast": bench_spf_fast, "dbl": bench_dbl, "ea_random": bench_ea_random, "re": bench_re, "le": bench_le, "perc": bench_perc, "comm": bench_comm, "sat": bench_sat, "satre": bench_satre, "tle": bench_tle, "xentr": bench_xentr}[which]()
