@@ -867,6 +867,23 @@ RRRMC_API int32_t rrrmc_snapshot_reserve(rrrmc_ctx *ctx, int32_t nslots);
 RRRMC_API int32_t rrrmc_snapshot_store(rrrmc_ctx *ctx, int32_t slot);
 RRRMC_API int32_t rrrmc_snapshot_get(rrrmc_ctx *ctx, int32_t slot, uint64_t *chunks);
 RRRMC_API int32_t rrrmc_overlaps(rrrmc_ctx *ctx, int64_t npairs, const int32_t *slotA, const int32_t *slotB, int32_t *q_out);
+/* Overlaps between DIFFERENT replicas of the stored configurations: the order-parameter distribution P(q) of the R chains on one sample,
+ * and parsexovs / stats_overlaps (scripts/scripts.jl:407-457, :459-522) with two replicas as the two runs.  Every distinct slot a call
+ * names is brought once to R x ceil(N/64) BitVector chunks on the device; one tiled xor-popcount kernel serves all layouts.
+ *   rrrmc_cross_overlaps  q_out[(p * nA + i) * nB + j] = pm1dot(replica a0 + i of slotA[p], replica b0 + j of slotB[p]);
+ *                         slot -1 names the live configuration; 0 <= a0, nA >= 1, a0 + nA <= R, likewise b0, nB
+ *   rrrmc_overlap_hist    hist_out[d], d = 0..N: the number of counted replica pairs at Hamming distance d (q = N - 2d), summed over the
+ *                         npairs slot pairs; hist_out is overwritten, not accumulated.  A pair with slotA[p] == slotB[p] counts
+ *                         r1 < r2 (R(R-1)/2 pairs), one with different slots every r1 != r2 (R(R-1) pairs); r1 == r2, the two-time
+ *                         self overlap, is rrrmc_overlaps' and is never counted.  RRRMC_XOV_NO_LDS_HIST=1, read at the call, replaces
+ *                         the per-workgroup LDS histogram by one global atomic per pair
+ * Both serve every context rrrmc_snapshot_store serves (GraphQuant, the ensembles and the pattern machines with the whole N = Nk*M
+ * configuration), multi-device ones included (the packed rows are gathered on the first shard's device through the host), and neither
+ * disturbs a run.  npairs = 0 returns RRRMC_OK and writes nothing.  RRRMC_ERR_INVALID_ARG: npairs < 0, a NULL pointer with npairs > 0,
+ * an empty or out-of-range slot, rows outside the context, npairs > 65535, npairs * nA * nB > 2^26 (256 MiB of results). */
+RRRMC_API int32_t rrrmc_cross_overlaps(rrrmc_ctx *ctx, int64_t npairs, const int32_t *slotA, const int32_t *slotB, int64_t a0, int64_t nA,
+                                       int64_t b0, int64_t nB, int32_t *q_out);
+RRRMC_API int32_t rrrmc_overlap_hist(rrrmc_ctx *ctx, int64_t npairs, const int32_t *slotA, const int32_t *slotB, int64_t *hist_out);
 /* GraphQuant observables of the live configuration of every replica (RRRMC_MODEL_QUANT_RRG):
  *   Qenergy_out[R]   Qenergy(X, C)            (src/graphs/QT.jl:253-268)
  *   tmag_out[R]      transverse_mag(X0, C, beta) (QT.jl:113-122)

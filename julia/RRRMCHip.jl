@@ -1197,6 +1197,21 @@ function overlaps(ctx::Ctx, ia::Vector{Int32}, ib::Vector{Int32})
     GC.@preserve ia ib check(ccall((:rrrmc_overlaps, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), ctx.p, length(ia), ia, ib, q), ctx.p)
     return q
 end
+"q[j, i, p] = pm1dot(replica a0 + i of slot ia[p], replica b0 + j of slot ib[p]) between DIFFERENT replicas: 0-based slots and first rows, -1 = the live configuration; the C array [p][i][j] read column-major"
+function cross_overlaps(ctx::Ctx, ia::Vector{Int32}, ib::Vector{Int32}; a0::Integer = 0, nA::Integer = ctx.R, b0::Integer = 0, nB::Integer = ctx.R)
+    length(ia) == length(ib) || throw(ArgumentError("ia and ib must have the same length"))
+    q = Array{Int32}(undef, max(nB, 0), max(nA, 0), length(ia))
+    GC.@preserve ia ib check(ccall((:rrrmc_cross_overlaps, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Int32}, Int64, Int64, Int64, Int64, Ptr{Int32}),
+                                   ctx.p, length(ia), ia, ib, a0, nA, b0, nB, q), ctx.p)
+    return q
+end
+"h[d + 1], d = 0:N = the number of replica pairs at Hamming distance d (q = N - 2d) over the slot pairs: r1 < r2 where ia[p] == ib[p], every r1 != r2 otherwise"
+function overlap_hist(ctx::Ctx, ia::Vector{Int32}, ib::Vector{Int32})
+    length(ia) == length(ib) || throw(ArgumentError("ia and ib must have the same length"))
+    h = zeros(Int64, ctx.N + 1)
+    GC.@preserve ia ib check(ccall((:rrrmc_overlap_hist, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}), ctx.p, length(ia), ia, ib, h), ctx.p)
+    return h
+end
 
 # ---- cache views for parity checks against the reference's own objects ----------------------------------------------------------------
 "X.cache.lfields of every replica (N × R), recomputed from the current spins for the integer models (src/Common.jl:27-36)"

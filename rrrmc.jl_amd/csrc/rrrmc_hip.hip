@@ -34,6 +34,7 @@ typedef hipError_t dev_err_t;
 #include "bign_kernels.hpp"
 #include "obs_kernels.hpp"
 #include "layout_kernels.hpp"
+#include "xov_kernels.hpp"
 #include "spf_kernels.hpp"
 #include "spf_team_api.hpp"
 #include "spf_fast_kernels.hpp"
@@ -284,6 +285,15 @@ struct rrrmc_ctx {
     size_t pairs_cap = 0;
     int32_t* d_ovl = nullptr;      // [pairs_cap][Rpad]
     int32_t* d_qobs = nullptr;     // GraphQuant: e0[R], Eslice[R][M], ovs_raw[R][M/2]
+    // ---- cross-replica overlaps (host_xov.hpp): grown on demand, kept across calls ----
+    unsigned long long* xov_pk = nullptr;    // [distinct slots of a batch][R][ceil(N/64)] packed rows
+    size_t xov_pk_cap = 0;
+    uint8_t* xov_tab = nullptr;              // the batch's row pointers, then its pairs' two indices into them
+    size_t xov_tab_cap = 0;                  // bytes
+    int32_t* xov_q = nullptr;                // [pairs of a batch][nA][nB]
+    size_t xov_q_cap = 0;
+    unsigned long long* xov_hist = nullptr;  // [N + 1]
+    size_t xov_hist_cap = 0;
     // ---- GraphRobustEnsemble (ENS_RE of ens_models.hpp): spins in q_spins / qW (ABI site order), qNk / qM, slices in q_Jb (binary SK) or sk_J +
     //      q_slf / q_smv / q_scur (GraphSKNormal), the DeltaECache in q_cls / q_sv / q_spos / q_st / q_T / q_z, E in sk_E, counts in q_stats ----
     uint32_t* re_sp = nullptr;     // [R][qW] slice-major working copy of the spins
@@ -1262,6 +1272,21 @@ size_t native_spin_bytes(const rrrmc_ctx* ctx)
     return sizeof(uint32_t) * (size_t)ctx->G * (size_t)ctx->N;
 }
 
+// device buffer in one of the three replica-in-word layouts -> R x ceil(N/64) BitVector chunks on the device, enqueued on the ctx's stream
+// (the bits beyond N in a row's last chunk come out zero)
+int32_t pack_native(rrrmc_ctx* ctx, const void* src, unsigned long long* dst)
+{
+    const int64_t N = ctx->N, nch = (N + 63) / 64;
+    if (ctx->model == RRRMC_MODEL_SPARSE_F64)
+        hipLaunchKernelGGL(spins_pack_kernel<unsigned long long>, dim3((unsigned)nch, (unsigned)ctx->pfW), dim3(64), 0, ctx->stream, (const unsigned long long*)src, dst, (int)N, (int)nch, (int)ctx->R);
+    else if (ctx->model == RRRMC_MODEL_SK_NORMAL || ctx->model == RRRMC_MODEL_SK_BINARY)
+        hipLaunchKernelGGL(spins_pack_kernel<uint8_t>, dim3((unsigned)nch, (unsigned)ctx->G8), dim3(64), 0, ctx->stream, (const uint8_t*)src, dst, (int)N, (int)nch, (int)ctx->R);
+    else
+        hipLaunchKernelGGL(spins_pack_kernel<uint32_t>, dim3((unsigned)nch, (unsigned)ctx->G), dim3(64), 0, ctx->stream, (const uint32_t*)src, dst, (int)N, (int)nch, (int)ctx->R);
+    HIP_TRY(ctx, hipGetLastError());
+    return RRRMC_OK;
+}
+
 // device buffer in the model's native layout -> R x ceil(N/64) BitVector chunks on the host
 int32_t spins_to_chunks(rrrmc_ctx* ctx, const void* src, uint64_t* chunks)
 {
@@ -1274,13 +1299,7 @@ int32_t spins_to_chunks(rrrmc_ctx* ctx, const void* src, uint64_t* chunks)
     }
     const size_t cbytes = sizeof(uint64_t) * (size_t)ctx->R * (size_t)nch;
     { const int32_t rci = ensure_io(ctx, cbytes); if (rci) return rci; }
-    if (ctx->model == RRRMC_MODEL_SPARSE_F64)
-        hipLaunchKernelGGL(spins_pack_kernel<unsigned long long>, dim3((unsigned)nch, (unsigned)ctx->pfW), dim3(64), 0, ctx->stream, (const unsigned long long*)src, ctx->d_io, (int)N, (int)nch, (int)ctx->R);
-    else if (ctx->model == RRRMC_MODEL_SK_NORMAL || ctx->model == RRRMC_MODEL_SK_BINARY)
-        hipLaunchKernelGGL(spins_pack_kernel<uint8_t>, dim3((unsigned)nch, (unsigned)ctx->G8), dim3(64), 0, ctx->stream, (const uint8_t*)src, ctx->d_io, (int)N, (int)nch, (int)ctx->R);
-    else
-        hipLaunchKernelGGL(spins_pack_kernel<uint32_t>, dim3((unsigned)nch, (unsigned)ctx->G), dim3(64), 0, ctx->stream, (const uint32_t*)src, ctx->d_io, (int)N, (int)nch, (int)ctx->R);
-    HIP_TRY(ctx, hipGetLastError());
+    { const int32_t rcp = pack_native(ctx, src, ctx->d_io); if (rcp) return rcp; }
     HIP_TRY(ctx, hipMemcpyAsync(chunks, ctx->d_io, cbytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RRRMC_OK;
@@ -3039,6 +3058,19 @@ int32_t rrrmc_overlaps(rrrmc_ctx* ctx, int64_t npairs, const int32_t* slotA, con
     for (int64_t p = 0; p < npairs; ++p)
         std::memcpy(q_out + p * ctx->R, h.data() + p * ctx->Rpad, sizeof(int32_t) * (size_t)ctx->R);
     return RRRMC_OK;
+}
+
+#include "host_xov.hpp"
+
+int32_t rrrmc_cross_overlaps(rrrmc_ctx* ctx, int64_t npairs, const int32_t* slotA, const int32_t* slotB, int64_t a0, int64_t nA, int64_t b0, int64_t nB,
+                             int32_t* q_out)
+{
+    return xov_call(ctx, false, npairs, slotA, slotB, a0, nA, b0, nB, q_out, nullptr);
+}
+
+int32_t rrrmc_overlap_hist(rrrmc_ctx* ctx, int64_t npairs, const int32_t* slotA, const int32_t* slotB, int64_t* hist_out)
+{
+    return xov_call(ctx, true, npairs, slotA, slotB, 0, 0, 0, 0, nullptr, hist_out);
 }
 
 int32_t rrrmc_quant_observables(rrrmc_ctx* ctx, double beta, double Gamma, double* Qenergy_out, double* tmag_out, double* ovs_out)

@@ -349,6 +349,32 @@ class Engine:
         check(lib().rrrmc_overlaps(self._ctx, a.size, a, b, q.reshape(-1)), self._ctx)
         return q
 
+    @staticmethod
+    def _slot_pairs(slotA, slotB):
+        a = np.ascontiguousarray(np.atleast_1d(slotA), np.int32)
+        b = np.ascontiguousarray(np.atleast_1d(slotB), np.int32)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError("slotA and slotB must have the same length")
+        return a, b
+
+    def cross_overlaps(self, slotA, slotB, rowsA=None, rowsB=None):
+        """q[p, i, j] = pm1dot(replica a0 + i of slotA[p], replica b0 + j of slotB[p]) between DIFFERENT replicas; slot -1 = live.
+        ``rowsA`` / ``rowsB``: ``(start, count)``, all replicas by default.  Scalars name one pair.  Read-only with respect to a run."""
+        a, b = self._slot_pairs(slotA, slotB)
+        a0, nA = (0, self.R) if rowsA is None else (int(rowsA[0]), int(rowsA[1]))
+        b0, nB = (0, self.R) if rowsB is None else (int(rowsB[0]), int(rowsB[1]))
+        q = np.zeros((a.size, max(nA, 0), max(nB, 0)), np.int32)
+        check(lib().rrrmc_cross_overlaps(self._ctx, a.size, a, b, a0, nA, b0, nB, q.reshape(-1)), self._ctx)
+        return q
+
+    def overlap_hist(self, slotA, slotB):
+        """h[d], d = 0..N: the number of replica pairs at Hamming distance d (q = N - 2d) over the given slot pairs — r1 < r2 for a pair
+        of one slot with itself, every r1 != r2 for two different slots.  ``overlap_moments`` turns it into <q^2>, <q^4> and the Binder ratio."""
+        a, b = self._slot_pairs(slotA, slotB)
+        h = np.zeros(self.X.N + 1, np.int64)
+        check(lib().rrrmc_overlap_hist(self._ctx, a.size, a, b, h), self._ctx)
+        return h
+
     def quant_observables(self, beta=None, Gamma=None):
         """(Qenergy[R], transverse_mag[R], overlaps[R, M // 2]) of a GraphQuant (src/graphs/QT.jl:113-122, 213-268)."""
         X = self.X

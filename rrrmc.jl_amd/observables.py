@@ -150,3 +150,62 @@ def parseovs(engine, tsm, lr, nsamples=None):
         sq2s.append(np.sqrt(np.maximum(0.0, mq4 - mq2 ** 2)))
     R = engine.R
     return (np.array(mq2s).reshape(-1, R), np.array(sq2s).reshape(-1, R))
+
+
+def parsexovs(engine, ts1, ts2, lr, r1, r2, nsamples=None):
+    """``parsexovs`` (scripts/scripts.jl:407-457) with replica ``r1`` of the batch as the first run and replica ``r2`` as the second:
+    <x^2> and its spread of the cross overlap x = pm1dot(s1[k1], s2[k2]) / N over the windows [t, 2t) of ``lr`` on each run's own clock,
+    from the device snapshots 0..nsamples-1.  Returns (mx2s, sx2s), one float per window as the reference does (NaN from 0/0 for a window
+    without pairs).  One ``cross_overlaps`` call per window (in blocks of 32768 slot pairs), accumulated in the reference's loop order."""
+    n1 = len(ts1) if nsamples is None else min(int(nsamples), len(ts1))
+    n2 = len(ts2) if nsamples is None else min(int(nsamples), len(ts2))
+    ts1, ts2 = list(ts1[:n1]), list(ts2[:n2])
+    N = engine.X.N
+    mx2s, sx2s = [], []
+    for t_st in lr:
+        i1, j1 = get_ts_range(ts1, t_st)
+        i2, j2 = get_ts_range(ts2, t_st)
+        if i1 is None or i2 is None:
+            break
+        if j1 is None:
+            j1 = n1
+        if j2 is None:
+            j2 = n2
+        pa = [(k1, k2) for k1 in range(i1, j1) for k2 in range(i2, j2)]
+        mx2 = mx4 = 0.0
+        for c0 in range(0, len(pa), 32768):
+            blk = pa[c0:c0 + 32768]
+            q = engine.cross_overlaps([p[0] for p in blk], [p[1] for p in blk], rowsA=(r1, 1), rowsB=(r2, 1)).reshape(-1)
+            for v in q.tolist():                               # sequential accumulation, as the reference does
+                x = v / N
+                x2 = x * x
+                mx2 += x2
+                mx4 += x2 * x2
+        if pa:
+            mx2 /= len(pa)
+            mx4 /= len(pa)
+        else:
+            mx2 = mx4 = float("nan")                           # 0.0 / 0
+        d = mx4 - mx2 * mx2
+        mx2s.append(mx2)
+        sx2s.append(float("nan") if d != d else float(np.sqrt(max(0.0, d))))
+    return mx2s, sx2s
+
+
+def overlap_moments(hist, N):
+    """Moments of the overlap distribution P(q) from ``Engine.overlap_hist``: q = (N - 2d) / N for bin d.  The sums over the bins are exact
+    integers, divided once at the end.  Returns ``pairs``, ``q2`` = <q^2>, ``q4`` = <q^4>, ``absq`` = <|q|> and the Binder ratio
+    ``binder`` = (3 - <q^4> / <q^2>^2) / 2 (NaN where there are no pairs or <q^2> = 0)."""
+    N = int(N)
+    h = [int(v) for v in np.asarray(hist).reshape(-1)]
+    if len(h) != N + 1:
+        raise ValueError("a histogram over N = %d spins has %d bins, given %d" % (N, N + 1, len(h)))
+    pairs = sum(h)
+    s1 = sum(v * abs(N - 2 * d) for d, v in enumerate(h))
+    s2 = sum(v * (N - 2 * d) ** 2 for d, v in enumerate(h))
+    s4 = sum(v * (N - 2 * d) ** 4 for d, v in enumerate(h))
+    nan = float("nan")
+    if pairs == 0:
+        return {"pairs": 0, "q2": nan, "q4": nan, "binder": nan, "absq": nan}
+    return {"pairs": pairs, "q2": s2 / (pairs * N ** 2), "q4": s4 / (pairs * N ** 4), "absq": s1 / (pairs * N),
+            "binder": 0.5 * (3.0 - (s4 * pairs) / (s2 * s2)) if s2 else nan}
