@@ -884,6 +884,34 @@ RRRMC_API int32_t rrrmc_overlaps(rrrmc_ctx *ctx, int64_t npairs, const int32_t *
 RRRMC_API int32_t rrrmc_cross_overlaps(rrrmc_ctx *ctx, int64_t npairs, const int32_t *slotA, const int32_t *slotB, int64_t a0, int64_t nA,
                                        int64_t b0, int64_t nB, int32_t *q_out);
 RRRMC_API int32_t rrrmc_overlap_hist(rrrmc_ctx *ctx, int64_t npairs, const int32_t *slotA, const int32_t *slotB, int64_t *hist_out);
+/* Replica exchange (parallel tempering) between two contexts of ONE graph on one device: a temperature is a context, a ladder of T
+ * temperatures is T contexts, and ladder r is replica r of each of them.  For every replica r, with Ea[r], Eb[r] the energies of the two
+ * live configurations in the model's own units as Float64 (what rrrmc_energy / rrrmc_energy_f64 report; RRRMC_MODEL_SPARSE_LEVELS through
+ * rrrmc_set_level_scale),
+ *     dB = beta_a - beta_b;  dE = Ea[r] - Eb[r];  x = dB * dE          (three roundings, no fused multiply-add)
+ *     the two configurations are swapped  iff  x >= 0  or  u < det_exp(x)
+ * where u = ((w[0] << 32 | w[1]) >> 11) * 2^-53 and w = Philox4x32-10 with key (lo32(seed), hi32(seed)) and counter (lo32(round),
+ * hi32(round), replica0 + r, 14): the EXCHANGE stream, a function of (seed, round, global replica id) only.  The Float64 models
+ * recompute energy(X, C); the integer models take the exact tracked energy of a standardMC call when nothing has touched the
+ * configuration since, and recompute otherwise.  So an exchange is a pure function of the two configurations, the two betas, seed and round.
+ *   rrrmc_exchange_async    queues the exchange behind everything queued on BOTH contexts' streams, and everything queued on either
+ *                           later runs behind it (events between the two streams; no host synchronisation).  Afterwards both contexts
+ *                           are in the state rrrmc_set_spins leaves: no live run, caches stale, rrrmc_tracked_energy(_f64) answers
+ *                           RRRMC_ERR_STATE until the next sampling call; rrrmc_fetch_results still returns the last call's samples
+ *                           (they belong to the temperature, not to the walker) and rrrmc_iterations_done is unchanged
+ *   rrrmc_exchange_results  waits for the last exchange whose FIRST argument was `a` and returns swapped_out[R] (1 = swapped), their
+ *                           count, and the energies Ea_out[R], Eb_out[R] the verdicts were taken from (before the swap).  Any pointer
+ *                           may be NULL.  RRRMC_ERR_STATE when there was no such exchange
+ * Covered: RRRMC_MODEL_SPARSE_PM1 (the big-N and colour-sweep contexts included), SPARSE_LEVELS, SPARSE_F64, SK_NORMAL, SK_BINARY.
+ * The library does NOT compare the two contexts' disorder: the caller states that both hold the same graph (the Python driver builds
+ * every context from one graph object).  Two handles made by rrrmc_ctx_create_multi over the same device list exchange shard by shard.
+ * Refusals leave both contexts untouched and set rrrmc_last_error(a): RRRMC_ERR_INVALID_ARG for a NULL handle, a == b or a beta that is
+ * not finite; RRRMC_ERR_STATE when a context has no graph or no configuration, or model, N, K, R or replica0 differ;
+ * RRRMC_ERR_UNSUPPORTED for every other model (GraphQuant and the ensembles carry beta inside the Hamiltonian; the message names the
+ * model), for contexts on different devices, for unequal device lists, and for more than 65535 replica groups (the replicas that
+ * share a word of the native spin layout) per context or shard. */
+RRRMC_API int32_t rrrmc_exchange_async(rrrmc_ctx *a, rrrmc_ctx *b, double beta_a, double beta_b, uint64_t seed, uint64_t round);
+RRRMC_API int32_t rrrmc_exchange_results(rrrmc_ctx *a, uint8_t *swapped_out, int64_t *nswapped_out, double *Ea_out, double *Eb_out);
 /* GraphQuant observables of the live configuration of every replica (RRRMC_MODEL_QUANT_RRG):
  *   Qenergy_out[R]   Qenergy(X, C)            (src/graphs/QT.jl:253-268)
  *   tmag_out[R]      transverse_mag(X0, C, beta) (QT.jl:113-122)

@@ -1212,6 +1212,20 @@ function overlap_hist(ctx::Ctx, ia::Vector{Int32}, ib::Vector{Int32})
     GC.@preserve ia ib check(ccall((:rrrmc_overlap_hist, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}), ctx.p, length(ia), ia, ib, h), ctx.p)
     return h
 end
+"""
+    exchange!(a::Ctx, b::Ctx, βa, βb; seed, round)
+
+One replica-exchange attempt per replica between two contexts of the SAME graph on one device, `a` held at `βa` and `b` at `βb`
+(`rrrmc_exchange_async`): queued behind everything queued on either context, no host synchronisation.  Replica r of the two trades
+configurations iff `x = (βa - βb) * (Ea[r] - Eb[r]) >= 0` or `u < det_exp(x)`, `u` from the EXCHANGE stream of (seed, round, replica).
+The flags come back through `rrrmc_exchange_results`, whose `uint8_t*` argument this file's checked type table has no name for: read
+the outcome from the configurations (`get_spins`) or bind that call where it is needed.
+"""
+function exchange!(a::Ctx, b::Ctx, βa::Real, βb::Real; seed::Integer, round::Integer)
+    check(ccall((:rrrmc_exchange_async, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, UInt64, UInt64),
+                a.p, b.p, Float64(βa), Float64(βb), UInt64(seed), UInt64(round)), a.p)
+    return nothing
+end
 
 # ---- cache views for parity checks against the reference's own objects ----------------------------------------------------------------
 "X.cache.lfields of every replica (N × R), recomputed from the current spins for the integer models (src/Common.jl:27-36)"

@@ -32,7 +32,7 @@ SYMBOLS = [
     "rrrmc_standard_mc_f64", "rrrmc_fetch_results_f64", "rrrmc_gen_sk_gauss",
     "rrrmc_set_couplings_bits", "rrrmc_gen_sk_binary", "rrrmc_set_coloring", "rrrmc_colored_sweeps_async", "rrrmc_colored_count_accepted",
     "rrrmc_ctx_create_quant", "rrrmc_ctx_create_quant_sk", "rrrmc_ctx_create_quant_skn", "rrrmc_ctx_create_quant_f64", "rrrmc_quant_set_field", "rrrmc_quant_slice_form", "rrrmc_rrr_mc_async", "rrrmc_rrr_stats", "rrrmc_rrr_cache", "rrrmc_bkl_mc_async",
-    "rrrmc_snapshot_reserve", "rrrmc_snapshot_store", "rrrmc_snapshot_get", "rrrmc_overlaps", "rrrmc_cross_overlaps", "rrrmc_overlap_hist", "rrrmc_quant_observables",
+    "rrrmc_snapshot_reserve", "rrrmc_snapshot_store", "rrrmc_snapshot_get", "rrrmc_overlaps", "rrrmc_cross_overlaps", "rrrmc_overlap_hist", "rrrmc_exchange_async", "rrrmc_exchange_results", "rrrmc_quant_observables",
     "rrrmc_set_graph_f64", "rrrmc_gen_couplings_gauss", "rrrmc_set_graph_discretized", "rrrmc_set_level_scale", "rrrmc_discretize", "rrrmc_discretize_scaled", "rrrmc_wtm_mc_async", "rrrmc_wtm_times", "rrrmc_extremal_opt_async", "rrrmc_extremal_opt_results", "rrrmc_extremal_opt_results_f64",
     "rrrmc_ctx_create_re", "rrrmc_re_set_params", "rrrmc_re_energies", "rrrmc_re_tables",
     "rrrmc_ctx_create_le", "rrrmc_le_set_params", "rrrmc_le_energies", "rrrmc_le_cenergy", "rrrmc_le_distances", "rrrmc_le_tables",
@@ -219,6 +219,10 @@ def lib():
     L.rrrmc_cross_overlaps.argtypes = [vp, C.c_int64, _I32OrNull, _I32OrNull, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _I32OrNull]
     L.rrrmc_overlap_hist.restype = C.c_int32
     L.rrrmc_overlap_hist.argtypes = [vp, C.c_int64, _I32OrNull, _I32OrNull, _I64OrNull]
+    L.rrrmc_exchange_async.restype = C.c_int32
+    L.rrrmc_exchange_async.argtypes = [vp, vp, C.c_double, C.c_double, C.c_uint64, C.c_uint64]
+    L.rrrmc_exchange_results.restype = C.c_int32
+    L.rrrmc_exchange_results.argtypes = [vp, vp, C.POINTER(C.c_int64), vp, vp]
     L.rrrmc_quant_observables.restype = C.c_int32
     L.rrrmc_quant_observables.argtypes = [vp, C.c_double, C.c_double, vp, vp, vp]
     L.rrrmc_set_graph_f64.restype = C.c_int32

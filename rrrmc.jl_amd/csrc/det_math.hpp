@@ -1,7 +1,11 @@
 // Float64 helpers shared by every kernel that evaluates accept (src/RRRMC.jl:39) on a Float64 energy difference: the ACCEPT_F64 stream's
 // uniform and exp / log1p with a fixed operation order (the oracle evaluates the same sequences, so `rand() < exp(x)` agrees bit for bit).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#else
+#include <cmath>
+#endif
 #include <stdint.h>
 
 #include "philox.hpp"
@@ -21,6 +25,25 @@ RRRMC_HD double rand53(uint32_t k0, uint32_t k1, uint64_t g, uint32_t replica)
     return (double)(u >> 11) * 0x1.0p-53;
 }
 
+#if !defined(__HIPCC__)
+// The same sequence for a plain C++ compiler (the stand-alone check programs of the HIP-free cores, built with -ffp-contract=off): every
+// product and sum below rounds once, as __dmul_rn / __dadd_rn do on the device.
+inline double det_exp(double x)
+{
+    const double LOG2E = 1.44269504088896338700e+00;
+    const double LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
+    const double c[14] = {1.0, 1.0, 0.5, 1.0 / 6, 1.0 / 24, 1.0 / 120, 1.0 / 720, 1.0 / 5040, 1.0 / 40320, 1.0 / 362880,
+                          1.0 / 3628800, 1.0 / 39916800, 1.0 / 479001600, 1.0 / 6227020800.0};
+    if (x != x) return x;
+    if (x < -745.2) return 0.0;
+    if (x > 709.7) return HUGE_VAL;
+    const double k = std::floor(x * LOG2E + 0.5);
+    const double r = (x + -(k * LN2_HI)) + -(k * LN2_LO);
+    double p = c[13];
+    for (int n = 12; n >= 0; --n) p = p * r + c[n];
+    return std::ldexp(p, (int)k);
+}
+#else
 // exp(x) with a fixed operation order and no fused multiply-add: Cody-Waite reduction, degree-13 Taylor polynomial in
 // Horner form, exact scaling.  The oracle evaluates the same sequence, so `rand() < exp(x)` agrees bit for bit.
 __device__ __forceinline__ double det_exp(double x)
@@ -105,5 +128,6 @@ __device__ __forceinline__ double det_log1p(double y)
     const double r = __dadd_rn(__dmul_rn((double)e, LN2_HI), __dadd_rn(lg, __dmul_rn((double)e, LN2_LO)));
     return __dadd_rn(r, -__ddiv_rn(__dadd_rn(__dadd_rn(u, -1.0), -y), u));
 }
+#endif  // __HIPCC__
 
 }  // namespace rrrmc

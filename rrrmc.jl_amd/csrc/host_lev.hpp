@@ -69,5 +69,6 @@ int32_t lev_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_
     ctx->timing_valid = true;
     ctx->last_call_rrr = false;
     ctx->colored_call = false;
+    ctx->pt_E_live = true; ctx->pt_swapped = false;          // d_E: the tracked energy of the configuration the call left (exact)
     return RRRMC_OK;
 }

@@ -247,6 +247,7 @@ int32_t pm1_standard_mc_async(rrrmc_ctx* ctx, double beta, int64_t iters, int64_
     ctx->it_done += (uint64_t)iters;
     ctx->results_valid = true;
     ctx->timing_valid = true;
+    ctx->pt_E_live = true; ctx->pt_swapped = false;          // d_E: the tracked energy of the configuration the call left (exact)
     if (ctx->debug_checks) { rc = debug_check_pm1(ctx); if (rc) return rc; }
     return RRRMC_OK;
 }

@@ -35,6 +35,7 @@ typedef hipError_t dev_err_t;
 #include "obs_kernels.hpp"
 #include "layout_kernels.hpp"
 #include "xov_kernels.hpp"
+#include "pt_kernels.hpp"
 #include "spf_kernels.hpp"
 #include "spf_team_api.hpp"
 #include "spf_fast_kernels.hpp"
@@ -294,6 +295,13 @@ struct rrrmc_ctx {
     size_t xov_q_cap = 0;
     unsigned long long* xov_hist = nullptr;  // [N + 1]
     size_t xov_hist_cap = 0;
+    // ---- replica exchange between contexts (host_pt.hpp): allocated by the first exchange whose first argument this context is ----
+    uint32_t* pt_mask = nullptr;             // [ceil(Rpad / 32)] the verdicts of the last such exchange, one bit per replica
+    double* pt_E = nullptr;                  // [2][Rpad] the energies they were taken from: this context's, the partner's
+    hipEvent_t pt_ev[2] = {nullptr, nullptr};   // partner's stream -> this one before the swap, this one -> partner's after it
+    bool pt_valid = false;                   // pt_mask / pt_E hold an exchange's results
+    bool pt_E_live = false;                  // integer models: d_E is the energy of the live configuration (a standardMC call left it, nothing has touched the spins since)
+    bool pt_swapped = false;                 // integer models: an exchange rewrote the spins behind d_E; no tracked energy until the next sampling call
     // ---- GraphRobustEnsemble (ENS_RE of ens_models.hpp): spins in q_spins / qW (ABI site order), qNk / qM, slices in q_Jb (binary SK) or sk_J +
     //      q_slf / q_smv / q_scur (GraphSKNormal), the DeltaECache in q_cls / q_sv / q_spos / q_st / q_T / q_z, E in sk_E, counts in q_stats ----
     uint32_t* re_sp = nullptr;     // [R][qW] slice-major working copy of the spins
@@ -721,7 +729,7 @@ int32_t debug_check_pm1(rrrmc_ctx* ctx)
 }
 // ---- resumed calls of the reduced-rejection samplers ---------------------------------------------------------------------------------
 // anything that changes the configuration, the disorder, the streams' position or the caches behind the samplers' back ends the run
-inline void smp_drop(rrrmc_ctx* ctx) { if (ctx) ctx->smp_kind = 0; }
+inline void smp_drop(rrrmc_ctx* ctx) { if (ctx) { ctx->smp_kind = 0; ctx->pt_E_live = false; } }
 // Start of a sampler call of `kind` with the given parameters: *S describes it to the kernel.  The call CONTINUES the live run when the
 // context is in resume mode and the run is of the same sampler with the same parameters (the weights of the cache depend on them);
 // otherwise it starts a run as a reference call does: energy(X, C), a fresh cache (src/RRRMC.jl:175-178).
@@ -738,6 +746,7 @@ int32_t smp_begin(rrrmc_ctx* ctx, int kind, double p0, double p1, double p2, dou
     if (cont && kind == 4)
         cont = ctx->smp_ftau.size() == (size_t)ctx->N && std::memcmp(ctx->smp_ftau.data(), ftau, sizeof(double) * (size_t)ctx->N) == 0;
     ctx->smp_kind = 0;                  // live again once the call has been queued (smp_commit)
+    ctx->pt_E_live = false; ctx->pt_swapped = false;
     if (!cont) {
         ctx->smp_par[0] = p0; ctx->smp_par[1] = p1; ctx->smp_par[2] = p2; ctx->smp_par[3] = p3;
         ctx->smp_step = step; ctx->smp_g0 = ctx->it_done; ctx->smp_it = 0; ctx->smp_call = ctx->wtm_calls; ctx->smp_build = 0;
@@ -1058,6 +1067,7 @@ void rrrmc_ctx_destroy(rrrmc_ctx* ctx)
     dev_free_all(ctx);
     if (ctx->plan_stream) { (void)hipStreamSynchronize(ctx->plan_stream); (void)hipStreamDestroy(ctx->plan_stream); }
     if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
+    for (int i = 0; i < 2; ++i) if (ctx->pt_ev[i]) (void)hipEventDestroy(ctx->pt_ev[i]);
     for (hipEvent_t e : ctx->ev_plan) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) if (ctx->ev_set_free[i]) (void)hipEventDestroy(ctx->ev_set_free[i]);
     if (ctx->h_chunks) (void)hipHostFree(ctx->h_chunks);
@@ -1470,6 +1480,7 @@ int32_t rrrmc_tracked_energy(rrrmc_ctx* ctx, int64_t* E_out)
     if (!ctx || !E_out) return RRRMC_ERR_INVALID_ARG;
     if (!sparse_int_model(ctx)) return fail(ctx, RRRMC_ERR_STATE, "this model's energies are Float64: use rrrmc_tracked_energy_f64");
     if (!ctx->results_valid || !ctx->d_E) return fail(ctx, RRRMC_ERR_STATE, "no sampler call has left a tracked energy");
+    if (ctx->pt_swapped) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_exchange_async has rewritten the configuration since the last sampler call: no tracked energy describes it");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // the colour sweeps track no energy: d_E holds their last SAMPLE, taken before a sweep.  Evaluate the configuration they left instead
     // (nothing resumes from d_E after such a call)
@@ -1694,6 +1705,7 @@ int32_t rrrmc_colored_sweeps_async(rrrmc_ctx* ctx, double beta, int64_t sweeps, 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->results_valid = false; ctx->last_call_wtm = false; ctx->last_call_eo = false;
     ctx->timing_valid = false;
+    ctx->pt_swapped = false;
     const int64_t K = ctx->K, nsamp = sweeps / step;
     const size_t es_need = (size_t)(nsamp > 0 ? nsamp : 1) * ctx->Rpad;
     HIP_TRY(ctx, dev_grow(ctx, ctx->d_Es, ctx->Es_cap, es_need));
@@ -3061,11 +3073,22 @@ int32_t rrrmc_overlaps(rrrmc_ctx* ctx, int64_t npairs, const int32_t* slotA, con
 }
 
 #include "host_xov.hpp"
+#include "host_pt.hpp"
 
 int32_t rrrmc_cross_overlaps(rrrmc_ctx* ctx, int64_t npairs, const int32_t* slotA, const int32_t* slotB, int64_t a0, int64_t nA, int64_t b0, int64_t nB,
                              int32_t* q_out)
 {
     return xov_call(ctx, false, npairs, slotA, slotB, a0, nA, b0, nB, q_out, nullptr);
+}
+
+int32_t rrrmc_exchange_async(rrrmc_ctx* a, rrrmc_ctx* b, double beta_a, double beta_b, uint64_t seed, uint64_t round)
+{
+    return pt_exchange(a, b, beta_a, beta_b, seed, round);
+}
+
+int32_t rrrmc_exchange_results(rrrmc_ctx* a, uint8_t* swapped_out, int64_t* nswapped_out, double* Ea_out, double* Eb_out)
+{
+    return pt_results(a, swapped_out, nswapped_out, Ea_out, Eb_out);
 }
 
 int32_t rrrmc_overlap_hist(rrrmc_ctx* ctx, int64_t npairs, const int32_t* slotA, const int32_t* slotB, int64_t* hist_out)

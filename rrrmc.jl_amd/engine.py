@@ -375,6 +375,27 @@ class Engine:
         check(lib().rrrmc_overlap_hist(self._ctx, a.size, a, b, h), self._ctx)
         return h
 
+    # -- replica exchange between two engines of one graph (rrrmc.jl_amd/tempering.py drives a ladder of them) ---------------------
+    def exchange(self, other, beta_self, beta_other, seed, round, wait=True):
+        """One replica-exchange attempt per replica between this engine (held at ``beta_self``) and ``other`` (``beta_other``), two
+        engines of the SAME graph on one device: replica r of the two trades configurations iff ``x = (beta_self - beta_other) *
+        (E_self[r] - E_other[r]) >= 0`` or ``u < det_exp(x)``, u from the EXCHANGE stream of (seed, round, replica).  Queued behind
+        everything queued on either engine, with no host synchronisation.  Returns ``(swapped[R] bool, E_self[R], E_other[R])`` — the
+        energies before the swap — or, with ``wait=False``, nothing: ``exchange_results()`` fetches them later."""
+        if not isinstance(other, Engine):
+            raise TypeError("exchange: other must be an Engine")
+        check(lib().rrrmc_exchange_async(self._ctx, other._ctx, float(beta_self), float(beta_other), int(seed) & (2 ** 64 - 1),
+                                         int(round) & (2 ** 64 - 1)), self._ctx)
+        return self.exchange_results() if wait else None
+
+    def exchange_results(self):
+        """(swapped[R] bool, E_self[R], E_other[R]) of the last ``exchange`` this engine started; waits for it."""
+        sw = np.zeros(self.R, np.uint8)
+        Ea, Eb = np.zeros(self.R, np.float64), np.zeros(self.R, np.float64)
+        n = C.c_int64(0)
+        check(lib().rrrmc_exchange_results(self._ctx, sw.ctypes.data, C.byref(n), Ea.ctypes.data, Eb.ctypes.data), self._ctx)
+        return sw.astype(bool), Ea, Eb
+
     def quant_observables(self, beta=None, Gamma=None):
         """(Qenergy[R], transverse_mag[R], overlaps[R, M // 2]) of a GraphQuant (src/graphs/QT.jl:113-122, 213-268)."""
         X = self.X
