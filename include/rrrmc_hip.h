@@ -576,6 +576,11 @@ RRRMC_API int32_t rrrmc_tle_cache(rrrmc_ctx *ctx, int32_t *pos_out, int32_t *siz
 /* The kernel build of the last rrrMC call: 0 none yet, 1 the chain's hot state in LDS (chosen when it fits and all R wavefronts are
  * resident at once), 2 in global memory.  RRRMC_TLE_NO_LDS=1 forces 2, RRRMC_TLE_LDS=1 forces 1 whenever the state fits. */
 RRRMC_API int32_t rrrmc_tle_build(rrrmc_ctx *ctx, int32_t *build_out);
+/* The same for a Robust Ensemble or Local Entropy context (rrrmc_ctx_create_re, rrrmc_ctx_create_le and their _f64 forms): the kernel
+ * build of the last rrrMC call: 0 none yet, 1 one wavefront per replica with the chain's hot state (and the slices' Stabilities) in LDS,
+ * chosen when they fit 160 KiB, 2 one thread per replica in global memory.  RRRMC_RE_NO_LDS=1 / RRRMC_LE_NO_LDS=1 force 2.  standardMC
+ * has one build and leaves the value alone.  A multi-device context reports its first shard.  Other contexts: RRRMC_ERR_STATE. */
+RRRMC_API int32_t rrrmc_ens_build(rrrmc_ctx *ctx, int32_t *build_out);
 
 /* ---- GraphAddFields / GraphAddSubFields (src/graphs/AddFields.jl; RRRMC_MODEL_AF_*, RRRMC_MODEL_ASF_*) ------------
  * A DoubleGraph whose inner graph X0 = GraphAF(h) is a set of N independent external fields (energy(X0) = sum_i h_i sigma_i, left to

@@ -717,6 +717,12 @@ function tle_build(ctx::Ctx)
     check(ccall((:rrrmc_tle_build, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), ctx.p, b), ctx.p)
     return Int(b[])
 end
+# the same for a GraphRobustEnsemble or GraphLocalEntropy context
+function ens_build(ctx::Ctx)
+    b = Ref{Int32}(0)
+    check(ccall((:rrrmc_ens_build, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), ctx.p, b), ctx.p)
+    return Int(b[])
+end
 # Cc and C1[k] from a configuration of the whole graph (what energy(X, C) does, TLE.jl:413-435), before a user's hook runs: the reference's
 # own RRRMC.TLEenergies(X), cenergy(X) and distances(X) then read the sample's configuration
 function le_slices!(X::RRRMC.TLE.GraphTopologicalLocalEntropy{M}, C::RRRMC.Config) where {M}

@@ -34,7 +34,7 @@ SYMBOLS = [
     "rrrmc_ctx_create_quant", "rrrmc_ctx_create_quant_sk", "rrrmc_ctx_create_quant_skn", "rrrmc_ctx_create_quant_f64", "rrrmc_quant_set_field", "rrrmc_quant_slice_form", "rrrmc_rrr_mc_async", "rrrmc_rrr_stats", "rrrmc_rrr_cache", "rrrmc_bkl_mc_async",
     "rrrmc_snapshot_reserve", "rrrmc_snapshot_store", "rrrmc_snapshot_get", "rrrmc_overlaps", "rrrmc_cross_overlaps", "rrrmc_overlap_hist", "rrrmc_exchange_async", "rrrmc_exchange_results", "rrrmc_quant_observables",
     "rrrmc_set_graph_f64", "rrrmc_gen_couplings_gauss", "rrrmc_set_graph_discretized", "rrrmc_set_level_scale", "rrrmc_discretize", "rrrmc_discretize_scaled", "rrrmc_wtm_mc_async", "rrrmc_wtm_times", "rrrmc_extremal_opt_async", "rrrmc_extremal_opt_results", "rrrmc_extremal_opt_results_f64",
-    "rrrmc_ctx_create_re", "rrrmc_re_set_params", "rrrmc_re_energies", "rrrmc_re_tables",
+    "rrrmc_ctx_create_re", "rrrmc_re_set_params", "rrrmc_re_energies", "rrrmc_re_tables", "rrrmc_ens_build",
     "rrrmc_ctx_create_le", "rrrmc_le_set_params", "rrrmc_le_energies", "rrrmc_le_cenergy", "rrrmc_le_distances", "rrrmc_le_tables",
     "rrrmc_ctx_create_perc", "rrrmc_set_patterns", "rrrmc_gen_patterns",
     "rrrmc_ctx_create_comm", "rrrmc_ctx_create_comm_qu", "rrrmc_set_comm_patterns", "rrrmc_gen_comm_patterns",
@@ -329,6 +329,8 @@ def lib():
     L.rrrmc_tle_cache.argtypes = [vp, vp, vp]
     L.rrrmc_tle_build.restype = C.c_int32
     L.rrrmc_tle_build.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.rrrmc_ens_build.restype = C.c_int32
+    L.rrrmc_ens_build.argtypes = [vp, C.POINTER(C.c_int32)]
     L.rrrmc_ctx_create_af.restype = C.c_int32
     L.rrrmc_ctx_create_af.argtypes = [C.POINTER(vp), C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_uint32]
     L.rrrmc_af_set_fields.restype = C.c_int32

@@ -442,7 +442,7 @@ __global__ __launch_bounds__(kRrrThreads) void af_standard_kernel(AfParams A)
 }
 
 // debug mode (rrrmc_set_debug_checks): after a sampler call every chain's energy(X, C) is re-evaluated from its configuration and compared
-// with the tracked E (|ΔE| <= 1e-10, the bound of the reference's check, RRRMC.jl:250); g's cache is held as its own family's check holds
+// with the tracked E (|ΔE| <= 1e-10 max(1, |E|): the reference's check, RRRMC.jl:250, has an absolute 1e-10; relative once |E| > 1 is a deliberate departure, see re_check_kernel); g's cache is held as its own family's check holds
 // it; after rrrMC, ΔEs and the weights must equal their definitions on the final spins bit for bit.
 template <int SLICE>
 __global__ __launch_bounds__(64) void af_check_kernel(AfParams A, int cache)
@@ -458,8 +458,9 @@ __global__ __launch_bounds__(64) void af_check_kernel(AfParams A, int cache)
     if (!A.sub)
         for (int i = 0; i < N; ++i) E0 += A.h[i] * (double)(2 * sbit(sp, i) - 1);
     const double Eg = re_slice_energy<SLICE>(P, v, 0);
-    const double d = (A.sub ? Eg : E0 + Eg) - P.E_cur[r];
-    bad = bad || !(d <= 1e-10 && d >= -1e-10);
+    const double E = A.sub ? Eg : E0 + Eg;
+    const double d = E - P.E_cur[r], tol = 1e-10 * (E < -1.0 ? -E : E > 1.0 ? E : 1.0);          // relative once |E| > 1, as le_check_kernel
+    bad = bad || !(d <= tol && d >= -tol);
     if constexpr (SLICE == RE_SKN) {
         for (int i = 0; i < N; ++i) {
             const int si = sbit(sp, i);

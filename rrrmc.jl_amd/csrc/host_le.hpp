@@ -157,6 +157,7 @@ int32_t le_mc_async(rrrmc_ctx* ctx, bool standard, double beta, int64_t iters, i
         } else {
             hipLaunchKernelGGL(fn, dim3(rrr_blocks(ctx->R)), dim3(rrr_tpb(ctx->R)), 0, st, P);
         }
+        ctx->ens_build = use_lds ? 1 : 2;
     }
     HIP_TRY(ctx, hipGetLastError());
     return ens_call_end(ctx, P, C, standard, iters, [&] { return le_debug_check(ctx, P, !standard); });

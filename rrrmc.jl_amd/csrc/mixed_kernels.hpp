@@ -451,8 +451,9 @@ __global__ __launch_bounds__(64) void mixed_check_kernel(AfParams A, int cache)
     if (!A.sub)
         for (int i = 0; i < N; ++i) E0 += A.h[i] * (double)(2 * sbit(sp, i) - 1);
     const double Eg = mixed_energy(A.mx, P, v);
-    const double d = (A.sub ? Eg : E0 + Eg) - P.E_cur[r];
-    bad = bad || !(d <= 1e-10 && d >= -1e-10);
+    const double E = A.sub ? Eg : E0 + Eg;
+    const double d = E - P.E_cur[r], tol = 1e-10 * (E < -1.0 ? -E : E > 1.0 ? E : 1.0);          // relative once |E| > 1, as af_check_kernel
+    bad = bad || !(d <= tol && d >= -tol);
     bad = bad || mixed_state_bad(A.mx, P, v, sp, r);
     if (cache) {
         const double* dEs = A.dEs + (size_t)r * N;

@@ -814,7 +814,8 @@ __global__ __launch_bounds__(64) void re_energies_kernel(ReParams P)
 }
 
 // debug mode (rrrmc_set_debug_checks): after a sampler call every replica's energy(X, C) is re-evaluated from its configuration and compared
-// with the tracked E (|ΔE| <= 1e-10, the bound of the reference's check, RRRMC.jl:250); μ, and after rrrMC every site's class and the set
+// with the tracked E (|ΔE| <= 1e-10 max(1, |E|): the reference's check, RRRMC.jl:250, has an absolute 1e-10; relative once |E| > 1 is a deliberate departure — at N = 65 535 the
+// energy reaches 10^4 and the rounding of a thousand E += ΔE alone can exceed an absolute 1e-10); μ, and after rrrMC every site's class and the set
 // sizes, must equal what the configuration gives; GraphSKNormal slices: the cached fields within 1e-10 Nk of recomputed ones (sparse Float64
 // slices: within 1e-10 K).
 template <int SLICE>
@@ -835,8 +836,8 @@ __global__ __launch_bounds__(64) void re_check_kernel(ReParams P, int cache)
         E -= P.etab[(m + M) >> 1];
     }
     for (int k = 0; k < M; ++k) E += re_slice_energy<SLICE>(P, v, k);
-    const double d = E - P.E_cur[r];
-    bad = bad || !(d <= 1e-10 && d >= -1e-10);
+    const double d = E - P.E_cur[r], tol = 1e-10 * (E < -1.0 ? -E : E > 1.0 ? E : 1.0);          // relative once |E| > 1, as le_check_kernel
+    bad = bad || !(d <= tol && d >= -tol);
     if constexpr (SLICE == RE_SKN) {
         for (int k = 0; k < M; ++k)
             for (int i = 0; i < Nk; ++i) {

@@ -327,6 +327,7 @@ struct rrrmc_ctx {
     double tle_lT = 0.0;           // λT = λ / β (TLE.jl:390-396)
     bool tle_topology_set = false;
     int tle_build = 0;             // the build of the last rrrMC call: 1 hot state in LDS, 2 in global memory; 0 none yet
+    int ens_build = 0;             // the same for the Robust Ensemble and the Local Entropy ensemble (host_re.hpp, host_le.hpp)
     // ---- GraphAddFields / GraphAddSubFields (af_models.hpp; host_af.hpp): g is one slice (qM = 1, qNk = N) in the buffers its kind has
     //      above, spins in q_spins, z in q_z, acc_rate in q_accrate, E in sk_E, counts in q_stats ----
     double* af_h = nullptr;        // [N] the fields
@@ -2225,6 +2226,15 @@ int32_t rrrmc_tle_build(rrrmc_ctx* ctx, int32_t* build_out)
     if (is_multi(ctx)) return rrrmc_tle_build(ctx->kids[0], build_out);
     if (!is_tle(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_tle_build is for contexts made by rrrmc_ctx_create_tle");
     *build_out = ctx->tle_build;
+    return RRRMC_OK;
+}
+
+int32_t rrrmc_ens_build(rrrmc_ctx* ctx, int32_t* build_out)
+{
+    if (!ctx || !build_out) return RRRMC_ERR_INVALID_ARG;
+    if (is_multi(ctx)) return rrrmc_ens_build(ctx->kids[0], build_out);
+    if (!is_re(ctx) && !is_le(ctx)) return fail(ctx, RRRMC_ERR_STATE, "rrrmc_ens_build is for contexts made by rrrmc_ctx_create_re or rrrmc_ctx_create_le");
+    *build_out = ctx->ens_build;
     return RRRMC_OK;
 }
 

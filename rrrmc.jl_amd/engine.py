@@ -299,6 +299,13 @@ class Engine:
         check(lib().rrrmc_tle_build(self._ctx, C.byref(b)), self._ctx)
         return int(b.value)
 
+    def ens_build(self):
+        """the kernel build of the last rrrMC call on a GraphRobustEnsemble or GraphLocalEntropy: 1 hot state in LDS, 2 in global memory,
+        0 none yet"""
+        b = C.c_int32(0)
+        check(lib().rrrmc_ens_build(self._ctx, C.byref(b)), self._ctx)
+        return int(b.value)
+
     def re_energies(self):
         """REenergies (RE.jl:285-301) of the live configuration: (M,) for one replica, (R, M) otherwise.  Read-only: a run the engine
         continues is not disturbed."""

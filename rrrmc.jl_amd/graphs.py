@@ -48,12 +48,11 @@ class Config:
 
     @staticmethod
     def from_bits(bits):
-        bits = np.atleast_2d(np.asarray(bits)).astype(np.uint64)
+        bits = np.atleast_2d(np.asarray(bits))
         R, N = bits.shape
-        s = np.zeros((R, nchunks(N)), np.uint64)
-        x = np.arange(N)
-        np.bitwise_or.at(s, (np.arange(R)[:, None], (x >> 6)[None, :]), bits << (x & 63).astype(np.uint64))
-        return Config(N, R, s)
+        pad = np.zeros((R, 64 * nchunks(N)), np.uint8)          # bit x of a row is bit (x & 63) of chunk x >> 6: little-endian bit order
+        pad[:, :N] = bits
+        return Config(N, R, np.packbits(pad, axis=1, bitorder="little").view("<u8"))
 
 
 def level_units(LEV):
